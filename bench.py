@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- BASELINE.json's headline metric on MI355X: SIFT detect+describe + brute-force L2 match on 1080p pairs.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times exactly K steps and prints the headline line (`value`, `ms_per_step`, ...);
+--dump-outputs DIR also writes what the last timed step computed as DIR/*.npy (see dump_outputs). --full adds every
+secondary measurement and check: the matcher's per-launch roofline, latency probe, fp32-screen loop, pyramid and
+descriptor probes, drop-in C++ API loop, materialised distance, configs[3] and [4], CPU baseline, oracle check of pair 0,
+and the detail file.
 
 One process per GPU (torch.distributed/RCCL only for the barrier and the max-over-ranks clock; the path shards by
 frame pair, no data-path collective). A step = one batch of `--pairs` synthetic 1080p frame pairs per GPU, inputs
@@ -345,19 +351,22 @@ _ROOF_KEYS = ("kernel", "bound", "achieved", "peak", "unit", "frac", "traffic", 
 def compact_line(out, detail_path):
     """The stdout line: the contract's keys, `summary`, the roofline objects cut down to their figures, `cpu_baseline`, and the
     name of the side file that holds everything (notes, secondary measurements, per-rank lists). Pure; tests/test_bench_host.py
-    holds it under 6 KB on a full-size record."""
+    holds it under 6 KB on a full-size record. A headline-only record (no --full) gives the contract's keys, `config` and
+    the rates of the timed steps; detail_path None: no side file."""
     cut = lambda r: ({k: r[k] for k in _ROOF_KEYS if k in r and r[k] is not None} if isinstance(r, dict) else r)
     line = {k: out[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                                 "vs_baseline", "dtype", "data") if k in out}
     cfg = out.get("config") or {}
     line["config"] = {k: cfg[k] for k in ("workload", "match_screen", "pairs_per_gpu_per_step", "frames_per_detect_call",
                                           "pairs_per_match_call", "capacity", "parallelism") if k in cfg}
-    line["summary"] = out.get("summary")
+    if "summary" in out:
+        line["summary"] = out["summary"]
     for k in ("keypoints_per_s", "descriptor_comparisons_per_s", "value_f32_screen", "verified_pair0_vs_oracle", "rccl_ranks_seen",
               "ranks_seen_by_communicator"):
         if out.get(k) is not None:
             line[k] = out[k]
-    line["roofline"] = cut(out.get("roofline"))
+    if "roofline" in out:
+        line["roofline"] = cut(out["roofline"])
     for k in ("roofline_f32_screen", "roofline_distance"):
         if out.get(k) is not None:
             line[k] = cut(out[k])
@@ -377,7 +386,8 @@ def compact_line(out, detail_path):
             line[k] = {q: out[k][q] for q in keys if q in out[k]}
     if out.get("cpu_baseline") is not None:
         line["cpu_baseline"] = out["cpu_baseline"]
-    line["detail_file"] = detail_path
+    if detail_path is not None:
+        line["detail_file"] = detail_path
     return line
 
 
@@ -445,7 +455,70 @@ def parse_args(argv=None):
     ap.add_argument("--no-dropin", action="store_true", help="skip the secondary measurement of the drop-in C++ API loop")
     ap.add_argument("--no-latency", action="store_true", help="skip the batch-1 latency probe")
     ap.add_argument("--no-f32-loop", action="store_true", help="skip the second timed loop with the fp32 MFMA screen")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: per-launch event timing of the matcher and the roofline "
+                         "objects, the batch-1 latency probe, the fp32-screen loop, the pyramid and descriptor probes, the "
+                         "drop-in C++ API loop, the materialised distance, configs[3], configs[4], the CPU baseline and the "
+                         "oracle check of pair 0; writes the detail file (the --no-* options switch parts off). Without it a run "
+                         "sets up, warms up, times the steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last round of the last timed step computed (counts, keypoints, "
+                         "orientations, matches and a fixed sample of the descriptors of rank 0) as DIR/<name>.npy")
     return ap.parse_args(argv)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE_ROWS = 512        # descriptor rows sampled per frame at most (a whole set is ~6 MB per frame)
+
+
+def dump_outputs(path, arenas, results, counts):
+    """What the timed path hands its caller for the round it computed last, as float32 / float64 .npy files under `path`:
+    every frame's count, its keypoints (x, y, kpts, orients; frames back to back in arena order, frames 2i and 2i + 1 are
+    pair i), every pair's match indexes (-1 = none; pair i's query rows back to back) and a sample of every frame's
+    descriptor rows at fixed, seeded fractions of its count (two builds with the same counts sample the same rows). If the
+    per-keypoint arrays do not fit under DUMP_LIMIT_BYTES (more pairs than the default), they are sampled at the same rows.
+    Returns the bytes written."""
+    import numpy as np
+    import torch
+    counts = [int(c) for c in counts]
+    F = len(arenas)
+    K = max(16, min(DUMP_SAMPLE_ROWS, (DUMP_LIMIT_BYTES // 2) // (F * (128 * 4 + 8))))
+    frac = np.sort(np.random.default_rng(20261016).random(K))
+
+    def rows_of(n):
+        return np.minimum((frac * n).astype(np.int64), max(n - 1, 0))
+
+    # x, y, kpts, orients: 8 float32 per keypoint; one float64 match per query row; the descriptor sample and its rows
+    sampled = 32 * sum(counts) + 8 * sum(counts[0::2]) + F * K * (128 * 4 + 8) > DUMP_LIMIT_BYTES
+
+    def rows(t, n, nan_shape):
+        """Rows [0, n) of a device tensor, or its sampled rows (NaN when the frame has none)."""
+        if not sampled:
+            return t[:n].cpu().numpy()
+        if n == 0:
+            return np.full((K,) + nan_shape, np.nan)
+        return t[torch.from_numpy(rows_of(n)).to(t.device)].cpu().numpy()
+
+    out = {}
+    for name in ("x", "y", "kpts", "orients"):
+        out[name] = np.concatenate([rows(getattr(a, name), n, tuple(getattr(a, name).shape[1:]))
+                                    for a, n in zip(arenas, counts)]).astype(np.float32)
+    out["matches"] = np.concatenate([rows(results[i], counts[2 * i], ()) for i in range(len(results))]).astype(np.float64)
+    desc = np.full((F, K, 128), np.nan, np.float32)
+    desc_rows = np.full((F, K), -1.0)
+    for k, (a, n) in enumerate(zip(arenas, counts)):
+        if n > 0:
+            r = rows_of(n)
+            desc_rows[k] = r
+            desc[k] = a.desc[torch.from_numpy(r).to(a.desc.device)].cpu().numpy()
+    out.update({"num_items": np.asarray(counts, np.float64), "desc_sample": desc, "desc_sample_rows": desc_rows,
+                "per_keypoint_arrays_sampled": np.asarray([1.0 if sampled else 0.0])})
+    total = sum(v.nbytes for v in out.values())
+    assert total <= DUMP_LIMIT_BYTES, "outputs of %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES)
+    os.makedirs(path, exist_ok=True)
+    for name, v in out.items():
+        np.save(os.path.join(path, name + ".npy"), v)
+    return total
 
 
 def latency_probe(nm, torch, dev, frames4):
@@ -589,7 +662,7 @@ def main():
     # create, an arena's side stream can land on the caller's queue -- the call's two branches then run one after the other
     # (434 instead of 297 us per frame in the same process; the captured graph does not care).
     latency = None
-    if rank == 0 and not args.no_latency:
+    if args.full and rank == 0 and not args.no_latency:
         latency = latency_probe(nm, torch, dev, (frame_sets[0] + frame_sets[-1])[:2] + (frame_sets[0] + frame_sets[-1])[-2:])
     streams = [torch.cuda.Stream(device=dev) for _ in range(S)]
     mstream = torch.cuda.Stream(device=dev)
@@ -740,18 +813,22 @@ def main():
         return max(1, nm.match_pairs_per_launch(min(MB, P)))
 
     screen = nm.get_match_screen()
-    evs = mk_events(EV_STEPS * P)
+    # the match launches of the timed steps are bracketed by events only for the roofline objects of --full
+    evs = mk_events(EV_STEPS * P) if args.full else None
     for k in range(args.warmup * R):
         step(k, None, None)
     dt, ranks_ms = timed_loop(args.warmup * R, evs, hist)
     torch.cuda.synchronize()
     counts_host = hist.cpu().tolist()                 # [step][frame]: read AFTER the timed region
-    match_ms, match_fl = launch_times(evs, counts_host)
-    ppl_default = pairs_per_launch()
+    if args.dump_outputs and rank == 0:               # before anything else runs on the arenas
+        dump_outputs(args.dump_outputs, arenas, results, counts_host[NSUB - 1])
+    if args.full:
+        match_ms, match_fl = launch_times(evs, counts_host)
+        ppl_default = pairs_per_launch()
     last_set = (total_steps - 1) % n_sets
     # what the timed loop left in the arenas / results of pair 0, for the oracle check below
     snap = None
-    if rank == 0:
+    if args.full and rank == 0:
         nA, nB = counts_host[NSUB - 1][0], counts_host[NSUB - 1][1]
         snap = {"n": (nA, nB), "seeds": tuple(seeds_of(last_set)[:2]),
                 "kpts": [arenas[k].kpts[:n].cpu().numpy() for k, n in ((0, nA), (1, nB))],
@@ -772,7 +849,7 @@ def main():
     # the SAME timed loop with the fp32 MFMA screen (NM_MATCH_SCREEN=f32: north_star's "matcher on MFMA fp32"): its
     # whole-job value and its per-launch roofline come from a timed region of their own, not from a probe
     f32 = None
-    if screen != "f32" and not args.no_f32_loop:
+    if args.full and screen != "f32" and not args.no_f32_loop:
         try:
             nm.set_match_screen("f32")
             evs32 = mk_events(EV_STEPS * P)
@@ -801,65 +878,67 @@ def main():
     # call, every octave, timed with events on the stream they run on
     frames = frame_sets[0]
     pyr_all_ms = pyr_nodog_ms = pyr_dogonly_ms = None
-    try:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        with torch.cuda.stream(mstream):
-            for _ in range(3):
-                nm.scale_space_batch(arenas[:B], frames[:B])
-            reps = 20
-            e0.record()
-            for _ in range(reps):
-                nm.scale_space_batch(arenas[:B], frames[:B])
-            e1.record()
-            for _ in range(5):                  # the octave-0 part of the same chain, through the library's profile hook
-                nm.profile_events(nm.PROF_PYRAMID_O0, ev_pyr[0][0], ev_pyr[0][1])
-                nm.scale_space_batch(arenas[:B], frames[:B])
-                nm.profile_events(nm.PROF_PYRAMID_O0, None, None)
-                mstream.synchronize()
-                pyr_ms.append(ev_pyr[0][0].elapsed_time(ev_pyr[0][1]))
-            e2, e3 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            nm.scale_space_batch(arenas[:B], frames[:B], write_dog=False)
-            e2.record()
-            for _ in range(reps):
+    if args.full:
+        try:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            with torch.cuda.stream(mstream):
+                for _ in range(3):
+                    nm.scale_space_batch(arenas[:B], frames[:B])
+                reps = 20
+                e0.record()
+                for _ in range(reps):
+                    nm.scale_space_batch(arenas[:B], frames[:B])
+                e1.record()
+                for _ in range(5):                  # the octave-0 part of the same chain, through the library's profile hook
+                    nm.profile_events(nm.PROF_PYRAMID_O0, ev_pyr[0][0], ev_pyr[0][1])
+                    nm.scale_space_batch(arenas[:B], frames[:B])
+                    nm.profile_events(nm.PROF_PYRAMID_O0, None, None)
+                    mstream.synchronize()
+                    pyr_ms.append(ev_pyr[0][0].elapsed_time(ev_pyr[0][1]))
+                e2, e3 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 nm.scale_space_batch(arenas[:B], frames[:B], write_dog=False)
-            e3.record()
-            e4, e5 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            nm.scale_space_batch(arenas[:B], frames[:B], write_dog=True, write_grad=False)
-            e4.record()
-            for _ in range(reps):
+                e2.record()
+                for _ in range(reps):
+                    nm.scale_space_batch(arenas[:B], frames[:B], write_dog=False)
+                e3.record()
+                e4, e5 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 nm.scale_space_batch(arenas[:B], frames[:B], write_dog=True, write_grad=False)
-            e5.record()
-        mstream.synchronize()
-        pyr_all_ms = e0.elapsed_time(e1) / reps
-        pyr_nodog_ms = e2.elapsed_time(e3) / reps
-        pyr_dogonly_ms = e4.elapsed_time(e5) / reps
-    except Exception:
-        pyr_all_ms = None
+                e4.record()
+                for _ in range(reps):
+                    nm.scale_space_batch(arenas[:B], frames[:B], write_dog=True, write_grad=False)
+                e5.record()
+            mstream.synchronize()
+            pyr_all_ms = e0.elapsed_time(e1) / reps
+            pyr_nodog_ms = e2.elapsed_time(e3) / reps
+            pyr_dogonly_ms = e4.elapsed_time(e5) / reps
+        except Exception:
+            pyr_all_ms = None
 
     # descriptor kernel of one B-frame detect call alone (library profile hook; chip otherwise idle), against the VALU issue
     # rate: it is the largest single kernel of a step and has no memory or MFMA yardstick
     desc_roof = None
-    try:
-        ed = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(6)]
-        ms_d = []
-        with torch.cuda.stream(mstream):
-            for a, b in ed:                      # torch creates the HIP event at its first record
-                a.record(); b.record()
-            for a, b in ed:
-                nm.profile_events(nm.PROF_DESCRIBE, a, b)
-                nm.detect_describe_batch(arenas[:B], frames[:B])
-                nm.profile_events(nm.PROF_DESCRIBE, None, None)
-        mstream.synchronize()
-        ms_d = sorted(a.elapsed_time(b) for a, b in ed[1:])
-        kp_call = float(sum(int(a.num_items.item()) for a in arenas[:B]))
-        desc_roof = describe_report(B, ms_d[len(ms_d) // 2], kp_call, load_traffic())
-    except Exception as e:
-        desc_roof = {"error": repr(e)}
+    if args.full:
+        try:
+            ed = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(6)]
+            ms_d = []
+            with torch.cuda.stream(mstream):
+                for a, b in ed:                      # torch creates the HIP event at its first record
+                    a.record(); b.record()
+                for a, b in ed:
+                    nm.profile_events(nm.PROF_DESCRIBE, a, b)
+                    nm.detect_describe_batch(arenas[:B], frames[:B])
+                    nm.profile_events(nm.PROF_DESCRIBE, None, None)
+            mstream.synchronize()
+            ms_d = sorted(a.elapsed_time(b) for a, b in ed[1:])
+            kp_call = float(sum(int(a.num_items.item()) for a in arenas[:B]))
+            desc_roof = describe_report(B, ms_d[len(ms_d) // 2], kp_call, load_traffic())
+        except Exception as e:
+            desc_roof = {"error": repr(e)}
 
     # the reference's own C++ API driven the way a NiftyMatch application drives it (SiftParams / PyramidData / SiftData +
     # the per-octave compute_* calls + compute_sift_matches), on one pair, one host thread, one stream; not part of `value`
     dropin = None
-    if rank == 0 and not args.no_dropin:
+    if args.full and rank == 0 and not args.no_dropin:
         try:
             import ctypes as C
             dropin = {"workload": "drop-in C++ API client loop on the 1080p pair (nm/src/nm_client.cpp: 2 x per-octave "
@@ -878,7 +957,7 @@ def main():
     # `distance`): the fp32 MFMA pass (distance_mfma_kernel, library profile site) and the whole call, beside the exact VALU
     # kernel's call; its own roofline entry -- MFMA fp32 by the 2 N M 128 flops, and the N x M x 4 bytes it writes
     dist_roof = None
-    if rank == 0 and not args.no_dropin:
+    if args.full and rank == 0 and not args.no_dropin:
         try:
             nm.detect_describe_batch(arenas[:2], frames[:2])
             torch.cuda.synchronize()
@@ -923,14 +1002,14 @@ def main():
             dist_roof = {"error": repr(exc)}
 
     detect256 = None
-    if not args.no_detect256:
+    if args.full and not args.no_detect256:
         try:
             detect256 = detect_256(nm, torch, dist, dev, cdev, rank, world, arenas, streams, B)
         except Exception as exc:
             detect256 = {"error": repr(exc)}
 
     extra = None
-    if not args.no_allpairs:
+    if args.full and not args.no_allpairs:
         for a in arenas:                     # give the memory back before the 100k x 100k workspaces
             a.close()
         frame_sets = frames = None
@@ -941,7 +1020,35 @@ def main():
 
     if rank == 0:
         pairs_total = P * R * world * args.steps
-        nA, nB = snap["n"]
+        nA, nB = counts_host[NSUB - 1][0], counts_host[NSUB - 1][1]
+        out = {
+            "metric": METRIC, "value": round(pairs_total / dt, 3), "unit": "frame-pairs/s", "n_gpus": world,
+            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * dt / args.steps, 3),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": DTYPE.get(screen, "f32"), "data": "synthetic",
+            "config": {"workload": "configs[2]: SIFT detect+describe x2 + fused BF L2 match per 1920x1080 pair",
+                       "match_screen": {"f16": "two-stage: f16 coarse pass + bf16x3 second pass on the unproven rows"}.get(screen, screen),
+                       "match_sizes": "device",
+                       "frames": "fresh every round: %d distinct sets of %d frames per rank, round q on set q mod %d "
+                                 "((warmup + steps) x rounds = %d)" % (n_sets, 2 * P, n_sets, total_steps),
+                       "pairs_per_gpu_per_step": P * R, "rounds_per_step": R, "pairs_per_round": P,
+                       "detect_streams": S, "frames_per_detect_call": B,
+                       "host_enqueue_threads": T, "match_streams": MS, "pairs_per_match_call": MB,
+                       "phases": "overlapped" if (args.overlap and B % 2 == 0) else "detect then match",
+                       "match_pipeline": ("PREP / FINISH of neighbouring calls on a helper stream beside the MFMA launches" if pipeline
+                                          else "whole calls on %d stream(s)" % MS),
+                       "keypoints_pair0_last_step": [nA, nB], "capacity": CAP,
+                       "parallelism": "frame-pair sharding, %d rank(s), no data-path collective" % world},
+            "keypoints_per_s": round(kp_all / dt, 1),
+            "descriptor_comparisons_per_s": round(cmp_all / dt, 1),
+            "per_rank_ms": [round(v, 3) for v in ranks_ms],
+            "ranks_seen_by_communicator": ranks_seen, "backend": (args.backend if world > 1 else None),
+        }
+        if world > 1 and args.backend == "nccl":
+            out["rccl_ranks_seen"] = ranks_seen
+        if not args.full:
+            print(json.dumps(compact_line(out, None)))
+
+    if rank == 0 and args.full:
         m_ms = sum(match_ms) / len(match_ms)            # every event-timed MFMA launch of the timed region
         p_ms = sum(pyr_ms) / len(pyr_ms) if pyr_ms else float("nan")
         traffic = load_traffic()
@@ -996,33 +1103,9 @@ def main():
         if snap.get("rows"):
             roof["rows_second_pass_sample"], roof["rows_exact_fallback_sample"] = snap["rows"]     # first pair of the last match call
         head = {}
-        out = {
-            "metric": METRIC, "value": round(pairs_total / dt, 3), "unit": "frame-pairs/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * dt / args.steps, 3),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": DTYPE.get(screen, "f32"), "data": "synthetic",
-            "config": {"workload": "configs[2]: SIFT detect+describe x2 + fused BF L2 match per 1920x1080 pair",
-                       "match_screen": {"f16": "two-stage: f16 coarse pass + bf16x3 second pass on the unproven rows"}.get(screen, screen),
-                       "match_sizes": "device",
-                       "frames": "fresh every round: %d distinct sets of %d frames per rank, round q on set q mod %d "
-                                 "((warmup + steps) x rounds = %d)" % (n_sets, 2 * P, n_sets, total_steps),
-                       "pairs_per_gpu_per_step": P * R, "rounds_per_step": R, "pairs_per_round": P,
-                       "detect_streams": S, "frames_per_detect_call": B,
-                       "host_enqueue_threads": T, "match_streams": MS, "pairs_per_match_call": MB,
-                       "phases": "overlapped" if (args.overlap and B % 2 == 0) else "detect then match",
-                       "match_pipeline": ("PREP / FINISH of neighbouring calls on a helper stream beside the MFMA launches" if pipeline
-                                          else "whole calls on %d stream(s)" % MS),
-                       "keypoints_pair0_last_step": [nA, nB], "capacity": CAP,
-                       "parallelism": "frame-pair sharding, %d rank(s), no data-path collective" % world},
-            "keypoints_per_s": round(kp_all / dt, 1),
-            "descriptor_comparisons_per_s": round(cmp_all / dt, 1),
-            "per_rank_ms": [round(v, 3) for v in ranks_ms],
-            "ranks_seen_by_communicator": ranks_seen, "backend": (args.backend if world > 1 else None),
-            "roofline": roof,
-            "roofline_pyramid": roofline_pyramid(B, p_ms, pyr_all_ms, traffic, pyr_nodog_ms, pyr_dogonly_ms),
-            "describe": desc_roof,
-        }
-        if world > 1 and args.backend == "nccl":
-            out["rccl_ranks_seen"] = ranks_seen
+        out.update({"roofline": roof,
+                    "roofline_pyramid": roofline_pyramid(B, p_ms, pyr_all_ms, traffic, pyr_nodog_ms, pyr_dogonly_ms),
+                    "describe": desc_roof})
         if f32 is not None:
             if "error" in f32:
                 out["roofline_f32_screen"] = {"error": f32["error"]}
@@ -1086,7 +1169,7 @@ def main():
                      "detect_256_frames_per_s": (detect256 or {}).get("frames_per_s")})
         out["summary"] = head
         # ONE short line on stdout (the driver keeps a tail of stdout: VERDICT r5 asked for < 6 KB); everything else in a side file
-        detail = os.environ.get("NM_BENCH_DETAIL", os.path.join(_ROOT, "gpurun_out", "bench_detail.json"))
+        detail = os.environ.get("NM_BENCH_DETAIL", os.path.join(_ROOT, "bench_out", "bench_detail.json"))
         try:
             os.makedirs(os.path.dirname(detail), exist_ok=True)
             json.dump(out, open(detail, "w"), indent=1)

@@ -143,3 +143,88 @@ def test_stdout_line_is_short_and_complete():
                     yield k, v
                 yield from fracs(v)
     assert all(v <= 1.0 for _, v in fracs(line)), list(fracs(line))
+
+
+def test_full_and_dump_outputs_are_opt_in():
+    """A plain run is headline-only: --full and --dump-outputs are off unless given."""
+    import bench
+    a = bench.parse_args(["--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and a.full is False and a.dump_outputs is None
+    a = bench.parse_args(["--full", "--dump-outputs", "out"])
+    assert a.full is True and a.dump_outputs == "out"
+
+
+def test_headline_line_without_full():
+    """The line of a plain run: every contract key, the config and the rates of the timed steps; no side file, no
+    roofline, no summary (they come with --full)."""
+    import json
+    import bench
+    out = {"metric": bench.METRIC, "value": 3176.9, "unit": "frame-pairs/s", "n_gpus": 1, "steps": 20, "warmup": 5,
+           "ms_per_step": 50.363, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": bench.DTYPE["f16"],
+           "data": "synthetic", "config": {"workload": "configs[2]: ...", "pairs_per_gpu_per_step": 160, "capacity": 16384},
+           "keypoints_per_s": 7.6e7, "descriptor_comparisons_per_s": 4.6e11, "per_rank_ms": [1007.3], "ranks_seen_by_communicator": 1}
+    line = bench.compact_line(out, None)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "config"):
+        assert line[k] == out[k], k
+    assert not {"detail_file", "roofline", "summary"} & set(line)
+    assert json.loads(json.dumps(line)) == line
+
+
+def _host_arenas(counts, cap=64, seed=3):
+    """Stand-ins for SiftArena with the tensors dump_outputs reads, on the host, filled with distinct values."""
+    import types
+    import torch
+    g = torch.Generator().manual_seed(seed)
+    ar = [types.SimpleNamespace(desc=torch.rand((cap, 128), generator=g), x=torch.rand(cap, generator=g),
+                                y=torch.rand(cap, generator=g), kpts=torch.rand((cap, 4), generator=g),
+                                orients=torch.rand((cap, 2), generator=g)) for _ in counts]
+    res = [torch.randint(-1, cap, (cap,), generator=g, dtype=torch.int32) for _ in counts[0::2]]
+    return ar, res
+
+
+def test_dump_outputs_writes_what_the_caller_receives(tmp_path):
+    """Every array float32 / float64, rows [0, n) of every frame back to back, pair i's match indexes over frame 2i's
+    rows, the descriptor sample at the rows it names; the same counts give the same sample."""
+    import bench
+    counts = [5, 7, 0, 3, 64, 1]
+    ar, res = _host_arenas(counts)
+    total = bench.dump_outputs(str(tmp_path / "a"), ar, res, counts)
+    d = {f[:-4]: np.load(str(tmp_path / "a" / f)) for f in os.listdir(str(tmp_path / "a"))}
+    assert total == sum(v.nbytes for v in d.values()) <= bench.DUMP_LIMIT_BYTES
+    assert all(v.dtype in (np.float32, np.float64) for v in d.values())
+    assert d["num_items"].tolist() == counts and d["per_keypoint_arrays_sampled"].tolist() == [0.0]
+    off = np.cumsum([0] + counts)
+    for k, (a, n) in enumerate(zip(ar, counts)):
+        assert np.array_equal(d["kpts"][off[k]:off[k + 1]], a.kpts[:n].numpy())
+        assert np.array_equal(d["orients"][off[k]:off[k + 1]], a.orients[:n].numpy())
+        assert np.array_equal(d["x"][off[k]:off[k + 1]], a.x[:n].numpy())
+        assert np.array_equal(d["y"][off[k]:off[k + 1]], a.y[:n].numpy())
+        rows = d["desc_sample_rows"][k]
+        if n == 0:
+            assert (rows == -1).all() and np.isnan(d["desc_sample"][k]).all()
+        else:
+            assert rows.min() >= 0 and rows.max() < n and np.array_equal(np.sort(rows), rows)
+            assert np.array_equal(d["desc_sample"][k], a.desc.numpy()[rows.astype(np.int64)])
+    qoff = np.cumsum([0] + counts[0::2])
+    for i, r in enumerate(res):
+        assert np.array_equal(d["matches"][qoff[i]:qoff[i + 1]], r[:counts[2 * i]].numpy().astype(np.float64))
+    bench.dump_outputs(str(tmp_path / "b"), ar, res, counts)
+    for f in os.listdir(str(tmp_path / "a")):
+        assert np.array_equal(np.load(str(tmp_path / "a" / f)), np.load(str(tmp_path / "b" / f)), equal_nan=True), f
+
+
+def test_dump_outputs_samples_what_does_not_fit(tmp_path, monkeypatch):
+    """Outputs larger than the limit: the per-keypoint arrays are sampled at the descriptor sample's rows and the total
+    stays under the limit."""
+    import bench
+    counts = [600, 500, 400, 0]
+    ar, res = _host_arenas(counts, cap=1024)
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 40 << 10)
+    total = bench.dump_outputs(str(tmp_path), ar, res, counts)
+    d = {f[:-4]: np.load(str(tmp_path / f)) for f in os.listdir(str(tmp_path))}
+    assert d["per_keypoint_arrays_sampled"].tolist() == [1.0] and total <= 40 << 10
+    K = d["desc_sample_rows"].shape[1]
+    assert d["kpts"].shape == (K * len(counts), 4) and d["matches"].shape == (K * 2,)
+    rows = d["desc_sample_rows"][1].astype(np.int64)
+    assert np.array_equal(d["kpts"][K:2 * K], ar[1].kpts.numpy()[rows])
+    assert np.isnan(d["kpts"][3 * K:]).all()

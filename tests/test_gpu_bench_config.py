@@ -204,3 +204,42 @@ def test_detect_256_loop_of_the_bench(nm, oracle, cuda):
     single.close()
     for a in arenas:
         a.close()
+
+
+def test_bench_dump_outputs_equal_the_oracle(oracle, tmp_path):
+    """`bench.py --dump-outputs DIR` end to end at a small size (2 pairs per round, one round per step, 1 warm-up + 1 timed
+    step on two frame sets): the headline line names exactly the timed steps and no side file, and what it writes for
+    pair 0 of the last timed step -- counts, keypoints, orientations, the descriptor sample, the match indexes -- equals the
+    oracle on that pair's frames (set 1 = seeds 4, 5) bit for bit."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    import bench
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out_dir = str(tmp_path / "dump")
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1",
+                        "--pairs", "2", "--rounds", "1", "--frame-sets", "2", "--batch", "4", "--streams", "1",
+                        "--match-batch", "2", "--dump-outputs", out_dir], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert line["steps"] == 1 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert "detail_file" not in line and "roofline" not in line
+    d = {f[:-4]: np.load(os.path.join(out_dir, f)) for f in os.listdir(out_dir)}
+    assert sum(v.nbytes for v in d.values()) <= bench.DUMP_LIMIT_BYTES
+    assert bench.seeds_of_set(1, 1, 0, 2)[:2] == [4, 5]
+    refs = [oracle.sift_detect_describe(H.blurred_frame(s, W, H_), CAP) for s in (4, 5)]
+    counts = d["num_items"].astype(np.int64).tolist()
+    assert len(counts) == 4 and counts[:2] == [refs[0]["n"], refs[1]["n"]]
+    off = 0
+    for k, ref in enumerate(refs):
+        n = ref["n"]
+        assert np.array_equal(d["kpts"][off:off + n], ref["kpts"]), k
+        assert np.array_equal(d["x"][off:off + n], ref["x"]) and np.array_equal(d["y"][off:off + n], ref["y"]), k
+        assert np.array_equal(d["orients"][off:off + n], ref["orient"]), k
+        rows = d["desc_sample_rows"][k].astype(np.int64)
+        assert np.array_equal(d["desc_sample"][k], ref["desc"][rows]), k
+        off += n
+    want, _, _ = oracle.sift_matches(refs[0]["desc"], refs[1]["desc"], 0.8, want_distance=False)
+    assert np.array_equal(d["matches"][:refs[0]["n"]], want.astype(np.float64))

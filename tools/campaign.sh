@@ -1,5 +1,5 @@
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-timeout -k 10 400 python bench.py --steps 20 --warmup 5 > gpurun_out/r05_n_bench.json 2> gpurun_out/r05_n_bench.err; python tools/show_bench.py gpurun_out/r05_n_bench.json | cut -c1-300
+mkdir -p bench_out && timeout -k 10 400 python bench.py --full --steps 20 --warmup 5 > bench_out/r05_n_bench.json 2> bench_out/r05_n_bench.err; python tools/show_bench.py bench_out/r05_n_bench.json | cut -c1-300
 echo "--- profiled headline-only run"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d gpurun_out/r05_n_prof -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-allpairs --no-detect256 --no-dropin --no-latency --no-f32-loop > gpurun_out/r05_n_bench_headline_only_profiled.json 2> gpurun_out/r05_n_prof.err
 python tools/prof_summary.py gpurun_out/r05_n_prof 90 > gpurun_out/r05_n_bench_headline_only_kernel_summary.txt 2>&1; head -30 gpurun_out/r05_n_bench_headline_only_kernel_summary.txt | cut -c1-130

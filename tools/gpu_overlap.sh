@@ -1,6 +1,6 @@
 # usage (GPU box): bash tools/gpu_overlap.sh  -- headline-only bench under stream / batch / grid-cap combinations (r06_d)
 cd $GRAFT_REPO_ROOT
-F="--steps 20 --warmup 5 --no-cpu-baseline --no-allpairs --no-detect256 --no-dropin --no-latency --no-f32-loop"
+F="--full --steps 20 --warmup 5 --no-cpu-baseline --no-allpairs --no-detect256 --no-dropin --no-latency --no-f32-loop"
 P='import sys,json; d=json.loads([l for l in sys.stdin if l.startswith("{")][-1]); print(sys.argv[1], d["value"], d["summary"].get("verified_pair0_vs_oracle"))'
 run() { name="$1"; shift; env "$@" timeout -k 10 200 python bench.py $F $EXTRA 2>/dev/null | python -c "$P" "$name" || exit 1; }
 for i in 1 2; do
