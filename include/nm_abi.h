@@ -440,6 +440,39 @@ NM_API int nm_ransac_f32(int model, const float *src_x, const float *src_y, cons
 /* Seed of the host-side sampler used by the C++ ransac_* wrappers (0 = std::random_device, the reference's behaviour). */
 NM_API void nm_ransac_seed(unsigned int seed);
 
+/* Batched RANSAC with DEVICE-side sampling (no reference counterpart): n <= NM_RANSAC_MAX_BATCH frame pairs in three
+ * launches on `stream`, no allocation, no synchronisation, no host read -- capturable into a HIP graph together with
+ * nm_sift_match_batch_dev_f32. Pair k (arrays of n):
+ *   src_x/src_y[k]  frame A's keypoint coordinates (e.g. an arena's x / y), dst_x/dst_y[k] frame B's;
+ *   matches[k]      the pair's result of nm_sift_match_batch[_dev]_f32 (row i of A -> a row of B, or -1);
+ *   d_nA[k]         DEVICE int, A's row count (e.g. the arena's num_items), clipped to [0, capA]; rows beyond it are never read.
+ * The valid rows V_k are the rows i < min(nA, capA), ascending, with matches[k][i] >= 0 and src_x[k][i] >= 0 (exactly the rows
+ * where align_points leaves c_src_x >= 0); m_k = |V_k|. Hypothesis t, sample s of S = 1, 2, 4 samples (model 0, 1, 2) uses row
+ * V_k[j], j = nm_ransac_batch_sample(seeds[k], t, s, S, m_k): SplitMix64 of c = (seed << 32) | (t S + s), i.e.
+ *   z = c + 0x9E3779B97F4A7C15; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^= z >> 31;
+ *   j = ((z >> 32) * m) >> 32                                                         (64-bit unsigned arithmetic)
+ * seeds is a HOST array of n. A pair's result depends only on its own inputs and seed, never on its slot in the call. Fit,
+ * repeated-index rule and inlier test are those of nm_ransac_f32, so the results equal nm_ransac_f32 on the aligned rows with
+ * rand_list[t][s] = V_k[j], bit for bit. Outputs (device): H_best n x 9 (the hypothesis at the FIRST maximum of the counts),
+ * best_inliers n, position n, status n (1; 0 when m_k is below the model's minimum of 2, 2, 4 points -- then H_best is 0,
+ * best_inliers 0, position -1). Optional (may be NULL): homographies n x iterations x 9, inliers n x iterations, every
+ * hypothesis (rows of a status-0 pair are zero). workspace: nm_ransac_batch_dev_workspace_bytes(n, capA, iterations) bytes
+ * (0 for arguments out of range). The call returns hipErrorInvalidValue, touching no device memory, for model not in
+ * {0, 1, 2}, n not in [1, 64], iterations not in [1, 2^20], capA not in [1, 2^22), a non-finite threshold or a NULL required
+ * pointer. The C++ ransac_* wrappers keep the reference's host mt19937 sampler: this entry draws different samples.    */
+#define NM_RANSAC_MAX_BATCH 64
+#define NM_RANSAC_MAX_ITERATIONS (1 << 20)
+NM_API size_t nm_ransac_batch_dev_workspace_bytes(int n, int capA, int iterations);
+NM_API int nm_ransac_batch_dev_f32(int model, int n,
+                                   const float *const *src_x, const float *const *src_y, const int *const *d_nA, int capA,
+                                   const float *const *dst_x, const float *const *dst_y, const int *const *matches,
+                                   int iterations, float inlier_threshold, const unsigned int *seeds,
+                                   float *H_best, int *best_inliers, int *position, int *status,
+                                   float *homographies, int *inliers, void *workspace, void *stream);
+/* Host-only: the batched entry's sampler, for tests and for clients that reproduce a draw. Returns j in [0, m), or -1 for
+ * samples not in {1, 2, 4}, sample not in [0, samples), hypothesis not in [0, 2^20) or m < 1.                          */
+NM_API int nm_ransac_batch_sample(unsigned int seed, int hypothesis, int sample, int samples, int m);
+
 /* ---- per-frame driver ---- */
 /* The per-octave client loop the reference leaves to its caller, run entirely on `stream` with no
  * host synchronisation and no allocation: Gaussian pyramid + DoG + gradients + extrema + ordered compaction +

@@ -100,6 +100,9 @@ _SIGNATURES = {
     "nm_transform_blend": (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _P, _I, _I, _P, _I, _P, _P, _I, _P]),
     "nm_ransac_f32": (_I, [_I, _P, _P, _P, _P, _I, _P, _I, _F, _P, _P, _P, _P, _P]),
     "nm_ransac_seed": (None, [C.c_uint]),
+    "nm_ransac_batch_dev_workspace_bytes": (_SZ, [_I, _I, _I]),
+    "nm_ransac_batch_dev_f32": (_I, [_I, _I, _P, _P, _P, _I, _P, _P, _P, _I, _F, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "nm_ransac_batch_sample": (_I, [C.c_uint, _I, _I, _I, _I]),
     "nm_sift_arena_create": (_I, [_I, _I, _I, _P]),
     "nm_sift_arena_destroy": (None, [_P]),
     "nm_sift_arena_bytes": (_SZ, [_P]),
@@ -715,6 +718,77 @@ def ransac(model, sx, sy, dx, dy, rand_list, thr):
                                _dev(rand_list, torch.int32), it, thr, _dev(H_all), _dev(inl), _dev(Hb), _dev(pos),
                                _stream()), "nm_ransac_f32")
     return pos, Hb, H_all, inl
+
+
+RANSAC_MAX_BATCH = 64
+RANSAC_MAX_ITERATIONS = 1 << 20
+
+
+class RansacBatchWorkspace:
+    """Device scratch for nm_ransac_batch_dev_f32: n pairs of at most capA rows and `iterations` hypotheses."""
+
+    def __init__(self, n, capA, iterations, device):
+        torch = _torch()
+        need = lib().nm_ransac_batch_dev_workspace_bytes(n, capA, iterations)
+        if need == 0:
+            raise NmError("RANSAC batch workspace: n=%d capA=%d iterations=%d out of range" % (n, capA, iterations))
+        self.n, self.capA, self.iterations = n, capA, iterations
+        self.buf = torch.empty(need, dtype=torch.uint8, device=device)
+
+
+def ransac_batch_sample(seed, hypothesis, sample, samples, m):
+    """The batched RANSAC's sampler (host): index j in [0, m) into the pair's valid rows, or -1 for bad arguments."""
+    return lib().nm_ransac_batch_sample(seed & 0xFFFFFFFF, hypothesis, sample, samples, m)
+
+
+def ransac_batch_dev(model, src_xs, src_ys, d_nAs, dst_xs, dst_ys, matches, iterations=4096, threshold=4.0, seeds=None,
+                     capA=None, workspace=None, want_all=False):
+    """len(src_xs) <= RANSAC_MAX_BATCH frame pairs in one call (nm_ransac_batch_dev_f32), sampled on the device: no host
+    read, no allocation inside the C call. d_nAs are int32 DEVICE tensors (e.g. SiftArena.num_items); matches[k] is the
+    pair's matcher result. model 0/1/2 = translation/similarity/homography; threshold bounds the squared reprojection
+    error. seeds (host ints) default to range(n); capA to the rows of the source tensors. Returns (H_best[n, 9],
+    best_inliers[n], position[n], status[n]) and, with want_all, also (homographies[n, iterations, 9], inliers[n, iterations])."""
+    torch = _torch()
+    n = len(src_xs)
+    if not (n == len(src_ys) == len(d_nAs) == len(dst_xs) == len(dst_ys) == len(matches)) or not 0 < n <= RANSAC_MAX_BATCH:
+        raise NmError("bad batch")
+    if model not in (0, 1, 2) or not 0 < iterations <= RANSAC_MAX_ITERATIONS:
+        raise NmError("model %r / iterations %r out of range" % (model, iterations))
+    seeds = list(range(n)) if seeds is None else [int(s) for s in seeds]
+    if len(seeds) != n or any(not 0 <= s <= 0xFFFFFFFF for s in seeds):
+        raise NmError("seeds: %d unsigned 32-bit values expected" % n)
+    capA = min(min(t.shape[0] for t in src_xs), min(t.shape[0] for t in src_ys), min(t.shape[0] for t in matches)) \
+        if capA is None else capA
+    if any(t.shape[0] < capA for t in list(src_xs) + list(src_ys) + list(matches)):
+        raise NmError("a source coordinate or match tensor is smaller than the capacity")
+    device = src_xs[0].device
+    tensors = list(src_xs) + list(src_ys) + list(d_nAs) + list(dst_xs) + list(dst_ys) + list(matches)
+    if any(t.device != device for t in tensors) or device.type != "cuda" or torch.cuda.current_device() != device.index:
+        raise NmError("all tensors must live on the current device")
+    if any(c.numel() < 1 for c in d_nAs):
+        raise NmError("a device size tensor is empty")
+    if workspace is None:
+        workspace = RansacBatchWorkspace(n, capA, iterations, device)
+    need = lib().nm_ransac_batch_dev_workspace_bytes(n, capA, iterations)
+    if need == 0 or workspace.buf.numel() < need:
+        raise NmError("RANSAC batch workspace too small")
+    H_best = torch.empty((n, 9), dtype=torch.float32, device=device)
+    best, pos, status = (torch.empty(n, dtype=torch.int32, device=device) for _ in range(3))
+    H_all = torch.empty((n, iterations, 9), dtype=torch.float32, device=device) if want_all else None
+    inl = torch.empty((n, iterations), dtype=torch.int32, device=device) if want_all else None
+    arr = lambda vals: (C.c_void_p * n)(*vals)
+    _check(lib().nm_ransac_batch_dev_f32(model, n, arr([_dev(t, torch.float32) for t in src_xs]),
+                                         arr([_dev(t, torch.float32) for t in src_ys]),
+                                         arr([_dev(t, torch.int32) for t in d_nAs]), capA,
+                                         arr([_dev(t, torch.float32) for t in dst_xs]),
+                                         arr([_dev(t, torch.float32) for t in dst_ys]),
+                                         arr([_dev(t, torch.int32) for t in matches]), iterations, threshold,
+                                         (C.c_uint * n)(*seeds), _dev(H_best), _dev(best), _dev(pos), _dev(status),
+                                         _dev(H_all) if want_all else None, _dev(inl) if want_all else None,
+                                         _dev(workspace.buf), _stream()), "nm_ransac_batch_dev_f32")
+    if want_all:
+        return H_best, best, pos, status, H_all, inl
+    return H_best, best, pos, status
 
 
 SIFT_MAX_BATCH = 64
