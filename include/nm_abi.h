@@ -473,6 +473,67 @@ NM_API int nm_ransac_batch_dev_f32(int model, int n,
  * samples not in {1, 2, 4}, sample not in [0, samples), hypothesis not in [0, 2^20) or m < 1.                          */
 NM_API int nm_ransac_batch_sample(unsigned int seed, int hypothesis, int sample, int samples, int m);
 
+/* ---- Mosaic plan and batched blend (no reference counterpart: the reference's client places frames on the host and
+ * calls transform_blend once per frame). Together with nm_ransac_batch_dev_f32 the chain detect -> match -> RANSAC ->
+ * plan -> blend runs on one stream with no host read and can be captured into one HIP graph.
+ *
+ * nm_mosaic_record: one frame's placement (64 bytes). m comes first, so &records[k] is a valid mat3x3 for
+ * nm_transform_blend; nm_transform_blend(canvas, .., frame_k, fw, fh, nw, nh, records[k].m, tx, ty, ..) blends frame k.
+ * placed = 1 for a placed frame; an unplaced frame's record is all zero. reserved is written as 0.
+ *
+ * nm_mosaic_plan_f32: n in [1, NM_MOSAIC_MAX_BATCH] frames. H (device, (n-1) x 9 row-major; may be NULL for n = 1): pair k
+ * maps frame-k pixels to frame-(k+1) pixels (H_best of nm_ransac_batch_dev_f32 for A = frame k, B = frame k+1). status
+ * (device, n-1 ints) may be NULL: every link valid. Frames are fw x fh, the canvas cw x ch; frame-0 coordinate (0, 0)
+ * lands on canvas pixel (ox, oy). M_first (device, 9 floats) maps the mosaic's reference coordinates to frame-0 pixels,
+ * NULL = identity; a previous call's last chain row continues a longer sequence. All arithmetic is fp32, fmaf explicit:
+ *   M_0 = M_first as given (or I). Link k is valid when (status == NULL || status[k] == 1) and all nine H_k are finite;
+ *   then p[r][c] = fmaf(h[r][2], m[2][c], fmaf(h[r][1], m[1][c], h[r][0] * m[0][c])) with m = M_k, and
+ *   M_{k+1} = p / p[8] element by element (IEEE division). An invalid link, or p[8] zero or not finite, BREAKS the chain:
+ *   frames k+1 .. n-1 get zero records and zero chain rows.
+ *   Footprint of a chained frame k: W = invert3x3(M_k) (csrc/nm_warp_math.hpp), the corners (-1, -1), (fw, -1), (-1, fh),
+ *   (fw, fh) (the sampler's support) through project(W, x, y). A corner with denominator s <= 0, or a non-finite
+ *   projection, leaves frame k ALONE unplaced (zero record; its chain row is still written, later frames keep the chain).
+ *   Else box = (floor(min x) - 1, floor(min y) - 1, ceil(max x) + 1, ceil(max y) + 1), exclusive upper edge, in frame-0
+ *   coordinates; X0 = clamp(box.x0 + ox, 0, cw), X1 = clamp(box.x1 + ox, 0, cw) in float, then to int (Y alike with oy,
+ *   ch); tx = X0, nw = max(X1 - X0, 0), ty, nh alike. A frame wholly off the canvas has nw or nh = 0 and placed = 1.
+ *   Local map: m = M_k T(tx - ox, ty - oy): columns 0 and 1 of M_k, column 2 = fmaf(M[r][0], dx, fmaf(M[r][1], dy, M[r][2]))
+ *   with dx = tx - ox, dy = ty - oy; project(m, x, y) of local grid pixel (x, y) is the frame-k pixel that
+ *   nm_transform_blend samples for canvas pixel (x + tx, y + ty).
+ * Outputs (device): records n; chain n x 9 (optional): M_k (frame-0 coordinates -> frame-k pixels); extent 4 floats
+ * (optional): (min x0, min y0, max x1, max y1) of the boxes of all placed frames before clipping, in frame-0 coordinates
+ * (all 0 when no frame is placed). One launch of one workgroup (one lane chains, one lane per frame places), no
+ * allocation, no synchronisation. Returns hipErrorInvalidValue, touching no device memory, for n not in [1, 64], fw, fh,
+ * cw or ch not in [1, 32767], |ox| or |oy| >= 2^20, records NULL, or H NULL with n > 1.
+ * nm_mosaic_plan_host_f32: the same with every pointer in host memory, compiled from the same functions: host and
+ * device results are identical bit for bit.
+ *
+ * nm_transform_blend_batch: n in [1, NM_MOSAIC_MAX_BATCH] frames into one canvas (uchar4 cw x ch, cw and ch in
+ * [1, 32767]) in ONE launch. frames, masks, wts: HOST arrays of n device pointers (fw x fh uchar4 frames; scalar
+ * masks / weights of mask_format / wts_format, NM_TEX_U8N or NM_TEX_F32); pointers may repeat. records: device, n. The
+ * result equals, bit for bit and on canvas and canvas_wts alike, for k = 0 .. n-1 in order:
+ *   nm_transform_blend(canvas, cw, ch, frames[k], fw, fh, records[k].nw, records[k].nh, records[k].m, records[k].tx,
+ *                      records[k].ty, masks[k], mask_format, canvas_wts, wts[k], wts_format)
+ * for records with |tx|, |ty| < 2^24 and nw, nh in [0, 2^15). Pixels no frame writes keep their bytes. Any record values
+ * are safe (rectangles are clipped in 64-bit arithmetic). Each canvas pixel is read once and written at most once: one
+ * lane runs the blend step of every covering frame in index order in registers. Returns hipErrorInvalidValue, touching
+ * no device memory, for n, cw, ch out of range, fw or fh < 1, a non-scalar format or a NULL pointer.               */
+#define NM_MOSAIC_MAX_BATCH 64
+typedef struct nm_mosaic_record {
+    float m[9];
+    int tx, ty, nw, nh;
+    int placed;
+    int reserved[2];
+} nm_mosaic_record;
+NM_API int nm_mosaic_plan_f32(int n, const float *H, const int *status, int fw, int fh, int cw, int ch, int ox, int oy,
+                              const float *M_first, nm_mosaic_record *records, float *chain, float *extent,
+                              void *stream);
+NM_API int nm_mosaic_plan_host_f32(int n, const float *H, const int *status, int fw, int fh, int cw, int ch, int ox,
+                                   int oy, const float *M_first, nm_mosaic_record *records, float *chain, float *extent);
+NM_API int nm_transform_blend_batch(unsigned char *canvas, int cw, int ch, float *canvas_wts, int n,
+                                    const unsigned char *const *frames, int fw, int fh, const void *const *masks,
+                                    int mask_format, const void *const *wts, int wts_format,
+                                    const nm_mosaic_record *records, void *stream);
+
 /* ---- per-frame driver ---- */
 /* The per-octave client loop the reference leaves to its caller, run entirely on `stream` with no
  * host synchronisation and no allocation: Gaussian pyramid + DoG + gradients + extrema + ordered compaction +

@@ -103,6 +103,9 @@ _SIGNATURES = {
     "nm_ransac_batch_dev_workspace_bytes": (_SZ, [_I, _I, _I]),
     "nm_ransac_batch_dev_f32": (_I, [_I, _I, _P, _P, _P, _I, _P, _P, _P, _I, _F, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "nm_ransac_batch_sample": (_I, [C.c_uint, _I, _I, _I, _I]),
+    "nm_mosaic_plan_f32": (_I, [_I, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "nm_mosaic_plan_host_f32": (_I, [_I, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "nm_transform_blend_batch": (_I, [_P, _I, _I, _P, _I, _P, _I, _I, _P, _I, _P, _I, _P, _P]),
     "nm_sift_arena_create": (_I, [_I, _I, _I, _P]),
     "nm_sift_arena_destroy": (None, [_P]),
     "nm_sift_arena_bytes": (_SZ, [_P]),
@@ -789,6 +792,112 @@ def ransac_batch_dev(model, src_xs, src_ys, d_nAs, dst_xs, dst_ys, matches, iter
     if want_all:
         return H_best, best, pos, status, H_all, inl
     return H_best, best, pos, status
+
+
+MOSAIC_MAX_BATCH = 64
+_MOSAIC_SIZE_LIMIT = 32767
+_MOSAIC_OFFSET_LIMIT = 1 << 20
+
+
+def _mosaic_check_geometry(n, fw, fh, cw, ch, ox, oy):
+    if not 0 < n <= MOSAIC_MAX_BATCH:
+        raise NmError("mosaic: %d frames (1 .. %d)" % (n, MOSAIC_MAX_BATCH))
+    if any(not 1 <= int(v) <= _MOSAIC_SIZE_LIMIT for v in (fw, fh, cw, ch)):
+        raise NmError("mosaic: frame %dx%d / canvas %dx%d outside [1, %d]" % (fw, fh, cw, ch, _MOSAIC_SIZE_LIMIT))
+    if any(abs(int(v)) >= _MOSAIC_OFFSET_LIMIT for v in (ox, oy)):
+        raise NmError("mosaic: |ox|, |oy| must be below 2^20")
+
+
+def mosaic_plan(H, status, fw, fh, cw, ch, ox, oy, M_first=None):
+    """Placement records of n = H.shape[0] + 1 frames from the pairwise homographies (nm_mosaic_plan_f32), one launch on
+    the current stream, no host read. H: float32 device (n-1, 9) or (n-1, 3, 3), pair k mapping frame k to frame k+1 (e.g.
+    ransac_batch_dev's H_best); status: int32 device (n-1,) or None (every link valid); frame-0 pixel (0, 0) lands on
+    canvas pixel (ox, oy); M_first: float32 device (9,) or (3, 3) map from the reference coordinates to frame 0, None =
+    identity. Returns (records int32 (n, 16): m = records[:, :9].view(float32), then tx, ty, nw, nh, placed, 0, 0;
+    chain float32 (n, 9); extent float32 (4,))."""
+    torch = _torch()
+    n = H.shape[0] + 1
+    _mosaic_check_geometry(n, fw, fh, cw, ch, ox, oy)
+    if H.numel() != 9 * (n - 1):
+        raise NmError("mosaic_plan: H must hold (n-1) x 9 floats")
+    tensors = [H] + ([status] if status is not None else []) + ([M_first] if M_first is not None else [])
+    device = H.device
+    if any(t.device != device for t in tensors) or device.type != "cuda" or torch.cuda.current_device() != device.index:
+        raise NmError("mosaic_plan: all tensors must live on the current device")
+    if status is not None and status.numel() != n - 1:
+        raise NmError("mosaic_plan: status must hold n-1 values")
+    if M_first is not None and M_first.numel() != 9:
+        raise NmError("mosaic_plan: M_first must hold 9 floats")
+    records = torch.empty((n, 16), dtype=torch.int32, device=device)
+    chain = torch.empty((n, 9), dtype=torch.float32, device=device)
+    extent = torch.empty(4, dtype=torch.float32, device=device)
+    _check(lib().nm_mosaic_plan_f32(n, _dev(H, torch.float32) if n > 1 else None,
+                                    _dev(status, torch.int32) if status is not None else None, fw, fh, cw, ch, ox, oy,
+                                    _dev(M_first, torch.float32) if M_first is not None else None, _dev(records),
+                                    _dev(chain), _dev(extent), _stream()), "nm_mosaic_plan_f32")
+    return records, chain, extent
+
+
+def mosaic_plan_host(H, status, fw, fh, cw, ch, ox, oy, M_first=None):
+    """mosaic_plan on the host (nm_mosaic_plan_host_f32, the same functions): numpy in and out, bit-identical results."""
+    import numpy as np
+    H = np.ascontiguousarray(H, dtype=np.float32).reshape(-1, 9)
+    n = H.shape[0] + 1
+    _mosaic_check_geometry(n, fw, fh, cw, ch, ox, oy)
+    if status is not None:
+        status = np.ascontiguousarray(status, dtype=np.int32).reshape(-1)
+        if status.size != n - 1:
+            raise NmError("mosaic_plan_host: status must hold n-1 values")
+    if M_first is not None:
+        M_first = np.ascontiguousarray(M_first, dtype=np.float32).reshape(-1)
+        if M_first.size != 9:
+            raise NmError("mosaic_plan_host: M_first must hold 9 floats")
+    records = np.zeros((n, 16), np.int32)
+    chain = np.zeros((n, 9), np.float32)
+    extent = np.zeros(4, np.float32)
+    ptr = lambda a: a.ctypes.data if a is not None else None
+    _check(lib().nm_mosaic_plan_host_f32(n, ptr(H) if n > 1 else None, ptr(status), fw, fh, cw, ch, ox, oy, ptr(M_first),
+                                         ptr(records), ptr(chain), ptr(extent)), "nm_mosaic_plan_host_f32")
+    return records, chain, extent
+
+
+def transform_blend_batch(canvas, canvas_wts, frames, masks, wts, records):
+    """n = len(frames) <= MOSAIC_MAX_BATCH frames into the canvas IN PLACE, one launch (nm_transform_blend_batch): the same
+    bits as transform_blend(canvas, canvas_wts, frames[k], nw_k, nh_k, m_k, tx_k, ty_k, masks[k], wts[k]) for k in order,
+    with the fields of records[k] (int32 device (n, 16), e.g. from mosaic_plan). masks / wts: one scalar plane for every
+    frame, or a list of n planes of one format."""
+    torch = _torch()
+    n = len(frames)
+    if not 0 < n <= MOSAIC_MAX_BATCH:
+        raise NmError("transform_blend_batch: %d frames (1 .. %d)" % (n, MOSAIC_MAX_BATCH))
+    masks = list(masks) if isinstance(masks, (list, tuple)) else [masks] * n
+    wts = list(wts) if isinstance(wts, (list, tuple)) else [wts] * n
+    if len(masks) != n or len(wts) != n:
+        raise NmError("transform_blend_batch: %d frames, %d masks, %d weight planes" % (n, len(masks), len(wts)))
+    if canvas.dim() != 3 or canvas.shape[2] != 4 or tuple(canvas_wts.shape) != tuple(canvas.shape[:2]):
+        raise NmError("transform_blend_batch: canvas must be (ch, cw, 4) uint8 with (ch, cw) float32 weights")
+    ch, cw = canvas.shape[0], canvas.shape[1]
+    if not (1 <= cw <= _MOSAIC_SIZE_LIMIT and 1 <= ch <= _MOSAIC_SIZE_LIMIT):
+        raise NmError("transform_blend_batch: canvas %dx%d outside [1, %d]" % (cw, ch, _MOSAIC_SIZE_LIMIT))
+    fh, fw = frames[0].shape[0], frames[0].shape[1]
+    if any(f.dim() != 3 or tuple(f.shape) != (fh, fw, 4) for f in frames) or fw < 1 or fh < 1:
+        raise NmError("transform_blend_batch: frames must all be (fh, fw, 4) uint8")
+    if any(tuple(t.shape) != (fh, fw) for t in masks + wts):
+        raise NmError("transform_blend_batch: masks and weights must be (fh, fw) planes")
+    mfmt, wfmt = _tex_format(masks[0]), _tex_format(wts[0])
+    if any(_tex_format(t) != mfmt for t in masks) or any(_tex_format(t) != wfmt for t in wts):
+        raise NmError("transform_blend_batch: one mask format and one weight format per call")
+    if tuple(records.shape) != (n, 16) or records.dtype != torch.int32:
+        raise NmError("transform_blend_batch: records must be int32 (n, 16)")
+    device = canvas.device
+    tensors = [canvas, canvas_wts, records] + list(frames) + masks + wts
+    if any(t.device != device for t in tensors) or device.type != "cuda" or torch.cuda.current_device() != device.index:
+        raise NmError("transform_blend_batch: all tensors must live on the current device")
+    arr = lambda vals: (C.c_void_p * n)(*vals)
+    _check(lib().nm_transform_blend_batch(_dev(canvas, torch.uint8), cw, ch, _dev(canvas_wts, torch.float32), n,
+                                          arr([_dev(f, torch.uint8) for f in frames]), fw, fh,
+                                          arr([_dev(t) for t in masks]), mfmt, arr([_dev(t) for t in wts]), wfmt,
+                                          _dev(records, torch.int32), _stream()), "nm_transform_blend_batch")
 
 
 SIFT_MAX_BATCH = 64

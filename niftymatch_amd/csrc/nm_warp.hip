@@ -4,96 +4,13 @@
 // code objects launched through HIP have no such object here: the sampler is written out (border test, weights
 // quantised to 1/256 like the texture unit's 9-bit fixed point, fixed left-to-right sum). Same operation sequence as
 // oracle/nmo_warp.h. All kernels are one pixel per lane on 64 x 4 tiles: coordinate streams are read coalesced, the 4
-// texel taps are gathers that hit L2 (a warp of neighbouring pixels touches neighbouring texels).
-#include "nm_common.hpp"
-#include "../../include/nm_abi.h"
+// texel taps are gathers that hit L2 (a warp of neighbouring pixels touches neighbouring texels). The sampler, the
+// projective map and transform_blend's per-pixel step live in nm_warp_math.hpp, shared with nm_mosaic.hip.
+#include "nm_warp_math.hpp"
 
 namespace {
 
-struct Tex { const void *data; int w, h, fmt; };
-
-__device__ __forceinline__ float fmaf_(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
-
-template <int FMT>
-__device__ __forceinline__ float texel(const Tex &t, int i, int j, int ch)
-{
-    if (i < 0 || i >= t.w || j < 0 || j >= t.h) return 0.f;
-    const size_t p = (size_t)j * t.w + i;
-    if (FMT == NM_TEX_F32) return ((const float *)t.data)[p];
-    if (FMT == NM_TEX_U8N) return (float)((const unsigned char *)t.data)[p] / 255.0f;
-    return (float)((const unsigned char *)t.data)[4 * p + ch] / 255.0f;
-}
-
-__device__ __forceinline__ bool tex_setup(const Tex &t, float x, float y, int &i, int &j, float w[4])
-{
-    const float xb = x - 0.5f, yb = y - 0.5f;
-    if (!(xb >= -1.0f && xb < (float)t.w && yb >= -1.0f && yb < (float)t.h)) return false;
-    const float fi = __builtin_floorf(xb), fj = __builtin_floorf(yb);
-    const float a = __builtin_floorf((xb - fi) * 256.0f + 0.5f) * 0.00390625f;
-    const float b = __builtin_floorf((yb - fj) * 256.0f + 0.5f) * 0.00390625f;
-    i = (int)fi; j = (int)fj;
-    w[0] = (1.0f - a) * (1.0f - b); w[1] = a * (1.0f - b); w[2] = (1.0f - a) * b; w[3] = a * b;
-    return true;
-}
-
-template <int FMT>
-__device__ __forceinline__ float tex2d(const Tex &t, float x, float y)
-{
-    int i, j; float w[4];
-    if (!tex_setup(t, x, y, i, j, w)) return 0.f;
-    return ((w[0] * texel<FMT>(t, i, j, 0) + w[1] * texel<FMT>(t, i + 1, j, 0)) + w[2] * texel<FMT>(t, i, j + 1, 0)) +
-           w[3] * texel<FMT>(t, i + 1, j + 1, 0);
-}
-
-__device__ __forceinline__ float tex2d_any(const Tex &t, float x, float y)
-{
-    return t.fmt == NM_TEX_F32 ? tex2d<NM_TEX_F32>(t, x, y) : tex2d<NM_TEX_U8N>(t, x, y);
-}
-
-// uchar4 texture: one 4-byte load per tap, the four channels share the weights
-__device__ __forceinline__ void tex2d_u8x4(const Tex &t, float x, float y, float out[4])
-{
-    int i, j; float w[4];
-    out[0] = out[1] = out[2] = out[3] = 0.f;
-    if (!tex_setup(t, x, y, i, j, w)) return;
-    float tap[4][4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int ii = i + (k & 1), jj = j + (k >> 1);
-        uchar4 p = make_uchar4(0, 0, 0, 0);
-        if (ii >= 0 && ii < t.w && jj >= 0 && jj < t.h) p = ((const uchar4 *)t.data)[(size_t)jj * t.w + ii];
-        tap[k][0] = (float)p.x / 255.0f; tap[k][1] = (float)p.y / 255.0f;
-        tap[k][2] = (float)p.z / 255.0f; tap[k][3] = (float)p.w / 255.0f;
-    }
-#pragma unroll
-    for (int c = 0; c < 4; ++c) out[c] = ((w[0] * tap[0][c] + w[1] * tap[1][c]) + w[2] * tap[2][c]) + w[3] * tap[3][c];
-}
-
-__device__ __forceinline__ void project(const float *m, float x, float y, float &xp, float &yp)
-{
-    const float a = fmaf_(m[0], x, m[1] * y) + m[2];
-    const float b = fmaf_(m[3], x, m[4] * y) + m[5];
-    const float s = fmaf_(m[6], x, m[7] * y) + m[8];
-    xp = a / s; yp = b / s;
-}
-
-__device__ __forceinline__ void invert3x3(const float *t, float *inv)
-{
-    const float c0 = fmaf_(t[4], t[8], -(t[7] * t[5]));
-    const float c1 = fmaf_(t[3], t[8], -(t[5] * t[6]));
-    const float c2 = fmaf_(t[3], t[7], -(t[4] * t[6]));
-    const float det = fmaf_(t[2], c2, fmaf_(t[0], c0, -(t[1] * c1)));
-    const float invdet = 1.0f / det;
-    inv[0] = c0 * invdet;
-    inv[1] = fmaf_(t[2], t[7], -(t[1] * t[8])) * invdet;
-    inv[2] = fmaf_(t[1], t[5], -(t[2] * t[4])) * invdet;
-    inv[3] = fmaf_(t[5], t[6], -(t[3] * t[8])) * invdet;
-    inv[4] = fmaf_(t[0], t[8], -(t[2] * t[6])) * invdet;
-    inv[5] = fmaf_(t[3], t[2], -(t[0] * t[5])) * invdet;
-    inv[6] = fmaf_(t[3], t[7], -(t[6] * t[4])) * invdet;
-    inv[7] = fmaf_(t[6], t[1], -(t[0] * t[7])) * invdet;
-    inv[8] = fmaf_(t[0], t[4], -(t[3] * t[1])) * invdet;
-}
+using namespace nmw;
 
 __global__ __launch_bounds__(256) void undistort_map_kernel(const float *__restrict__ x, const float *__restrict__ y,
                                                            size_t n, const float *__restrict__ cam,
@@ -170,30 +87,13 @@ __global__ __launch_bounds__(256) void transform_blend_kernel(uchar4 *__restrict
     const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
     const int px = x + tx, py = y + ty;
     if (x >= nw || y >= nh || px < 0 || px >= cw || py < 0 || py >= ch) return;
-    float xp, yp;
-    project(m, (float)x, (float)y, xp, yp);
-    if (xp >= (float)frame.w || yp >= (float)frame.h) return;
-    const float u = xp + 0.5f, v = yp + 0.5f;
-    if (tex2d_any(mask, u, v) <= 0.5f) return;
-    const float nwt = tex2d_any(wts, u, v);
-    float r[4];
-    tex2d_u8x4(frame, u, v, r);
+    float r[4], nwt;
+    if (!blend_sample(m, frame, mask, wts, x, y, r, nwt)) return;
     const size_t idx = (size_t)py * cw + px;
-    const float cwt = canvas_wts[idx];
-    uchar4 c;
-    if (cwt == 0) {
-        c = make_uchar4((unsigned char)(r[0] * 255.9999f), (unsigned char)(r[1] * 255.9999f),
-                        (unsigned char)(r[2] * 255.9999f), 255);
-        canvas_wts[idx] = nwt;
-    } else {
-        const uchar4 cur = canvas[idx];
-        const float sum = cwt + nwt;
-        c.x = (unsigned char)(fmaf_(r[0] * nwt, 255.9999f, (float)cur.x * cwt) / sum);
-        c.y = (unsigned char)(fmaf_(r[1] * nwt, 255.9999f, (float)cur.y * cwt) / sum);
-        c.z = (unsigned char)(fmaf_(r[2] * nwt, 255.9999f, (float)cur.z * cwt) / sum);
-        c.w = 255;
-        canvas_wts[idx] = sum;
-    }
+    float cwt = canvas_wts[idx];
+    uchar4 c = cwt == 0 ? make_uchar4(0, 0, 0, 0) : canvas[idx];
+    blend_combine(r, nwt, c, cwt);
+    canvas_wts[idx] = cwt;
     canvas[idx] = c;
 }
 
