@@ -221,11 +221,13 @@ NM_API int nm_compute_sift_descriptors_levels(int n_levels, const float *const *
 /* Device-sized forms of the two (round 5): the three level counts of the octave are read ON THE DEVICE (d_counts: what
  * nm_compact_keypoints3 left there), so the host needs no count to issue them -- the reference's client synchronises once
  * per level for it (thrust::copy_if, sift/pyramidata.cu:84-91). An empty level ends the octave (siftfunctions.cu:145,160);
- * max_pts bounds a level's count (grid size; the lists hold at least as many entries). Descriptors go to the CONTAINER's
- * arrays: slot = running count + kept keypoints of the earlier levels + index, the running count read from *d_base_in (NULL:
- * host_base) and clipped at `capacity` (siftfunctions.cu:165-169); the new running count is written to *d_items_out. h_counts
- * (3 ints) / h_items (1 int): device-accessible pointers of pinned host memory that receive the raw counts / the new running
- * count, valid once `stream` has reached the launch (or NULL). nm/lazy_count.h is the C++ layer's use of them.            */
+ * max_pts is the room of every level list (key_pts, result / orients) and is ENFORCED: a level count above it is clipped to
+ * max_pts, both kernels touch entries [0, max_pts) only, and those entries are what the unclipped lists would give.
+ * Descriptors go to the CONTAINER's arrays: slot = running count + kept keypoints of the earlier levels + index, the running
+ * count read from *d_base_in (NULL: host_base) and clipped at `capacity` (siftfunctions.cu:165-169); the new running count
+ * is written to *d_items_out. h_counts (3 ints) / h_items (1 int): device-accessible pointers of pinned host memory that
+ * receive the clipped counts / the new running count, valid once `stream` has reached the launch (or NULL). nm/lazy_count.h
+ * is the C++ layer's use of them.                                                                                        */
 NM_API int nm_detect_orientations_levels_dev(const float *const *key_pts, const int *d_counts, int max_pts, const float *grad,
                                              int octave_width, int octave_height, float gauss_factor, float xper,
                                              float *const *result, int *h_counts, void *stream);

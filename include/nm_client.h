@@ -36,6 +36,13 @@ __attribute__((visibility("default"))) int nm_client_copy_semantics(const float 
  * the item count (all three runs agree on counts, descriptors and coordinates), -2 on a mismatch, -1 on an exception. */
 __attribute__((visibility("default"))) int nm_client_lazy_counts(const float *gray, int width, int height, int capacity,
                                                                 int *watch, int max_octaves, int *pending_seen);
+/* A client that hand-fills PyramidData::_key_pts[0] of octave 0 with one valid keypoint (x, y, sigma, 0) per pixel -- more than
+ * the level list holds (nm_keypoint_bound) -- after compute_keypoints, then runs compute_orientations / compute_descriptors on
+ * the lazy path. sizes (4 ints, host): _orientations[0..2].size() and _num_items, read after compute_descriptors. desc
+ * (capacity*128) / x / y (capacity): host. Returns 1 (lazy path taken), 0 (not taken) or -1 on an exception. */
+__attribute__((visibility("default"))) int nm_client_dense_level_keypoints(const float *gray, int width, int height,
+                                                                          int capacity, float sigma, int *sizes, float *desc,
+                                                                          float *x, float *y);
 /* A: nA*128, B: nB*128 (host). distance: nA*nB (host) or NULL. result: nA ints, pre-filled by the caller. */
 __attribute__((visibility("default"))) int nm_client_match(const float *A, int nA, const float *B, int nB,
                                                           float *distance, int *result, float ambiguity);

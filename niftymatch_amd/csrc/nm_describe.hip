@@ -485,6 +485,7 @@ struct NmLevelLists {
     // x[0] / y[0] are then the container's arrays from slot 0. One lane mirrors the counts / the new running count into
     // mapped host words.
     const int *d_counts;
+    int max_pts;                       // a level's count is clipped here: the lists hold max_pts entries
     const int *d_base_in; int host_base, capacity;
     int *d_items_out;
     int *h_counts, *h_items;           // mapped pinned host words (or NULL)
@@ -500,6 +501,7 @@ __device__ __forceinline__ void level_extent_dev(const NmLevelLists &a, int l, b
     for (int k = 0; k < 3; ++k) {
         int cnt = live ? a.d_counts[k] : 0;
         if (cnt <= 0) { live = false; cnt = 0; }
+        if (cnt > a.max_pts) cnt = a.max_pts;     // beyond the lists' room (only a hand-filled dense map gets here)
         int keep = cnt;
         if (clip) { if (keep + run > a.capacity) keep = a.capacity - run; if (keep < 0) keep = 0; }
         if (k == l) { n = keep; base = run; }
@@ -530,7 +532,8 @@ __global__ __launch_bounds__(256) void orientations_levels_kernel(NmLevelLists a
     const int wave = threadIdx.x >> 6;
     int n[3], base[3], run;
     level_counts(a, false, n, base, run);
-    if (a.d_counts && a.h_counts && blockIdx.x == 0 && threadIdx.x < 3) a.h_counts[threadIdx.x] = a.d_counts[threadIdx.x];
+    if (a.d_counts && a.h_counts && blockIdx.x == 0 && threadIdx.x < 3)
+        a.h_counts[threadIdx.x] = min(a.d_counts[threadIdx.x], a.max_pts);       // the count that was written
     const int total = n[0] + n[1] + n[2];
     for (int idx = blockIdx.x * 4 + wave; idx < total; idx += gridDim.x * 4) {
         const int l = idx < n[0] ? 0 : (idx < n[0] + n[1] ? 1 : 2);
@@ -813,7 +816,7 @@ int nm_detect_orientations_levels(int n_levels, const float *const *key_pts, con
 
 // The device-sized forms (lazy_count.h): the three level counts are read on the device, nothing comes back to the host except
 // through the mapped words h_counts[3] / h_items[1] (device-accessible pointers of pinned host memory, or NULL).
-// max_pts: upper bound of a level's count (sizes the grid; the lists hold at least that many entries).
+// max_pts: the room of every level list (key_pts and result); a level's count is clipped there, and it sizes the grid.
 int nm_detect_orientations_levels_dev(const float *const *key_pts, const int *d_counts, int max_pts, const float *grad,
                                       int octave_width, int octave_height, float gauss_factor, float xper, float *const *result,
                                       int *h_counts, void *stream)
@@ -825,7 +828,7 @@ int nm_detect_orientations_levels_dev(const float *const *key_pts, const int *d_
         a.key_pts[l] = reinterpret_cast<const float4 *>(key_pts[l]);
         a.orients[l] = reinterpret_cast<float2 *>(result[l]);
     }
-    a.d_counts = d_counts; a.h_counts = h_counts;
+    a.d_counts = d_counts; a.max_pts = max_pts; a.h_counts = h_counts;
     hipLaunchKernelGGL(orientations_levels_kernel, dim3(min(nm_divup(max_pts, 4), 1024)), dim3(256), 0, nm_stream(stream), a,
                        reinterpret_cast<const float2 *>(grad), octave_width, octave_height, gauss_factor, xper);
     NM_LAUNCH_CHECK();
@@ -847,7 +850,7 @@ int nm_compute_sift_descriptors_levels_dev(const float *const *key_pts, const fl
         a.orients[l] = const_cast<float2 *>(reinterpret_cast<const float2 *>(orients[l]));
     }
     a.desc[0] = desc; a.x[0] = x; a.y[0] = y;
-    a.d_counts = d_counts; a.d_base_in = d_base_in; a.host_base = host_base; a.capacity = capacity;
+    a.d_counts = d_counts; a.max_pts = max_pts; a.d_base_in = d_base_in; a.host_base = host_base; a.capacity = capacity;
     a.d_items_out = d_items_out; a.h_items = h_items;
     hipLaunchKernelGGL(descriptors_levels_kernel, dim3(min(min(max_pts, capacity), 4096)), dim3(64), 0, nm_stream(stream), a,
                        reinterpret_cast<const float2 *>(grad), octave_width, octave_height, num_dogs, xper);

@@ -194,6 +194,55 @@ extern "C" int nm_client_lazy_counts(const float *gray, int width, int height, i
     }
 }
 
+// A client that fills PyramidData::_key_pts itself (a public member) with more valid keypoints than a level list holds: octave 0
+// of the frame through compute_keypoints, then EVERY pixel of level 0 becomes a keypoint (x, y, sigma, 0) -- w*h entries
+// against the nm_keypoint_bound(w, h) that _orientations[0] has room for -- and compute_orientations / compute_descriptors run
+// on the lazy path, which clips each level at the room of its list. sizes (4 ints): _orientations[0..2].size() and _num_items,
+// read only after compute_descriptors (reading a size earlier would resolve the counts and leave the lazy path). Returns 1 when
+// compute_descriptors took the lazy path, 0 when it did not, -1 on an exception. desc / x / y: capacity rows (host).
+extern "C" int nm_client_dense_level_keypoints(const float *gray, int width, int height, int capacity, float sigma, int *sizes,
+                                               float *desc, float *x, float *y)
+{
+    try {
+        SiftParams params(width, height);
+        PyramidData py(params);
+        SiftData out(capacity);
+        out._num_items = 0;
+        const size_t npix = (size_t)width * height;
+        nm::device_vector<float> d_gray(std::vector<float>(gray, gray + npix));
+        convolve<float>(py._octave[0].data(), d_gray.data(), py._buffer.data(), width, height, py._base_kernel.data(),
+                        py._base_radius, 0);
+        for (int i = 1; i < py._num_octaves; ++i)
+            convolve<float>(py._octave[i].data(), py._octave[i - 1].data(), py._buffer.data(), width, height,
+                            py._kernels[i - 1].data(), py._kernel_radii[i - 1], 0);
+        compute_dog(py, width, height, 0);
+        compute_gradients(py, params, width, height, 0);
+        compute_keypoints(py, params, 0, width, height, 0);
+        std::vector<float4> dense(npix);
+        for (int yy = 0; yy < height; ++yy)
+            for (int xx = 0; xx < width; ++xx) dense[(size_t)yy * width + xx] = make_float4((float)xx, (float)yy, sigma, 0.f);
+        nm_check((int)hipDeviceSynchronize(), "sync");
+        nm_check((int)hipMemcpy(py._key_pts[0].data(), dense.data(), npix * sizeof(float4), hipMemcpyHostToDevice), "key_pts");
+        compute_orientations(py, params, 0, width, height, 0);
+        compute_descriptors(py, params, 0, width, height, out, 0);
+        const int lazy = out._num_items.pending() ? 1 : 0;
+        for (int l = 0; l < 3; ++l) sizes[l] = (int)py._orientations[l].size();
+        const int n = out._num_items;
+        sizes[3] = n;
+        nm_check((int)hipDeviceSynchronize(), "sync");
+        if (n > 0) {
+            std::vector<float> h = out._desc.to_host();
+            std::memcpy(desc, h.data(), (size_t)n * 128 * sizeof(float));
+            h = out._x.to_host(); std::memcpy(x, h.data(), (size_t)n * sizeof(float));
+            h = out._y.to_host(); std::memcpy(y, h.data(), (size_t)n * sizeof(float));
+        }
+        return lazy;
+    } catch (const std::exception &e) {
+        std::cerr << e.what() << std::endl;
+        return -1;
+    }
+}
+
 // Throughput of the drop-in path as an application would drive it: `reps` times { detect+describe both frames with the
 // reference's per-octave client loop, compute_sift_matches(A, B, distance) }. Objects are created once, as a real client
 // does. gray0/gray1 are DEVICE planes. with_distance != 0 passes a caller-allocated N x M `distance` (the reference's

@@ -201,6 +201,19 @@ void compute_keypoints_with_mask(PyramidData &pydata, SiftParams &params, NmText
                    octave_height, stream);
 }
 
+// What the level lists of the lazy path can hold: the device-sized kernels clip every level's count there. The collation
+// leaves at most num_pixels keypoints per level; _orientations[l] holds nm_keypoint_bound of the octave (or more), which real
+// detector output never exceeds (strict extrema, pyramidata.cpp) -- only a hand-filled _key_pts can, and its surplus is dropped.
+static int lazy_list_room(const PyramidData &pydata, int num_pixels)
+{
+    size_t room = (size_t)num_pixels;
+    for (int l = 0; l < 3; ++l) {
+        if (pydata._collated_kpts[l].size() < room) room = pydata._collated_kpts[l].size();
+        if (pydata._orientations[l].capacity() < room) room = pydata._orientations[l].capacity();
+    }
+    return (int)room;
+}
+
 void compute_orientations(PyramidData &pydata, const SiftParams &params, const int octave, const int octave_width,
                           const int octave_height, hipStream_t stream)
 {
@@ -220,7 +233,7 @@ void compute_orientations(PyramidData &pydata, const SiftParams &params, const i
             kp[i] = reinterpret_cast<const float *>(pydata._collated_kpts[i].data());
             res[i] = reinterpret_cast<float *>(pydata._orientations[i].data());
         }
-        nm_check(nm_detect_orientations_levels_dev(kp, pydata.lazy_counts_dev(), num_pixels_for_octave,
+        nm_check(nm_detect_orientations_levels_dev(kp, pydata.lazy_counts_dev(), lazy_list_room(pydata, num_pixels_for_octave),
                                                    reinterpret_cast<const float *>(pydata._grad.data()), octave_width,
                                                    octave_height, 1.5f, xper, res, words, stream),
                  "Orientation histogram launch failed");
@@ -281,7 +294,7 @@ void compute_descriptors(PyramidData &pydata, const SiftParams &params, const in
             kp[i] = reinterpret_cast<const float *>(pydata._collated_kpts[i].data());
             ori[i] = reinterpret_cast<const float *>(pydata._orientations[i].data());
         }
-        const int bound = octave_width * octave_height;
+        const int bound = lazy_list_room(pydata, octave_width * octave_height);
         nm_check(nm_compute_sift_descriptors_levels_dev(kp, ori, pydata.lazy_counts_dev(), bound, base_in,
                                                         dev_base ? 0 : data._num_items.host_value(), capacity, items_out,
                                                         words + 3, reinterpret_cast<const float *>(pydata._grad.data()),

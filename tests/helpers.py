@@ -35,3 +35,41 @@ def assert_distance(nm, D, Dref, what="distance matrix"):
     bad = np.abs(a - b) > 1e-4 * np.abs(b)
     assert not bad.any(), "%s: %d of %d entries off by more than 1e-4 relative (worst %g)" % (
         what, bad.sum(), bad.size, float(np.max(np.abs(a - b)[bad] / np.maximum(np.abs(b[bad]), 1e-300))))
+
+
+def blob_field(seed, width, height):
+    """Signed isotropic Gaussian blobs on a grey background, ~w*h/6000 of them with sigma log-uniform in [1.5, min(w,h)/24],
+    rounded to integers and clipped to [0, 255]: keypoints at every scale (the deep octaves that blurred noise barely reaches),
+    quantised plateaus and, where blobs saturate, flats with exact ties."""
+    rng = np.random.default_rng(seed)
+    img = np.full((height, width), 128.0, np.float64)
+    n = max(1, int(width * height / 6000))
+    s_hi = max(1.6, min(width, height) / 24.0)
+    sig = np.exp(rng.uniform(np.log(1.5), np.log(s_hi), n))
+    amp = rng.uniform(40.0, 160.0, n) * rng.choice([-1.0, 1.0], n)
+    cx, cy = rng.uniform(0, width, n), rng.uniform(0, height, n)
+    for s, a, x0, y0 in zip(sig, amp, cx, cy):
+        r = int(np.ceil(4 * s))
+        xa, xb = max(0, int(x0) - r), min(width, int(x0) + r + 1)
+        ya, yb = max(0, int(y0) - r), min(height, int(y0) + r + 1)
+        if xa >= xb or ya >= yb:
+            continue
+        gx = np.exp(-((np.arange(xa, xb) - x0) ** 2) / (2 * s * s))
+        gy = np.exp(-((np.arange(ya, yb) - y0) ** 2) / (2 * s * s))
+        img[ya:yb, xa:xb] += a * np.outer(gy, gx)
+    return np.clip(np.rint(img), 0, 255).astype(np.float32)
+
+
+def step_field(seed, width, height):
+    """0/255 rectangles XOR-ed onto a 0 background (~w*h/8000 of them, sides log-uniform from 3 px to a quarter of the frame):
+    step edges, flats whose gradient is exactly zero and dense exact ties in the DoG planes."""
+    rng = np.random.default_rng(seed)
+    on = np.zeros((height, width), bool)
+    n = max(1, int(width * height / 8000))
+    s_hi = max(4.0, min(width, height) / 4.0)
+    rw = np.exp(rng.uniform(np.log(3.0), np.log(s_hi), n)).astype(int)
+    rh = np.exp(rng.uniform(np.log(3.0), np.log(s_hi), n)).astype(int)
+    x0, y0 = rng.integers(0, width, n), rng.integers(0, height, n)
+    for x, y, a, b in zip(x0, y0, rw, rh):
+        on[y: y + b, x: x + a] ^= True
+    return np.where(on, np.float32(255.0), np.float32(0.0))

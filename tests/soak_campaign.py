@@ -18,9 +18,12 @@ import oracle_lib as O  # noqa: E402
 n_frames = int(sys.argv[1]) if len(sys.argv) > 1 else 60
 n_match = int(sys.argv[2]) if len(sys.argv) > 2 else 120
 rng = np.random.default_rng(int(sys.argv[3]) if len(sys.argv) > 3 else 12345)
+# the large-geometry and structured-content arms draw from a stream of their own: the arms above draw exactly as before
+rng_x = np.random.default_rng((int(sys.argv[3]) if len(sys.argv) > 3 else 12345) + 7)
 dev = torch.device("cuda:0")
 t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
 bad = 0
+n_large = n_structured = 0
 t0 = time.time()
 for it in range(n_frames):
     w = int(rng.integers(24, 400)); h = int(rng.integers(24, 300))
@@ -30,6 +33,13 @@ for it in range(n_frames):
         w = (w // 4) * 4 + (0 if rng.random() < 0.8 else 1)        # mostly the packed path, sometimes the generic one
     nb = int(rng.integers(1, 4))
     cap = int(rng.choice([64, 500, 4096]))
+    if rng_x.random() < 0.03:                                          # geometries up to 4K, odd large sizes (octave tail from
+        if rng_x.random() < 0.4:                                       # 960 x 540, 7 octaves; the generic path above 1080p)
+            w, h = 3840, 2160
+        else:
+            w, h = int(rng_x.integers(1500, 3841)), int(rng_x.integers(700, 2161))
+        cap = int(rng_x.choice([cap, 65536]))
+        n_large += 1
     frames = []
     for k in range(nb):
         f = H.blurred_frame(int(rng.integers(1, 1 << 30)), w, h, sigma=float(rng.uniform(0.8, 4.0)))
@@ -38,6 +48,13 @@ for it in range(n_frames):
             f[: h // 3] = 0                                            # flat region
         if rng.random() < 0.2:
             f = np.round(f).astype(np.float32)                         # quantised image: many exact ties / zeros
+        kind = rng_x.random()
+        if kind < 0.06:                                                # blobs at every scale (keypoints in the deep octaves)
+            f = H.blob_field(int(rng_x.integers(1, 1 << 30)), w, h)
+            n_structured += 1
+        elif kind < 0.12:                                              # 0/255 rectangles: step edges, zero gradients, ties
+            f = H.step_field(int(rng_x.integers(1, 1 << 30)), w, h)
+            n_structured += 1
         frames.append(np.ascontiguousarray(f, dtype=np.float32))
     arenas = [nm.SiftArena(w, h, cap) for _ in range(nb)]
     nm.set_detect_tall_min(1 if rng.random() < 0.5 else -1)            # round 5: 20-row detection groups forced on half the batches
@@ -58,7 +75,8 @@ for it in range(n_frames):
         a.close()
     if it % 500 == 499:
         print("  ... %d frame batches, %d mismatches so far, %.0fs" % (it + 1, bad, time.time() - t0), flush=True)
-print("frames done: %d cases, %d mismatches, %.1fs" % (n_frames, bad, time.time() - t0), flush=True)
+print("frames done: %d cases (%d up to 4K, %d structured frames), %d mismatches, %.1fs" % (
+    n_frames, n_large, n_structured, bad, time.time() - t0), flush=True)
 t0 = time.time()
 for it in range(n_match):
     na = int(rng.integers(1, 3000)); nb = int(rng.integers(1, 3000))

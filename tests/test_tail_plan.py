@@ -18,7 +18,7 @@ def plan(nm, w, h, T=2):
 
 
 @pytest.mark.parametrize("w,h", [(1920, 1080), (3840, 2160), (640, 480), (1916, 1076), (400, 300), (256, 192), (1280, 720),
-                                 (4096, 130), (129, 2000)])
+                                 (4096, 130), (129, 2000), (7680, 4320), (2047, 1531)])
 @pytest.mark.parametrize("T", [1, 2, 3])
 def test_segments_are_in_topological_order(nm, w, h, T):
     rows, info = plan(nm, w, h, T)
