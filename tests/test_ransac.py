@@ -74,6 +74,17 @@ def test_cpp_api_ransac(nm, cuda):
                                    H.ctypes.data)
     assert rc == 1
     np.testing.assert_allclose(H.reshape(3, 3) / H[8], TRUE_H, rtol=3e-2, atol=3e-2)
+    # the recovery rule of tests/ransac_ref.py: the frame corners land within 2 sqrt(thr) px of the true map, in float64
+    import ransac_ref as R
+    assert R.iterations_for(550 / 800, 4) < 2000
+    assert R.corner_distance64(H, TRUE_H, 1920, 1080)[0] <= 2 * np.sqrt(4.0)
+    sc = R.scene(2, 3840, 2160, 800, 0.3, 0.0, 6, "perspective")     # a second scene, at 3840x2160 coordinates
+    H4 = np.zeros(9, np.float32)
+    assert nm.lib().nm_client_ransac(2, sc["sx"].ctypes.data, sc["sy"].ctypes.data, sc["dx"].ctypes.data, sc["dy"].ctypes.data,
+                                     800, 4.0, 2000, 42, H4.ctypes.data) == 1
+    M = sc["M"]
+    np.testing.assert_allclose(H4.reshape(3, 3) / H4[8], M / M[2, 2], rtol=3e-2, atol=3e-2)
+    assert R.corner_distance64(H4, M, 3840, 2160)[0] <= 2 * np.sqrt(4.0)
     H2 = np.zeros(9, np.float32)
     nm.lib().nm_client_ransac(2, sx.ctypes.data, sy.ctypes.data, dx.ctypes.data, dy.ctypes.data, 800, 4.0, 2000, 42, H2.ctypes.data)
     assert np.array_equal(H, H2)                               # same seed, same answer
