@@ -423,6 +423,14 @@ NM_API int nm_resample_mask_u8(unsigned char *result, const void *tex, int tex_w
 NM_API int nm_resample_perspective_u8x4(unsigned char *result, const unsigned char *tex, int tex_width, int tex_height,
                                         int cols, int rows, float *x_pos, float *y_pos, const float *mat3x3, int inverse,
                                         void *stream);
+/* resample_2D<uchar4> (resample.cu:116-204, the sampling half of resample_perspective_transform) on a map the caller
+ * supplies: result[p], channel c, = (unsigned char)(s[c] * 255.9999f) with s = the uchar4 sample of tex at
+ * (x[p] + 0.5f, y[p] + 0.5f), exactly as nm_resample_perspective_u8x4 writes it after projecting (a coordinate outside
+ * the sampler's support, NaN and +-inf included, samples 0). tex is tex_width x tex_height uchar4, x / y / result are
+ * cols x rows. Returns 0 without launching when cols or rows <= 0, hipErrorInvalidValue when tex_width or tex_height
+ * <= 0. */
+NM_API int nm_resample_map_u8x4(unsigned char *result, const unsigned char *tex, int tex_width, int tex_height,
+                                const float *x, const float *y, int cols, int rows, void *stream);
 /* transform_blend (resample.h:16-20, resample.cu:7-66,218-232): frame (uchar4), frame_mask and frame_wts are fw x fh. */
 NM_API int nm_transform_blend(unsigned char *canvas, int cw, int ch, const unsigned char *frame, int fw, int fh, int nw,
                               int nh, const float *mat3x3, int tx, int ty, const void *frame_mask, int mask_format,
@@ -535,6 +543,31 @@ NM_API int nm_transform_blend_batch(unsigned char *canvas, int cw, int ch, float
                                     const unsigned char *const *frames, int fw, int fh, const void *const *masks,
                                     int mask_format, const void *const *wts, int wts_format,
                                     const nm_mosaic_record *records, void *stream);
+
+/* ---- Batched frame ingest (no reference counterpart: the reference's client undistorts and converts each frame with
+ * its own launches). nm_frame_ingest_batch_f32 turns n camera frames into the fp32 gray planes SIFT reads and,
+ * optionally, their undistorted BGRA frames, in ONE launch.
+ * frames, gray, undistorted: HOST arrays of n device pointers (gray can be handed straight to
+ * nm_sift_detect_describe_batch). Each frame is fw x fh uchar4 (BGRA). One map is shared by all frames (one camera):
+ * map_x / map_y are cols x rows floats, e.g. from nm_undistort_map_f32, or any map. Each output is cols x rows.
+ *   With a map: undistorted[k] equals nm_resample_map_u8x4(frames[k], map_x, map_y) bit for bit, and gray[k] equals
+ *   nm_grayscale_f32 of that uchar4 result bit for bit. gray is always computed from the rounded uchar4 pixel, also
+ *   when undistorted is NULL (gray only). For B, G, R and gray this is also what the per-frame channel chain
+ *   nm_extract_channel_f32 -> nm_cast_f32_u8 -> nm_resample_undistort_f32 (NM_TEX_U8N) -> nm_put_channel_f32 per
+ *   channel, then nm_grayscale_f32, produces; alpha is the sampled alpha, as in resample_2D<uchar4> (the chain's
+ *   put_channel(3) writes 255 instead).
+ *   Identity mode (map_x == map_y == NULL): a batched nm_grayscale_f32, gray[k] = nm_grayscale_f32(frames[k]). It
+ *   requires cols == fw, rows == fh and undistorted == NULL.
+ * One launch; no allocation, no synchronisation, no host read, so the call can be captured into a HIP graph. A frame's
+ * result does not depend on its slot in the call or on n. Frame pointers may repeat; outputs must not overlap the
+ * inputs or each other. Nothing outside each cols x rows output plane is written.
+ * Returns hipErrorInvalidValue, before any device access, for n not in [1, NM_INGEST_MAX_BATCH]; fw, fh, cols or rows
+ * not in [1, 32767]; frames or gray NULL or holding a NULL among its first n; exactly one of map_x / map_y NULL;
+ * identity mode with undistorted != NULL or cols != fw or rows != fh; undistorted non-NULL but holding a NULL.      */
+#define NM_INGEST_MAX_BATCH 64
+NM_API int nm_frame_ingest_batch_f32(int n, const unsigned char *const *frames, int fw, int fh, const float *map_x,
+                                     const float *map_y, int cols, int rows, float *const *gray,
+                                     unsigned char *const *undistorted, void *stream);
 
 /* ---- per-frame driver ---- */
 /* The per-octave client loop the reference leaves to its caller, run entirely on `stream` with no

@@ -97,6 +97,7 @@ _SIGNATURES = {
     "nm_resample_undistort_f32": (_I, [_P, _I, _I, _I, _P, _P, _SZ, _SZ, _P, _P]),
     "nm_resample_mask_u8": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _F, _P]),
     "nm_resample_perspective_u8x4": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _P]),
+    "nm_resample_map_u8x4": (_I, [_P, _P, _I, _I, _P, _P, _I, _I, _P]),
     "nm_transform_blend": (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _P, _I, _I, _P, _I, _P, _P, _I, _P]),
     "nm_ransac_f32": (_I, [_I, _P, _P, _P, _P, _I, _P, _I, _F, _P, _P, _P, _P, _P]),
     "nm_ransac_seed": (None, [C.c_uint]),
@@ -106,6 +107,7 @@ _SIGNATURES = {
     "nm_mosaic_plan_f32": (_I, [_I, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "nm_mosaic_plan_host_f32": (_I, [_I, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "nm_transform_blend_batch": (_I, [_P, _I, _I, _P, _I, _P, _I, _I, _P, _I, _P, _I, _P, _P]),
+    "nm_frame_ingest_batch_f32": (_I, [_I, _P, _I, _I, _P, _P, _I, _I, _P, _P, _P]),
     "nm_sift_arena_create": (_I, [_I, _I, _I, _P]),
     "nm_sift_arena_destroy": (None, [_P]),
     "nm_sift_arena_bytes": (_SZ, [_P]),
@@ -899,6 +901,84 @@ def transform_blend_batch(canvas, canvas_wts, frames, masks, wts, records):
                                           arr([_dev(f, torch.uint8) for f in frames]), fw, fh,
                                           arr([_dev(t) for t in masks]), mfmt, arr([_dev(t) for t in wts]), wfmt,
                                           _dev(records, torch.int32), _stream()), "nm_transform_blend_batch")
+
+
+INGEST_MAX_BATCH = 64
+_INGEST_SIZE_LIMIT = 32767
+
+
+def _on_current_device(tensors, what):
+    torch = _torch()
+    device = tensors[0].device
+    if any(t.device != device for t in tensors) or device.type != "cuda" or torch.cuda.current_device() != device.index:
+        raise NmError("%s: all tensors must live on the current device" % what)
+    return device
+
+
+def _ingest_map(u, v, what):
+    torch = _torch()
+    if u.dim() != 2 or tuple(v.shape) != tuple(u.shape) or u.dtype != torch.float32 or v.dtype != torch.float32:
+        raise NmError("%s: the map must be two float32 (rows, cols) planes of one shape" % what)
+    rows, cols = u.shape
+    if not (1 <= cols <= _INGEST_SIZE_LIMIT and 1 <= rows <= _INGEST_SIZE_LIMIT):
+        raise NmError("%s: map %dx%d outside [1, %d]" % (what, cols, rows, _INGEST_SIZE_LIMIT))
+    return cols, rows
+
+
+def resample_map_u8x4(tex, x, y):
+    """resample_2D<uchar4> on a caller's map (nm_resample_map_u8x4): tex uint8 (fh, fw, 4) BGRA sampled at (x + 0.5,
+    y + 0.5) of the float32 (rows, cols) planes x, y. Returns uint8 (rows, cols, 4)."""
+    torch = _torch()
+    if tex.dim() != 3 or tex.shape[2] != 4 or tex.dtype != torch.uint8:
+        raise NmError("resample_map_u8x4: tex must be (fh, fw, 4) uint8")
+    fh, fw = tex.shape[0], tex.shape[1]
+    if not (1 <= fw <= _INGEST_SIZE_LIMIT and 1 <= fh <= _INGEST_SIZE_LIMIT):
+        raise NmError("resample_map_u8x4: frame %dx%d outside [1, %d]" % (fw, fh, _INGEST_SIZE_LIMIT))
+    cols, rows = _ingest_map(x, y, "resample_map_u8x4")
+    device = _on_current_device([tex, x, y], "resample_map_u8x4")
+    out = torch.empty((rows, cols, 4), dtype=torch.uint8, device=device)
+    _check(lib().nm_resample_map_u8x4(_dev(out), _dev(tex, torch.uint8), fw, fh, _dev(x, torch.float32),
+                                      _dev(y, torch.float32), cols, rows, _stream()), "nm_resample_map_u8x4")
+    return out
+
+
+def ingest_batch(frames, u=None, v=None, undistorted=False):
+    """n = len(frames) <= INGEST_MAX_BATCH BGRA frames (uint8 (fh, fw, 4), one camera) in ONE launch
+    (nm_frame_ingest_batch_f32). With a map (u, v: float32 (rows, cols), e.g. from undistort_map) each frame is resampled
+    as resample_map_u8x4(frame, u, v) and its gray plane is grayscale() of that uchar4 result; without one (identity mode)
+    gray[k] = grayscale(frames[k]). Returns the list of float32 gray planes, and with undistorted=True (a map is needed)
+    also the list of uint8 (rows, cols, 4) undistorted frames."""
+    torch = _torch()
+    frames = list(frames)
+    n = len(frames)
+    if not 0 < n <= INGEST_MAX_BATCH:
+        raise NmError("ingest_batch: %d frames (1 .. %d)" % (n, INGEST_MAX_BATCH))
+    if any(f.dim() != 3 or f.shape[2] != 4 or f.dtype != torch.uint8 for f in frames):
+        raise NmError("ingest_batch: frames must be (fh, fw, 4) uint8")
+    fh, fw = frames[0].shape[0], frames[0].shape[1]
+    if any(tuple(f.shape) != (fh, fw, 4) for f in frames):
+        raise NmError("ingest_batch: all frames must have one shape")
+    if not (1 <= fw <= _INGEST_SIZE_LIMIT and 1 <= fh <= _INGEST_SIZE_LIMIT):
+        raise NmError("ingest_batch: frame %dx%d outside [1, %d]" % (fw, fh, _INGEST_SIZE_LIMIT))
+    if (u is None) != (v is None):
+        raise NmError("ingest_batch: give both map planes or neither")
+    if u is None:
+        if undistorted:
+            raise NmError("ingest_batch: undistorted frames need a map")
+        cols, rows = fw, fh
+        device = _on_current_device(frames, "ingest_batch")
+    else:
+        cols, rows = _ingest_map(u, v, "ingest_batch")
+        device = _on_current_device(frames + [u, v], "ingest_batch")
+    gray = [torch.empty((rows, cols), dtype=torch.float32, device=device) for _ in range(n)]
+    und = [torch.empty((rows, cols, 4), dtype=torch.uint8, device=device) for _ in range(n)] if undistorted else None
+    arr = lambda vals: (C.c_void_p * n)(*vals)
+    _check(lib().nm_frame_ingest_batch_f32(n, arr([_dev(f, torch.uint8) for f in frames]), fw, fh,
+                                           _dev(u, torch.float32) if u is not None else None,
+                                           _dev(v, torch.float32) if v is not None else None, cols, rows,
+                                           arr([_dev(g) for g in gray]), arr([_dev(t) for t in und]) if und else None,
+                                           _stream()), "nm_frame_ingest_batch_f32")
+    return (gray, und) if undistorted else gray
 
 
 SIFT_MAX_BATCH = 64

@@ -3,17 +3,12 @@
 // (kernels/cast.cu:8-36), uchar4 decimation (kernels/downsample.cu:6-32) and the match gather align_points
 // (kernels/ransac.cu:29-59). All are HBM-bound streaming kernels: one 16-byte or 4-byte access per lane, grid-stride.
 #include "nm_common.hpp"
+#include "nm_gray.hpp"
 #include "../../include/nm_abi.h"
 
 namespace {
 
-__device__ __forceinline__ float gray_of(uchar4 p)
-{
-    // 0.07*B + 0.72*G + 0.21*R in double (the literals are double), narrowed to float (bgra_2_gray.cu:16);
-    // contraction written out: fma(0.21, R, fma(0.07, B, 0.72*G))
-    const double b = (double)(int)p.x, g = (double)(int)p.y, r = (double)(int)p.z;
-    return (float)__builtin_fma(0.21, r, __builtin_fma(0.07, b, 0.72 * g));
-}
+using nmg::gray_of;
 
 __global__ __launch_bounds__(256) void grayscale_kernel(const uchar4 *__restrict__ bgra, float *__restrict__ out, size_t n)
 {

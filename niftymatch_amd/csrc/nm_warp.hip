@@ -73,8 +73,21 @@ __global__ __launch_bounds__(256) void perspective_resample_kernel(uchar4 *__res
     x_pos[p] = xp; y_pos[p] = yp;
     float r[4];
     tex2d_u8x4(t, xp + 0.5f, yp + 0.5f, r);
-    result[p] = make_uchar4((unsigned char)(r[0] * 255.9999f), (unsigned char)(r[1] * 255.9999f),
-                            (unsigned char)(r[2] * 255.9999f), (unsigned char)(r[3] * 255.9999f));
+    result[p] = u8x4_of(r);
+}
+
+// resample_2D<uchar4> on a caller's map: the sampling half of perspective_resample_kernel
+__global__ __launch_bounds__(256) void resample_map_u8x4_kernel(uchar4 *__restrict__ result, Tex t,
+                                                               const float *__restrict__ x, const float *__restrict__ y,
+                                                               size_t n)
+{
+    size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t stride = (size_t)gridDim.x * 256;
+    for (; p < n; p += stride) {
+        float r[4];
+        tex2d_u8x4(t, x[p] + 0.5f, y[p] + 0.5f, r);
+        result[p] = u8x4_of(r);
+    }
 }
 
 __global__ __launch_bounds__(256) void transform_blend_kernel(uchar4 *__restrict__ canvas, int cw, int ch, Tex frame,
@@ -152,6 +165,18 @@ int nm_resample_perspective_u8x4(unsigned char *result, const unsigned char *tex
     hipLaunchKernelGGL(perspective_resample_kernel, grid, dim3(256), 0, nm_stream(stream),
                        reinterpret_cast<uchar4 *>(result), Tex{tex, tex_width, tex_height, NM_TEX_U8X4N}, cols, rows, x_pos,
                        y_pos, mat3x3, inverse);
+    NM_LAUNCH_CHECK();
+    return 0;
+}
+
+int nm_resample_map_u8x4(unsigned char *result, const unsigned char *tex, int tex_width, int tex_height, const float *x,
+                         const float *y, int cols, int rows, void *stream)
+{
+    if (cols <= 0 || rows <= 0) return 0;
+    if (tex_width <= 0 || tex_height <= 0) return (int)hipErrorInvalidValue;
+    const size_t n = (size_t)cols * rows;
+    hipLaunchKernelGGL(resample_map_u8x4_kernel, dim3(stream_blocks(n)), dim3(256), 0, nm_stream(stream),
+                       reinterpret_cast<uchar4 *>(result), Tex{tex, tex_width, tex_height, NM_TEX_U8X4N}, x, y, n);
     NM_LAUNCH_CHECK();
     return 0;
 }

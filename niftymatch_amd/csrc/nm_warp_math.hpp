@@ -1,7 +1,8 @@
-// nm_warp_math.hpp -- the warp arithmetic shared by nm_warp.hip (per-frame entries) and nm_mosaic.hip (mosaic plan and
-// batched blend): the software bilinear sampler, the projective map, the 3x3 inverse and the per-pixel blend step of
-// transform_blend. One copy, so that the batched blend equals n per-frame transform_blend calls by construction. The
-// build uses -ffp-contract=off and correctly rounded fp32 division; every multiply-add here is an explicit fmaf.
+// nm_warp_math.hpp -- the warp arithmetic shared by nm_warp.hip (per-frame entries), nm_mosaic.hip (mosaic plan and
+// batched blend) and nm_ingest.hip (batched frame ingest): the software bilinear sampler, the projective map, the 3x3
+// inverse and the per-pixel blend step of transform_blend. One copy, so that the batched blend equals n per-frame
+// transform_blend calls, and the ingest equals per-frame resamples, by construction. The build uses -ffp-contract=off
+// and correctly rounded fp32 division; every multiply-add here is an explicit fmaf.
 // project / invert3x3 / blend_combine are __host__ __device__: the mosaic plan's host twin runs the same sequence.
 #pragma once
 #include "nm_common.hpp"
@@ -49,23 +50,55 @@ __device__ __forceinline__ float tex2d_any(const Tex &t, float x, float y)
     return t.fmt == NM_TEX_F32 ? tex2d<NM_TEX_F32>(t, x, y) : tex2d<NM_TEX_U8N>(t, x, y);
 }
 
-// uchar4 texture: one 4-byte load per tap, the four channels share the weights
+// uchar4 texture: one 4-byte load per tap, the four channels share the weights. Three steps, so that the batched
+// ingest (nm_ingest.hip) runs setup and tap addressing once per pixel and the fetch and filter once per frame:
+//   tex_taps_u8x4   the texel index and in-frame test of the 4 taps of tex_setup's (i, j)
+//   tex_fetch_u8x4  the 4 loads (an out-of-frame tap reads as 0)
+//   tex_filter_u8x4 c / 255 per channel, then the weighted sum in a fixed order
+__device__ __forceinline__ void tex_taps_u8x4(const Tex &t, int i, int j, size_t off[4], bool in[4])
+{
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int ii = i + (k & 1), jj = j + (k >> 1);
+        in[k] = ii >= 0 && ii < t.w && jj >= 0 && jj < t.h;
+        off[k] = in[k] ? (size_t)jj * t.w + ii : 0;
+    }
+}
+
+__device__ __forceinline__ void tex_fetch_u8x4(const uchar4 *data, const size_t off[4], const bool in[4], uchar4 p[4])
+{
+#pragma unroll
+    for (int k = 0; k < 4; ++k) p[k] = in[k] ? data[off[k]] : make_uchar4(0, 0, 0, 0);
+}
+
+__device__ __forceinline__ void tex_filter_u8x4(const uchar4 p[4], const float w[4], float out[4])
+{
+    float tap[4][4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        tap[k][0] = (float)p[k].x / 255.0f; tap[k][1] = (float)p[k].y / 255.0f;
+        tap[k][2] = (float)p[k].z / 255.0f; tap[k][3] = (float)p[k].w / 255.0f;
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c) out[c] = ((w[0] * tap[0][c] + w[1] * tap[1][c]) + w[2] * tap[2][c]) + w[3] * tap[3][c];
+}
+
 __device__ __forceinline__ void tex2d_u8x4(const Tex &t, float x, float y, float out[4])
 {
     int i, j; float w[4];
     out[0] = out[1] = out[2] = out[3] = 0.f;
     if (!tex_setup(t, x, y, i, j, w)) return;
-    float tap[4][4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int ii = i + (k & 1), jj = j + (k >> 1);
-        uchar4 p = make_uchar4(0, 0, 0, 0);
-        if (ii >= 0 && ii < t.w && jj >= 0 && jj < t.h) p = ((const uchar4 *)t.data)[(size_t)jj * t.w + ii];
-        tap[k][0] = (float)p.x / 255.0f; tap[k][1] = (float)p.y / 255.0f;
-        tap[k][2] = (float)p.z / 255.0f; tap[k][3] = (float)p.w / 255.0f;
-    }
-#pragma unroll
-    for (int c = 0; c < 4; ++c) out[c] = ((w[0] * tap[0][c] + w[1] * tap[1][c]) + w[2] * tap[2][c]) + w[3] * tap[3][c];
+    size_t off[4]; bool in[4]; uchar4 p[4];
+    tex_taps_u8x4(t, i, j, off, in);
+    tex_fetch_u8x4((const uchar4 *)t.data, off, in, p);
+    tex_filter_u8x4(p, w, out);
+}
+
+// the uchar4 result pixel of a sample, as resample_2D<uchar4> writes it
+__device__ __forceinline__ uchar4 u8x4_of(const float s[4])
+{
+    return make_uchar4((unsigned char)(s[0] * 255.9999f), (unsigned char)(s[1] * 255.9999f),
+                       (unsigned char)(s[2] * 255.9999f), (unsigned char)(s[3] * 255.9999f));
 }
 
 // the denominator of project(m, x, y), same operations
