@@ -483,6 +483,58 @@ NM_API int nm_ransac_batch_dev_f32(int model, int n,
  * samples not in {1, 2, 4}, sample not in [0, samples), hypothesis not in [0, 2^20) or m < 1.                          */
 NM_API int nm_ransac_batch_sample(unsigned int seed, int hypothesis, int sample, int samples, int m);
 
+/* Batched least-squares refit of RANSAC models over their inliers, with inlier masks (no reference counterpart: the
+ * reference hands out the hypothesis fitted to its minimal sample). n <= NM_RANSAC_MAX_BATCH pairs in ONE launch on
+ * `stream` whatever n and rounds are; no allocation, no synchronisation, no host read, no workspace -- capturable into a
+ * HIP graph behind nm_ransac_batch_dev_f32. src_x .. matches, d_nA, capA and the valid rows V_k are those of
+ * nm_ransac_batch_dev_f32. H_in: device, n x 9 (e.g. H_best); status_in: device, n ints, NULL = all 1.
+ *   Classification: row i of V_k is an inlier of a map H when nmr_is_inlier(H, .., inlier_threshold) holds
+ *   (csrc/nm_ransac_math.hpp, the test of nm_ransac_f32), so with rounds = 0 the count equals best_inliers bit for bit.
+ *   One round: S = inliers of H_cur, c_cur = |S|; stop if c_cur < 1, 2, 4 (model 0, 1, 2); H_new = the least-squares fit to
+ *   all of S, its nine values rounded to fp32; stop unless all nine are finite; c_new = inliers of H_new; stop unless
+ *   c_new >= c_cur; else H_cur = H_new (its inliers are the next round's S). At most `rounds` in [0, 4] rounds; the count
+ *   never falls, and with no accepted round H_out is H_in bit for bit.
+ *   Fits (fp64 from the fp32 coordinates, fma explicit, IEEE divide and sqrt; the sums below in the order given last):
+ *     translation  t = (sum d - sum s) / c, per axis.
+ *     similarity   c1 = sum s / c, c2 = sum d / c, s_c = s - c1, d_c = d - c2; a = (sum fma(s_cx, d_cx, s_cy d_cy)
+ *                  + i sum fma(s_cx, d_cy, -(s_cy d_cx))) / sum fma(s_cx, s_cx, s_cy s_cy); t = c2 - a c1;
+ *                  H = (Re a, -Im a, t_x; Im a, Re a, t_y; 0, 0, 1).
+ *     homography   normalised DLT. s1 = sqrt(2) / (sum |s_c| / c), s2 alike; a = s_c s1, b = d_c s2, p = (a_x, a_y, 1).
+ *                  Each inlier gives the equations (0, -p, b_y p) and (p, 0, -b_x p); their 9 x 9 moment matrix is built
+ *                  from the 24 sums of P = (a_x^2, a_x a_y, a_x, a_y^2, a_y, 1), b_x P, b_y P and fma(b_x, b_x, b_y b_y) P.
+ *                  Its eigenvector of the smallest eigenvalue comes from a cyclic two-sided Jacobi in round-robin order:
+ *                  in step t = 0 .. 8 of a sweep index t rests and (t + k) % 9 meets (t - k) % 9, k = 1 .. 4; the four
+ *                  rotations (Golub & Van Loan 8.5; skipped when |a_pq| <= 2^-52 sqrt(|a_pp a_qq|)) are computed from
+ *                  the matrix as the step finds it, then all columns are rotated (A J, V J), then all rows (J^T A), and
+ *                  a_pq = a_qp = 0 is stored; sweeps end when one rotates nothing (30 at most). The column of V at the
+ *                  first smallest diagonal entry is denormalised (inv(T2) Hn T1) and divided by its last entry.
+ *     Sums: 512 virtual lanes; lane l adds rows l, l + 512, .. of the pair's arrays in ascending order (only inliers
+ *     contribute); each group of 64 lanes is reduced as v[l] += v[l + d] for d = 32, 16, .. 1; the 8 group totals are
+ *     added in ascending order. No atomics: a pair's outputs depend on that pair's inputs alone, never on n, on the pair's
+ *     slot or on scheduling.
+ * Outputs (device): H_out n x 9, count n (inliers of H_out), status n, rounds_done n (accepted rounds); optional (may be
+ * NULL): mask n x capA bytes (mask[k capA + i] = 1 for an inlier row of H_out, else 0; all capA bytes of a pair are written)
+ * and rms n (sqrt of the mean squared reprojection distance over the final inliers, the distances and the sum in fp64 from
+ * the fp32 map; 0 without inliers). A pair with status_in != 1 or a non-finite value in H_in gets status 0 and zeros in
+ * every output; every other pair gets status 1, so H_out and status can go to nm_mosaic_plan_f32 as they are.
+ * Returns hipErrorInvalidValue, touching no device memory, for model not in {0, 1, 2}, n not in [1, 64], rounds not in
+ * [0, 4], capA not in [1, 2^22), a non-finite threshold, a NULL required pointer or a NULL among the first n table entries.
+ * nm_ransac_refit_host_f32: the same with every pointer in host memory (nA[k] points to a host int), compiled from the
+ * same functions (csrc/nm_ransac_refit_math.hpp): host and device results are identical bit for bit.                    */
+#define NM_RANSAC_REFIT_MAX_ROUNDS 4
+NM_API int nm_ransac_refit_batch_dev_f32(int model, int n,
+                                         const float *const *src_x, const float *const *src_y, const int *const *d_nA,
+                                         int capA, const float *const *dst_x, const float *const *dst_y,
+                                         const int *const *matches, const float *H_in, const int *status_in,
+                                         float inlier_threshold, int rounds, float *H_out, int *count, int *status,
+                                         int *rounds_done, unsigned char *mask, float *rms, void *stream);
+NM_API int nm_ransac_refit_host_f32(int model, int n,
+                                    const float *const *src_x, const float *const *src_y, const int *const *nA, int capA,
+                                    const float *const *dst_x, const float *const *dst_y, const int *const *matches,
+                                    const float *H_in, const int *status_in, float inlier_threshold, int rounds,
+                                    float *H_out, int *count, int *status, int *rounds_done, unsigned char *mask,
+                                    float *rms);
+
 /* ---- Mosaic plan and batched blend (no reference counterpart: the reference's client places frames on the host and
  * calls transform_blend once per frame). Together with nm_ransac_batch_dev_f32 the chain detect -> match -> RANSAC ->
  * plan -> blend runs on one stream with no host read and can be captured into one HIP graph.

@@ -104,6 +104,8 @@ _SIGNATURES = {
     "nm_ransac_batch_dev_workspace_bytes": (_SZ, [_I, _I, _I]),
     "nm_ransac_batch_dev_f32": (_I, [_I, _I, _P, _P, _P, _I, _P, _P, _P, _I, _F, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "nm_ransac_batch_sample": (_I, [C.c_uint, _I, _I, _I, _I]),
+    "nm_ransac_refit_batch_dev_f32": (_I, [_I, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _F, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "nm_ransac_refit_host_f32": (_I, [_I, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _F, _I, _P, _P, _P, _P, _P, _P]),
     "nm_mosaic_plan_f32": (_I, [_I, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "nm_mosaic_plan_host_f32": (_I, [_I, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "nm_transform_blend_batch": (_I, [_P, _I, _I, _P, _I, _P, _I, _I, _P, _I, _P, _I, _P, _P]),
@@ -795,6 +797,95 @@ def ransac_batch_dev(model, src_xs, src_ys, d_nAs, dst_xs, dst_ys, matches, iter
     if want_all:
         return H_best, best, pos, status, H_all, inl
     return H_best, best, pos, status
+
+
+RANSAC_REFIT_MAX_ROUNDS = 4
+
+
+def _refit_check(model, n, lens, rounds, threshold):
+    if any(l != n for l in lens) or not 0 < n <= RANSAC_MAX_BATCH:
+        raise NmError("bad batch")
+    if model not in (0, 1, 2) or not 0 <= int(rounds) <= RANSAC_REFIT_MAX_ROUNDS or int(rounds) != rounds:
+        raise NmError("model %r / rounds %r out of range" % (model, rounds))
+    if threshold != threshold or threshold in (float("inf"), float("-inf")):
+        raise NmError("threshold must be finite")
+
+
+def ransac_refit_batch_dev(model, src_xs, src_ys, d_nAs, dst_xs, dst_ys, matches, H, status=None, rounds=2, threshold=4.0,
+                           capA=None, want_mask=False, want_rms=False):
+    """Least-squares refit of n = len(src_xs) <= RANSAC_MAX_BATCH maps over their inliers (nm_ransac_refit_batch_dev_f32):
+    one launch on the current stream, no host read. The per-pair tensors are those of ransac_batch_dev; H is float32
+    device (n, 9) or (n, 3, 3), e.g. its H_best; status int32 device (n,) or None (all usable). rounds in [0, 4]: 0 gives
+    the inlier count (and mask) of H itself. Returns (H_out[n, 9], count[n], status[n], rounds_done[n]) and then, when
+    asked for, mask uint8 (n, capA) and rms float32 (n,)."""
+    torch = _torch()
+    n = len(src_xs)
+    _refit_check(model, n, [len(v) for v in (src_ys, d_nAs, dst_xs, dst_ys, matches)], rounds, threshold)
+    capA = min(min(t.shape[0] for t in src_xs), min(t.shape[0] for t in src_ys), min(t.shape[0] for t in matches)) \
+        if capA is None else capA
+    if not 1 <= capA < (1 << 22) or any(t.shape[0] < capA for t in list(src_xs) + list(src_ys) + list(matches)):
+        raise NmError("a source coordinate or match tensor is smaller than the capacity, or the capacity is out of range")
+    device = src_xs[0].device
+    tensors = list(src_xs) + list(src_ys) + list(d_nAs) + list(dst_xs) + list(dst_ys) + list(matches) + [H] + \
+        ([status] if status is not None else [])
+    if any(t.device != device for t in tensors) or device.type != "cuda" or torch.cuda.current_device() != device.index:
+        raise NmError("all tensors must live on the current device")
+    if any(c.numel() < 1 for c in d_nAs):
+        raise NmError("a device size tensor is empty")
+    if H.numel() != 9 * n or (status is not None and status.numel() != n):
+        raise NmError("H must hold n x 9 floats and status n values")
+    H_out = torch.empty((n, 9), dtype=torch.float32, device=device)
+    count, st, done = (torch.empty(n, dtype=torch.int32, device=device) for _ in range(3))
+    mask = torch.empty((n, capA), dtype=torch.uint8, device=device) if want_mask else None
+    rms = torch.empty(n, dtype=torch.float32, device=device) if want_rms else None
+    arr = lambda vals: (C.c_void_p * n)(*vals)
+    _check(lib().nm_ransac_refit_batch_dev_f32(model, n, arr([_dev(t, torch.float32) for t in src_xs]),
+                                               arr([_dev(t, torch.float32) for t in src_ys]),
+                                               arr([_dev(t, torch.int32) for t in d_nAs]), capA,
+                                               arr([_dev(t, torch.float32) for t in dst_xs]),
+                                               arr([_dev(t, torch.float32) for t in dst_ys]),
+                                               arr([_dev(t, torch.int32) for t in matches]), _dev(H, torch.float32),
+                                               _dev(status, torch.int32) if status is not None else None, threshold,
+                                               int(rounds), _dev(H_out), _dev(count), _dev(st), _dev(done),
+                                               _dev(mask) if want_mask else None, _dev(rms) if want_rms else None,
+                                               _stream()), "nm_ransac_refit_batch_dev_f32")
+    return (H_out, count, st, done) + ((mask,) if want_mask else ()) + ((rms,) if want_rms else ())
+
+
+def ransac_refit_host(model, src_xs, src_ys, nAs, dst_xs, dst_ys, matches, H, status=None, rounds=2, threshold=4.0,
+                      capA=None, want_mask=False, want_rms=False):
+    """ransac_refit_batch_dev on the host (nm_ransac_refit_host_f32, the same functions): numpy in and out, bit-identical
+    results. nAs are host ints."""
+    import numpy as np
+    n = len(src_xs)
+    _refit_check(model, n, [len(v) for v in (src_ys, nAs, dst_xs, dst_ys, matches)], rounds, threshold)
+    f32 = lambda vs: [np.ascontiguousarray(v, dtype=np.float32).reshape(-1) for v in vs]
+    src_xs, src_ys, dst_xs, dst_ys = f32(src_xs), f32(src_ys), f32(dst_xs), f32(dst_ys)
+    matches = [np.ascontiguousarray(v, dtype=np.int32).reshape(-1) for v in matches]
+    capA = min(min(t.shape[0] for t in src_xs), min(t.shape[0] for t in src_ys), min(t.shape[0] for t in matches)) \
+        if capA is None else capA
+    if not 1 <= capA < (1 << 22) or any(t.shape[0] < capA for t in src_xs + src_ys + matches):
+        raise NmError("a source coordinate or match tensor is smaller than the capacity, or the capacity is out of range")
+    for m, x, y in zip(matches, dst_xs, dst_ys):
+        if m.size and int(m.max()) >= min(x.size, y.size):
+            raise NmError("a match points beyond the destination coordinates")
+    H = np.ascontiguousarray(H, dtype=np.float32).reshape(-1)
+    if status is not None:
+        status = np.ascontiguousarray(status, dtype=np.int32).reshape(-1)
+    if H.size != 9 * n or (status is not None and status.size != n):
+        raise NmError("H must hold n x 9 floats and status n values")
+    nA = np.array([int(v) for v in nAs], np.int32)
+    H_out = np.zeros((n, 9), np.float32)
+    count, st, done = (np.zeros(n, np.int32) for _ in range(3))
+    mask = np.zeros((n, capA), np.uint8) if want_mask else None
+    rms = np.zeros(n, np.float32) if want_rms else None
+    arr = lambda vals: (C.c_void_p * n)(*[v.ctypes.data for v in vals])
+    ptr = lambda a: a.ctypes.data if a is not None else None
+    _check(lib().nm_ransac_refit_host_f32(model, n, arr(src_xs), arr(src_ys), arr([nA[k:k + 1] for k in range(n)]), capA,
+                                          arr(dst_xs), arr(dst_ys), arr(matches), ptr(H), ptr(status), threshold,
+                                          int(rounds), ptr(H_out), ptr(count), ptr(st), ptr(done), ptr(mask), ptr(rms)),
+           "nm_ransac_refit_host_f32")
+    return (H_out, count, st, done) + ((mask,) if want_mask else ()) + ((rms,) if want_rms else ())
 
 
 MOSAIC_MAX_BATCH = 64
