@@ -22,6 +22,7 @@
 // which is the quantity screen_err_coeff budgets (the representation error of the images is bounded separately, from
 // measured residual norms, and is not part of this premise).
 #include "nm_common.hpp"
+#include "nm_match_fp.hpp"
 #include "../../include/nm_abi.h"
 
 namespace {
@@ -201,19 +202,8 @@ __global__ __launch_bounds__(64) void selftest_instr_kernel(float *__restrict__ 
 constexpr int DIM = 128;
 constexpr int NFAM = 8;
 
-__device__ __forceinline__ unsigned bf16_rne_bits(float x)
-{
-    const unsigned u = __float_as_uint(x);
-    return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
-}
-__device__ __forceinline__ void bf16_three_bits(float n, unsigned &h, unsigned &m, unsigned &l)
-{
-    const unsigned uh = __float_as_uint(n) & 0xFFFF0000u;
-    const float r1 = n - __uint_as_float(uh);
-    const unsigned um = __float_as_uint(r1) & 0xFFFF0000u;
-    const float r2 = r1 - __uint_as_float(um);
-    h = uh >> 16; m = um >> 16; l = __float_as_uint(r2) >> 16;
-}
+using nm_match::bf16_rne;              // the matcher's own bf16 pieces: the chains below split as its kernels do
+using nm_match::bf16_three;
 
 // element k of row `row` (0..31 = queries a, 32..63 = candidates b) of family `fam`; partner = the same element of the
 // query row with the same index (candidates of the duplicate families are built from it)
@@ -261,9 +251,9 @@ __global__ __launch_bounds__(64) void selftest_chain_kernel(float *__restrict__ 
                     if (INSTR == 1) {
                         img[lane][k] = __builtin_bit_cast(unsigned short, (_Float16)sx);
                     } else {
-                        const unsigned hi = bf16_rne_bits(sx);
+                        const unsigned hi = bf16_rne(sx);
                         img[lane][k] = (unsigned short)hi;
-                        img_lo[lane][k] = (unsigned short)bf16_rne_bits(sx - __uint_as_float(hi << 16));
+                        img_lo[lane][k] = (unsigned short)bf16_rne(sx - __uint_as_float(hi << 16));
                     }
                 }
                 s_norm[lane] = (float)nrm;
@@ -273,11 +263,11 @@ __global__ __launch_bounds__(64) void selftest_chain_kernel(float *__restrict__ 
         // the chain: norm k-slots (candidate: nb_h, nb_m, nb_l, 1, 1, 1, 0, 0; query, lanes of k = 0..7 only: 1, 1, 1, na_h, na_m,
         // na_l, 0, 0), then the k-steps t = 0..7 (k = 16 t + 8 h .. + 7), as f16_slots / f16_kstep / bf16_kstep issue them
         unsigned nh, nm, nl;
-        bf16_three_bits(s_norm[32 + r], nh, nm, nl);
+        bf16_three(s_norm[32 + r], nh, nm, nl);
         const u32x4 cslot = {nh | (nm << 16), nl | (0x3F80u << 16), 0x3F80u | (0x3F80u << 16), 0u};
         u32x4 qslot = {0u, 0u, 0u, 0u};
         if (h == 0) {
-            bf16_three_bits(s_norm[r], nh, nm, nl);
+            bf16_three(s_norm[r], nh, nm, nl);
             qslot = (u32x4){0x3F80u | (0x3F80u << 16), 0x3F80u | (nh << 16), nm | (nl << 16), 0u};
         }
         f32x16 acc;

@@ -16,8 +16,10 @@ for src in srcs:
     obj = os.path.join(B.BUILD, "variant_%s_%s.o" % (name, os.path.basename(src)))
     subprocess.check_call([B.HIPCC] + B.FLAGS + flags + ["-c", os.path.join(B.CSRC, src), "-o", obj])
     vobjs.append(obj)
-objs = [os.path.join(B.BUILD, f) for f in os.listdir(B.BUILD)
-        if f.endswith(".o") and not f.startswith("variant_") and f not in [os.path.basename(x) + ".o" for x in srcs]]
+# the objects of the build's CURRENT sources, not whatever _build/ holds: an object left behind by a source that was since renamed
+# or merged into another unit would define its symbols a second time
+known = B.KERNEL_SOURCES + B.SIFT_SOURCES + B.KERNEL_CPP + B.SIFT_CPP + B.UTIL_CPP
+objs = [os.path.join(B.BUILD, f + ".o") for f in known if f not in [os.path.basename(x) for x in srcs]]
 lib = os.path.join(out_dir, "libnm_hip_%s.so" % name)
 subprocess.check_call([B.HIPCC, "--offload-arch=" + B.ARCH, "-shared", "-fPIC", "-o", lib] + vobjs + objs)
 for obj in vobjs:                  # the variant's objects are only link inputs: ~0.5 MB each, a hundred of them once rode every gpurun push

@@ -1,5 +1,5 @@
 """Where a tile iteration of match_coarse_kernel spends its cycles: reads the s_memtime stamps of a -DNM_COARSE_STAMPS=1 build
-(python tools/build_variant.py stamps nm_match.hip -DNM_COARSE_STAMPS=1; NM_DIAGNOSTIC=1 NM_HIP_LIB=tools/_variants/libnm_hip_stamps.so).
+(python tools/build_variant.py stamps nm_match_screen.hip -DNM_COARSE_STAMPS=1; NM_DIAGNOSTIC=1 NM_HIP_LIB=tools/_variants/libnm_hip_stamps.so).
 Shares only: the stamps' fences forbid overlaps the product has."""
 import ctypes as C, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
