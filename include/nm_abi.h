@@ -535,6 +535,65 @@ NM_API int nm_ransac_refit_host_f32(int model, int n,
                                     float *H_out, int *count, int *status, int *rounds_done, unsigned char *mask,
                                     float *rms);
 
+/* Batched homography-guided matching (no reference counterpart: the reference's matcher is blind and nothing returns to the
+ * descriptors once a model is known). Given pair k's map H_k (frame A pixels -> frame B pixels, e.g. H_out of
+ * nm_ransac_refit_batch_dev_f32), every row of A is matched again, by the reference's scan, against those rows of B alone
+ * that lie within sqrt(radius2) pixels of where H_k sends it: more correspondences than the blind ratio test keeps, all of
+ * them inliers of H_k, ready for a second refit. n <= NM_MATCH_GUIDED_MAX_BATCH pairs in THREE launches on `stream`
+ * whatever n is (pair slots 0-31, slots 32-63, the counts); no allocation, no synchronisation, no host read, no workspace
+ * -- capturable into a HIP graph behind the refit. Brute-force gating (every row of A against every row of B); a spatial
+ * grid over B is out of scope. Pair k (tables of n pointers, the tables themselves in HOST memory):
+ *   A[k] / B[k]        descriptors, nA x 128 / nB x 128 row-major (an arena's desc);
+ *   ax, ay / bx, by    the rows' keypoint coordinates (an arena's x / y);
+ *   d_nA[k], d_nB[k]   DEVICE ints, the row counts: nA = clip(*d_nA[k], 0, capA), nB = clip(*d_nB[k], 0, capB). Rows beyond
+ *                      them are never read;
+ *   H + 9 k            device, nine floats row-major; status_in: device, n ints, NULL = all 1.
+ * Per pair, all fp32 (fma explicit, IEEE division):
+ *   Unusable pair: status_in[k] != 1 or a non-finite value in H_k: result[k][0 .. capA) = -1, count[k] = 0
+ *     (best_distance[k][0 .. capA) = +inf).
+ *   Valid rows: i < nA with ax[i] >= 0 (the rule of nm_ransac_batch_dev_f32 and of the refit; a NaN is not >= 0). Any
+ *     other row has no candidates.
+ *   Gate: candidate j < nB passes for row i exactly when nmr_is_inlier(H_k, ax[i], ay[i], bx[j], by[j], radius2) holds
+ *     (csrc/nm_ransac_math.hpp), i.e. with h = H_k
+ *       x = fmaf(h0, ax, h1 * ay) + h2;  y = fmaf(h3, ax, h4 * ay) + h5;  z = fmaf(h6, ax, h7 * ay) + h8;
+ *       px = x / z;  py = y / z;  ex = bx[j] - px;  ey = by[j] - py;  fmaf(ex, ex, ey * ey) < radius2
+ *     (px, py are computed once per row: the same operations, the same bits). A NaN anywhere fails the gate, so a row
+ *     projected with z = 0 has no candidates; so has every row when radius2 <= 0.
+ *   Distance of a gated candidate: the chain of nm_bf_distance_f32, acc = 0; acc = fmaf(t, t, acc) with t = A[i][q] - B[j][q],
+ *     q = 0 .. 127 in this order -- bit-equal to it.
+ *   Decision: get_sift_matches' scan (kernels/match.cu:88-116) over the gated candidates in ascending j: the first one sets
+ *     min1 (whatever its value) and the index, min2 starts at 2139095040.0f; a later d with d < min1 moves min1 to min2 and
+ *     takes its place, else d < min2 replaces min2 (strict <). The row's result is the index when min2 > 0 and
+ *     min1 / min2 < ambiguity and min1 < max_distance (+inf disables the last test), else -1; -1 also without any gated
+ *     candidate. With a gate that passes every candidate and max_distance = +inf the result therefore equals
+ *     nm_sift_match_f32 on a prior of -1, bit for bit (nB >= 1).
+ * Outputs: result[k] (device, capA ints; ALL capA entries are written, -1 beyond nA), count (device, n ints: entries >= 0 of
+ * result[k]), best_distance (optional table, may be NULL: best_distance[k] device, capA floats = the row's min1, +inf for
+ * a row without a gated candidate). result[k] can go to nm_ransac_refit_batch_dev_f32 as matches[k] as it is. A pair's
+ * outputs depend on that pair's inputs alone, never on n, on the pair's slot or on scheduling (no atomics).
+ * Returns hipErrorInvalidValue, touching no device memory, for n not in [1, 64], capA or capB not in [1, 2^22), a non-finite
+ * radius2 or ambiguity, a NaN max_distance, a NULL required pointer (every argument but status_in, best_distance and
+ * stream) or a NULL among the first n entries of a table.
+ * nm_sift_match_guided_host_f32: the same with every pointer in host memory (nA[k] / nB[k] point to host ints), compiled
+ * from the same functions (csrc/nm_match_guided_math.hpp): host and device results are identical bit for bit.          */
+#define NM_MATCH_GUIDED_MAX_BATCH 64
+NM_API int nm_sift_match_guided_batch_dev_f32(int n,
+                                              const float *const *A, const float *const *ax, const float *const *ay,
+                                              const int *const *d_nA, int capA,
+                                              const float *const *B, const float *const *bx, const float *const *by,
+                                              const int *const *d_nB, int capB,
+                                              const float *H, const int *status_in, float radius2, float ambiguity,
+                                              float max_distance, int *const *result, int *count,
+                                              float *const *best_distance, void *stream);
+NM_API int nm_sift_match_guided_host_f32(int n,
+                                         const float *const *A, const float *const *ax, const float *const *ay,
+                                         const int *const *nA, int capA,
+                                         const float *const *B, const float *const *bx, const float *const *by,
+                                         const int *const *nB, int capB,
+                                         const float *H, const int *status_in, float radius2, float ambiguity,
+                                         float max_distance, int *const *result, int *count,
+                                         float *const *best_distance);
+
 /* ---- Mosaic plan and batched blend (no reference counterpart: the reference's client places frames on the host and
  * calls transform_blend once per frame). Together with nm_ransac_batch_dev_f32 the chain detect -> match -> RANSAC ->
  * plan -> blend runs on one stream with no host read and can be captured into one HIP graph.

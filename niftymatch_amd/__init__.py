@@ -106,6 +106,8 @@ _SIGNATURES = {
     "nm_ransac_batch_sample": (_I, [C.c_uint, _I, _I, _I, _I]),
     "nm_ransac_refit_batch_dev_f32": (_I, [_I, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _F, _I, _P, _P, _P, _P, _P, _P, _P]),
     "nm_ransac_refit_host_f32": (_I, [_I, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _F, _I, _P, _P, _P, _P, _P, _P]),
+    "nm_sift_match_guided_batch_dev_f32": (_I, [_I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _P, _F, _F, _F, _P, _P, _P, _P]),
+    "nm_sift_match_guided_host_f32": (_I, [_I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _P, _F, _F, _F, _P, _P, _P]),
     "nm_mosaic_plan_f32": (_I, [_I, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "nm_mosaic_plan_host_f32": (_I, [_I, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "nm_transform_blend_batch": (_I, [_P, _I, _I, _P, _I, _P, _I, _I, _P, _I, _P, _I, _P, _P]),
@@ -886,6 +888,110 @@ def ransac_refit_host(model, src_xs, src_ys, nAs, dst_xs, dst_ys, matches, H, st
                                           int(rounds), ptr(H_out), ptr(count), ptr(st), ptr(done), ptr(mask), ptr(rms)),
            "nm_ransac_refit_host_f32")
     return (H_out, count, st, done) + ((mask,) if want_mask else ()) + ((rms,) if want_rms else ())
+
+
+MATCH_GUIDED_MAX_BATCH = 64
+
+
+def _guided_check(n, lens, capA, capB, radius2, ambiguity, max_distance):
+    inf = float("inf")
+    if any(l != n for l in lens) or not 0 < n <= MATCH_GUIDED_MAX_BATCH:
+        raise NmError("bad batch")
+    if not (1 <= capA < (1 << 22) and 1 <= capB < (1 << 22)):
+        raise NmError("capacity out of range")
+    if radius2 != radius2 or ambiguity != ambiguity or radius2 in (inf, -inf) or ambiguity in (inf, -inf):
+        raise NmError("radius2 and ambiguity must be finite")
+    if max_distance != max_distance:
+        raise NmError("max_distance must not be NaN")
+
+
+def _guided_caps(As, axs, ays, Bs, bxs, bys, capA, capB):
+    capA = min(min(t.shape[0] for t in As), min(t.shape[0] for t in axs), min(t.shape[0] for t in ays)) if capA is None else capA
+    capB = min(min(t.shape[0] for t in Bs), min(t.shape[0] for t in bxs), min(t.shape[0] for t in bys)) if capB is None else capB
+    if any(t.shape[0] < capA for t in list(As) + list(axs) + list(ays)) or \
+            any(t.shape[0] < capB for t in list(Bs) + list(bxs) + list(bys)):
+        raise NmError("a descriptor or coordinate tensor is smaller than the capacity")
+    if any(t.ndim != 2 or t.shape[1] != 128 for t in list(As) + list(Bs)):
+        raise NmError("descriptors must be (rows, 128)")
+    return capA, capB
+
+
+def sift_match_guided_batch_dev(As, axs, ays, d_nAs, Bs, bxs, bys, d_nBs, H, status=None, radius2=9.0, ambiguity=0.8,
+                                max_distance=float("inf"), capA=None, capB=None, results=None, want_distance=False):
+    """Homography-guided matching of n = len(As) <= MATCH_GUIDED_MAX_BATCH pairs (nm_sift_match_guided_batch_dev_f32): three
+    launches on the current stream, no host read. As / Bs are float32 device descriptors (rows, 128), axs .. bys the rows'
+    coordinates, d_nAs / d_nBs int32 DEVICE sizes (e.g. SiftArena.desc, .x, .y, .num_items); H float32 device (n, 9) or
+    (n, 3, 3) mapping A pixels to B pixels (e.g. the refit's H_out), status int32 device (n,) or None. Row i of A is matched
+    by the reference's scan against the rows of B within sqrt(radius2) pixels of H(ax, ay); max_distance bounds the best
+    descriptor distance (inf = no bound). results: n int32 device tensors of >= capA rows to write into (default: new).
+    Returns (results, count[n]) and, with want_distance, the list of float32 (capA,) best distances. results[k] plugs into
+    ransac_refit_batch_dev(matches=...)."""
+    torch = _torch()
+    n = len(As)
+    lens = [len(v) for v in (axs, ays, d_nAs, Bs, bxs, bys, d_nBs)] + ([len(results)] if results is not None else [])
+    if n == 0 or any(l != n for l in lens):
+        raise NmError("bad batch")
+    capA, capB = _guided_caps(As, axs, ays, Bs, bxs, bys, capA, capB)
+    _guided_check(n, lens, capA, capB, radius2, ambiguity, max_distance)
+    device = As[0].device
+    if results is None:
+        results = [torch.empty(capA, dtype=torch.int32, device=device) for _ in range(n)]
+    if any(r.shape[0] < capA for r in results):
+        raise NmError("a result tensor is smaller than the capacity")
+    tensors = list(As) + list(axs) + list(ays) + list(d_nAs) + list(Bs) + list(bxs) + list(bys) + list(d_nBs) + \
+        list(results) + [H] + ([status] if status is not None else [])
+    if any(t.device != device for t in tensors) or device.type != "cuda" or torch.cuda.current_device() != device.index:
+        raise NmError("all tensors must live on the current device")
+    if any(c.numel() < 1 for c in list(d_nAs) + list(d_nBs)):
+        raise NmError("a device size tensor is empty")
+    if H.numel() != 9 * n or (status is not None and status.numel() != n):
+        raise NmError("H must hold n x 9 floats and status n values")
+    count = torch.empty(n, dtype=torch.int32, device=device)
+    best = [torch.empty(capA, dtype=torch.float32, device=device) for _ in range(n)] if want_distance else None
+    arr = lambda ts, dt: (C.c_void_p * n)(*[_dev(t, dt) for t in ts])
+    f, i32 = torch.float32, torch.int32
+    _check(lib().nm_sift_match_guided_batch_dev_f32(n, arr(As, f), arr(axs, f), arr(ays, f), arr(d_nAs, i32), capA,
+                                                    arr(Bs, f), arr(bxs, f), arr(bys, f), arr(d_nBs, i32), capB,
+                                                    _dev(H, f), _dev(status, i32) if status is not None else None,
+                                                    radius2, ambiguity, max_distance, arr(results, i32), _dev(count),
+                                                    arr(best, f) if want_distance else None, _stream()),
+           "nm_sift_match_guided_batch_dev_f32")
+    return (results, count) + ((best,) if want_distance else ())
+
+
+def sift_match_guided_host(As, axs, ays, nAs, Bs, bxs, bys, nBs, H, status=None, radius2=9.0, ambiguity=0.8,
+                           max_distance=float("inf"), capA=None, capB=None, want_distance=False):
+    """sift_match_guided_batch_dev on the host (nm_sift_match_guided_host_f32, the same functions): numpy in and out,
+    bit-identical results. nAs / nBs are host ints. Returns (results (n, capA) int32, count (n,)) and, with want_distance,
+    best distances (n, capA) float32."""
+    import numpy as np
+    n = len(As)
+    lens = [len(v) for v in (axs, ays, nAs, Bs, bxs, bys, nBs)]
+    if n == 0 or any(l != n for l in lens):
+        raise NmError("bad batch")
+    f32 = lambda vs: [np.ascontiguousarray(v, dtype=np.float32) for v in vs]
+    As, Bs = f32(As), f32(Bs)
+    axs, ays, bxs, bys = ([v.reshape(-1) for v in f32(vs)] for vs in (axs, ays, bxs, bys))
+    capA, capB = _guided_caps(As, axs, ays, Bs, bxs, bys, capA, capB)
+    _guided_check(n, lens, capA, capB, radius2, ambiguity, max_distance)
+    H = np.ascontiguousarray(H, dtype=np.float32).reshape(-1)
+    if status is not None:
+        status = np.ascontiguousarray(status, dtype=np.int32).reshape(-1)
+    if H.size != 9 * n or (status is not None and status.size != n):
+        raise NmError("H must hold n x 9 floats and status n values")
+    nA = np.array([int(v) for v in nAs], np.int32)
+    nB = np.array([int(v) for v in nBs], np.int32)
+    result = np.zeros((n, capA), np.int32)
+    count = np.zeros(n, np.int32)
+    best = np.zeros((n, capA), np.float32) if want_distance else None
+    arr = lambda vals: (C.c_void_p * n)(*[v.ctypes.data for v in vals])
+    _check(lib().nm_sift_match_guided_host_f32(n, arr(As), arr(axs), arr(ays), arr([nA[k:k + 1] for k in range(n)]), capA,
+                                               arr(Bs), arr(bxs), arr(bys), arr([nB[k:k + 1] for k in range(n)]), capB,
+                                               H.ctypes.data, status.ctypes.data if status is not None else None, radius2,
+                                               ambiguity, max_distance, arr(list(result)), count.ctypes.data,
+                                               arr(list(best)) if want_distance else None),
+           "nm_sift_match_guided_host_f32")
+    return (result, count) + ((best,) if want_distance else ())
 
 
 MOSAIC_MAX_BATCH = 64
