@@ -20,6 +20,16 @@
 
 static inline int nm_divup(int a, int b) { return (a + b - 1) / b; }
 
+// float -> unsigned char, the ONE rule of every such store of the image, warp, blend and ingest kernels: truncate toward
+// zero, clamp to [0, 255], NaN -> 0. Equal to the plain C cast for every v in (-1, 256), where the cast is defined; outside
+// it the C cast is undefined on the host and hardware-defined on the device, and the reference's own result there cannot
+// be observed without its hardware (parity unpinned). oracle/nmo_math.h has the same rule as nmo_u8_sat.
+__host__ __device__ __forceinline__ unsigned char nm_u8_sat(float v)
+{
+    if (!(v >= 0.f)) return 0;                      // negatives, -0.0 truncates to 0 either way, NaN
+    return v >= 255.f ? (unsigned char)255 : (unsigned char)v;
+}
+
 // Compute units / XCDs of the CURRENT device, read once per device from hipDeviceProp_t (a partitioned mode such as CPX
 // shows 32 CUs and one XCD per device). Without a device (host-only planning calls on a CPU box) the MI355X SPX values
 // 256 / 8 are assumed. XCDs are not a device property: 32 CUs per XCD on gfx950.

@@ -36,7 +36,7 @@ __global__ __launch_bounds__(256) void put_channel_kernel(uchar4 *__restrict__ b
     const size_t stride = (size_t)gridDim.x * 256;
     for (; i < n; i += stride) {
         uchar4 p = bgra[i];
-        const unsigned char v = (unsigned char)in[i];
+        const unsigned char v = nm_u8_sat(in[i]);
         if (channel == 0) p.x = v;
         else if (channel == 1) p.y = v;
         else if (channel == 2) p.z = v;
@@ -59,7 +59,7 @@ __global__ __launch_bounds__(256) void cast_f32_u8_kernel(const float *__restric
     const size_t stride = (size_t)gridDim.x * 256;
     for (; i < n; i += stride) {
         const float v = src[i];
-        dst[i] = (max_val != 0 && v >= (float)max_val) ? max_val : (unsigned char)v;    // cast.cu:17-19
+        dst[i] = (max_val != 0 && v >= (float)max_val) ? max_val : nm_u8_sat(v);    // cast.cu:17-19
     }
 }
 

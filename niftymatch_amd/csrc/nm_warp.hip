@@ -48,7 +48,7 @@ __global__ __launch_bounds__(256) void resample_mask_kernel(unsigned char *__res
     const size_t stride = (size_t)gridDim.x * 256;
     for (; p < n; p += stride) {
         const float r = tex2d_any(t, x[p] + 0.5f, y[p] + 0.5f);
-        result[p] = (r <= lower_limit) ? (unsigned char)0 : (unsigned char)(r * 255.999f);
+        result[p] = (r <= lower_limit) ? (unsigned char)0 : nm_u8_sat(r * 255.999f);
     }
 }
 

@@ -97,8 +97,8 @@ __device__ __forceinline__ void tex2d_u8x4(const Tex &t, float x, float y, float
 // the uchar4 result pixel of a sample, as resample_2D<uchar4> writes it
 __device__ __forceinline__ uchar4 u8x4_of(const float s[4])
 {
-    return make_uchar4((unsigned char)(s[0] * 255.9999f), (unsigned char)(s[1] * 255.9999f),
-                       (unsigned char)(s[2] * 255.9999f), (unsigned char)(s[3] * 255.9999f));
+    return make_uchar4(nm_u8_sat(s[0] * 255.9999f), nm_u8_sat(s[1] * 255.9999f),
+                       nm_u8_sat(s[2] * 255.9999f), nm_u8_sat(s[3] * 255.9999f));
 }
 
 // the denominator of project(m, x, y), same operations
@@ -153,15 +153,15 @@ __device__ __forceinline__ bool blend_sample(const float *m, const Tex &frame, c
 __host__ __device__ __forceinline__ void blend_combine(const float r[4], float nwt, uchar4 &c, float &cwt)
 {
     if (cwt == 0) {
-        c = make_uchar4((unsigned char)(r[0] * 255.9999f), (unsigned char)(r[1] * 255.9999f),
-                        (unsigned char)(r[2] * 255.9999f), 255);
+        c = make_uchar4(nm_u8_sat(r[0] * 255.9999f), nm_u8_sat(r[1] * 255.9999f),
+                        nm_u8_sat(r[2] * 255.9999f), 255);
         cwt = nwt;
     } else {
         const uchar4 cur = c;
         const float sum = cwt + nwt;
-        c.x = (unsigned char)(fmaf_(r[0] * nwt, 255.9999f, (float)cur.x * cwt) / sum);
-        c.y = (unsigned char)(fmaf_(r[1] * nwt, 255.9999f, (float)cur.y * cwt) / sum);
-        c.z = (unsigned char)(fmaf_(r[2] * nwt, 255.9999f, (float)cur.z * cwt) / sum);
+        c.x = nm_u8_sat(fmaf_(r[0] * nwt, 255.9999f, (float)cur.x * cwt) / sum);
+        c.y = nm_u8_sat(fmaf_(r[1] * nwt, 255.9999f, (float)cur.y * cwt) / sum);
+        c.z = nm_u8_sat(fmaf_(r[2] * nwt, 255.9999f, (float)cur.z * cwt) / sum);
         c.w = 255;
         cwt = sum;
     }

@@ -844,7 +844,7 @@ NMO_API void nmo_put_channel(unsigned char *bgra, const float *in, int width, in
 {
     if (channel < 0 || channel > 3) return;
     const size_t n = (size_t)width * height;
-    for (size_t i = 0; i < n; ++i) bgra[4 * i + channel] = (channel == 3) ? 255 : (unsigned char)in[i];
+    for (size_t i = 0; i < n; ++i) bgra[4 * i + channel] = (channel == 3) ? 255 : nmo_u8_sat(in[i]);
 }
 NMO_API void nmo_set_alpha(unsigned char *bgra, int width, int height, unsigned char val)
 {
@@ -855,7 +855,7 @@ NMO_API void nmo_set_alpha(unsigned char *bgra, int width, int height, unsigned 
 NMO_API void nmo_cast_f32_u8(const float *src, size_t cols, size_t rows, unsigned char *dst, unsigned char max_val)
 {
     for (size_t i = 0; i < cols * rows; ++i)
-        dst[i] = (max_val != 0 && src[i] >= (float)max_val) ? max_val : (unsigned char)src[i];
+        dst[i] = (max_val != 0 && src[i] >= (float)max_val) ? max_val : nmo_u8_sat(src[i]);
 }
 /* downsample_by_2<uchar4> -- kernels/downsample.cu:6-17,32 */
 NMO_API void nmo_downsample2_u8x4(unsigned char *result, int rw, int rh, const unsigned char *source, int sw, int sh)
@@ -900,7 +900,7 @@ NMO_API void nmo_resample_mask(unsigned char *result, const void *tex, int tw, i
     const nmo_tex t{tex, tw, th, fmt};
     for (size_t p = 0; p < (size_t)cols * rows; ++p) {
         const float r = nmo_tex2d(t, x[p] + 0.5f, y[p] + 0.5f, 0);
-        result[p] = (r <= threshold) ? 0 : (unsigned char)(r * 255.999f);
+        result[p] = (r <= threshold) ? 0 : nmo_u8_sat(r * 255.999f);
     }
 }
 /* resample_perspective_transform -- resample.cu:84-98,116-204: fills x_pos / y_pos, then samples the uchar4 texture */
@@ -916,7 +916,7 @@ NMO_API void nmo_resample_perspective(unsigned char *result, const unsigned char
             const size_t p = (size_t)y * cols + x;
             nmo_project(m, (float)x, (float)y, x_pos[p], y_pos[p]);
             for (int c = 0; c < 4; ++c)
-                result[4 * p + c] = (unsigned char)(nmo_tex2d(t, x_pos[p] + 0.5f, y_pos[p] + 0.5f, c) * 255.9999f);
+                result[4 * p + c] = nmo_u8_sat(nmo_tex2d(t, x_pos[p] + 0.5f, y_pos[p] + 0.5f, c) * 255.9999f);
         }
 }
 /* transform_blend -- resample.cu:7-66,218-232. frame (uchar4), frame_mask and frame_wts are fw x fh textures. */
@@ -939,14 +939,14 @@ NMO_API void nmo_transform_blend(unsigned char *canvas, int cw, int ch, const un
             float res[3];
             for (int c = 0; c < 3; ++c) res[c] = nmo_tex2d(tf, u, v, c);
             if (canvas_wts[idx] == 0) {
-                for (int c = 0; c < 3; ++c) canvas[4 * idx + c] = (unsigned char)(res[c] * 255.9999f);
+                for (int c = 0; c < 3; ++c) canvas[4 * idx + c] = nmo_u8_sat(res[c] * 255.9999f);
                 canvas[4 * idx + 3] = 255;
                 canvas_wts[idx] = nwt;
             } else {
                 const float cwt = canvas_wts[idx], sum = cwt + nwt;
                 for (int c = 0; c < 3; ++c)
                     canvas[4 * idx + c] =
-                        (unsigned char)(std::fmaf(res[c] * nwt, 255.9999f, (float)canvas[4 * idx + c] * cwt) / sum);
+                        nmo_u8_sat(std::fmaf(res[c] * nwt, 255.9999f, (float)canvas[4 * idx + c] * cwt) / sum);
                 canvas[4 * idx + 3] = 255;
                 canvas_wts[idx] = cwt + nwt;
             }

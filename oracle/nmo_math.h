@@ -24,6 +24,16 @@
 #include <cstdint>
 #include <cstring>
 
+/* float -> unsigned char, the one rule of every such store of the image, warp and blend stages (the product's nm_u8_sat):
+ * truncate toward zero, clamp to [0, 255], NaN -> 0. Equal to the plain C cast wherever that is defined, (-1, 256). The
+ * reference writes the plain cast, whose result outside that range is hardware-defined and cannot be observed without
+ * its hardware: parity unpinned there. */
+static inline unsigned char nmo_u8_sat(float v)
+{
+    if (!(v >= 0.f)) return 0;
+    return v >= 255.f ? (unsigned char)255 : (unsigned char)v;
+}
+
 static inline float nmo_pow2i_f(int n)            /* exact 2^n, n in [-126,127] */
 {
     uint32_t bits = (uint32_t)(n + 127) << 23;

@@ -9,6 +9,12 @@
  * not the rounding of a, nor the order of the sum. THIS spec: a is rounded to the nearest 1/256 (half up), the four
  * weights are the exact products, the sum runs left to right in binary32 without contraction, 8-bit texels are c/255
  * (IEEE division), coordinates that cannot touch a texel (including NaN/inf) return 0.
+ *
+ * tests/warp_ref.py is a float64 model of the same operations written from the reference and CUDA's formula alone. It
+ * pins what this header shares with the device code: the geometry (projective map, true matrix inverse, undistortion
+ * polynomial), the conventions (sample at coordinate + 0.5, i = floor(x - 0.5), border texels 0, channel order, blend
+ * order and cutoffs) and the filter formula, each to a derived bound. It does NOT pin the rounding of a to 1/256 nor
+ * the order of the sum: both lie inside that bound.
  */
 #ifndef NMO_WARP_H
 #define NMO_WARP_H
