@@ -69,6 +69,7 @@ _SIGNATURES = {
     "nm_sift_match_pairs_per_launch": (_I, [_I]),
     "nm_sift_match_set_distance_mode": (_I, [_I]),
     "nm_sift_set_detect_tall_min": (_I, [_I]),
+    "nm_sift_set_frame_skew": (_I, [_I]),
     "nm_sift_match_get_distance_mode": (_I, []),
     "nm_sift_match_distance_listed": (_I, [_P, _I, _I, _P, _P, _P]),
     "nm_sift_match_f32": (_I, [_P, _I, _P, _I, _P, _P, _F, _P, _P]),
@@ -459,6 +460,13 @@ def set_detect_tall_min(min_groups=-1):
     """Batched detection launches with at least `min_groups` 20-row unit groups take the tall form (default 2048; -1 restores
     it, 2**31 - 1 disables it). Returns the previous value. Results do not depend on it."""
     return lib().nm_sift_set_detect_tall_min(int(min_groups))
+
+
+def set_frame_skew(mode=-1):
+    """Issue order of many-frame detect/describe calls: 0 = every octave's five levels on the caller's stream, 1 = levels 4-5
+    on the detection stream (the small octaves run beside the large ones); -1 restores the default (NM_FRAME_SKEW, 0 when
+    unset). Returns the previous value. Results do not depend on it."""
+    return lib().nm_sift_set_frame_skew(int(mode))
 
 
 DISTANCE_MODES = {"exact": 0, "mfma": 1}

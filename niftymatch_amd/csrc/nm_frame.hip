@@ -2,6 +2,7 @@
 // that runs the reference's implied client loop (orchestration order of sift/siftfunctions.cu:42-181)
 // as one allocation-free, sync-free launch sequence on a stream.
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <new>
 #include <vector>
@@ -84,7 +85,34 @@ static bool frame_driver_writes_dog()
     return v;
 }
 
+// Issue order of the per-octave path (calls of more frames than the octave tail serves). 0: levels 1-5 of every octave on the
+// caller's stream, detection beside the next octave's levels. 1 (skewed): only levels 1-3 -- all that the next octave's level 0
+// needs -- stay on the caller's stream; levels 4-5 go to the side stream in front of the octave's detection, so the chain
+// reaches the small octaves while the large launches of octaves 0-2 still run. Same launches, same results in either order.
+// NM_FRAME_SKEW (read once) is the default; nm_sift_set_frame_skew changes it per call. Off by default: measured, a 64-frame
+// call takes 7 904 us against 7 799 (profiles/r07_a_skew_alternation.txt) -- the side stream becomes one serial chain, and the
+// plain order's pairing of octave o's detection with octave o + 1's levels is lost.
+#ifndef NM_FRAME_SKEW_DEFAULT
+#define NM_FRAME_SKEW_DEFAULT 0
+#endif
+static int frame_skew_default()
+{
+    static const int v = [] {
+        const char *e = getenv("NM_FRAME_SKEW");
+        const int m = e ? atoi(e) : NM_FRAME_SKEW_DEFAULT;
+        return (m == 0 || m == 1) ? m : NM_FRAME_SKEW_DEFAULT;
+    }();
+    return v;
+}
+static std::atomic<int> g_frame_skew{-1};          // -1: the default
+
 extern "C" {
+
+int nm_sift_set_frame_skew(int mode)
+{
+    const int prev = g_frame_skew.exchange((mode == 0 || mode == 1) ? mode : -1);
+    return prev < 0 ? frame_skew_default() : prev;
+}
 
 const char *nm_version(void) { return "niftymatch_amd 0.1.0 gfx950"; }
 int nm_device_count(int *count) { return (int)hipGetDeviceCount(count); }
@@ -381,13 +409,16 @@ float *nm_sift_arena_level(nm_sift_arena *a, int l) { return (a && l >= 0 && l <
 float *nm_sift_arena_dog(nm_sift_arena *a, int d) { return (a && d >= 0 && d < 5) ? a->dog[0][d] : nullptr; }
 float *nm_sift_arena_grad(nm_sift_arena *a) { return a ? a->grad[0] : nullptr; }
 
+// i_first .. i_last: the levels this call computes (the skewed order issues 1-3 and 4-5 on different streams; the octave-0
+// profile site then begins in front of level 1 on the one and ends behind level 5 on the other)
 static int octave_pyramid(nm_sift_arena *const *as, int n, int o, int ow, int oh, bool store_top, bool decimate,
-                          hipStream_t st, bool write_dog = true, bool per_octave = false, bool write_grad = true)
+                          hipStream_t st, bool write_dog = true, bool per_octave = false, bool write_grad = true,
+                          int i_first = 1, int i_last = 5)
 {
-    if (o == 0) nm_prof_begin(NM_PROF_PYRAMID_O0, st);
+    if (o == 0 && i_first == 1) nm_prof_begin(NM_PROF_PYRAMID_O0, st);
     const size_t plane = (size_t)ow * oh;
     int rc = 0;
-    for (int i = 1; i < 6 && !rc; ++i) {
+    for (int i = i_first; i <= i_last && !rc; ++i) {
         // the launch that blurs level i-1 into level i also emits DoG i-1 and, for i-1 in 1..3, the gradient plane
         // i-2 of level i-1 (compute_gradients: level l from octave[l+1], sift/siftfunctions.cu:53-63)
         NmConvBatch b{};
@@ -405,7 +436,7 @@ static int octave_pyramid(nm_sift_arena *const *as, int n, int o, int ow, int oh
         }
         rc = nm_launch_convolve_batch(b, ow, oh, as[0]->taps[i - 1], as[0]->radii[i - 1], st);
     }
-    if (o == 0) nm_prof_end(NM_PROF_PYRAMID_O0, st);
+    if (o == 0 && i_last == 5) nm_prof_end(NM_PROF_PYRAMID_O0, st);
     return rc;
 }
 
@@ -486,6 +517,9 @@ int nm_sift_detect_describe_batch(nm_sift_arena *const *as, int n, const float *
     for (int f = 0; f < n; ++f)
         use_tail = use_tail && as[f]->tail_ok && as[f]->tail.T == as[0]->tail.T && as[f]->tail.n_oct == as[0]->tail.n_oct;
     const int first_tail = use_tail ? as[0]->tail.T : P._num_octaves;
+    // the skewed issue order (see g_frame_skew) is for the per-octave path with one description pass
+    const int skew_cfg = g_frame_skew.load(std::memory_order_relaxed);
+    const int skew = (use_tail || split) ? 0 : (skew_cfg < 0 ? frame_skew_default() : skew_cfg);
     // With the tail, the octaves < T (98 % of a frame's keypoints) are described on the description stream as soon as octave
     // T - 1 has been detected, BESIDE the tail launch; the few keypoints of the tail octaves follow behind its scans.
     if (use_tail) split = first_tail;
@@ -512,7 +546,9 @@ int nm_sift_detect_describe_batch(nm_sift_arena *const *as, int n, const float *
                 da.geom[o].ow = ow; da.geom[o].oh = oh; da.geom[o].xper = xper;
                 continue;
             }
-            int e = octave_pyramid(as, n, o, ow, oh, !dogs, o + 1 < P._num_octaves, st, dogs, true);
+            // skewed order: the caller's stream carries levels 1-3 only (level 3's launch decimates into the next octave's level
+            // 0; nothing of octave o + 1 reads levels 4-5), ev_pyr[o] then stands behind level 3
+            int e = octave_pyramid(as, n, o, ow, oh, !dogs, o + 1 < P._num_octaves, st, dogs, true, true, 1, skew ? 3 : 5);
             if (e) return e;
             NM_RETURN_IF(hipEventRecord(as[0]->ev_pyr[o], st));
             if (use_tail && o + 1 == first_tail) {
@@ -524,6 +560,13 @@ int nm_sift_detect_describe_batch(nm_sift_arena *const *as, int n, const float *
             }
             NM_RETURN_IF(hipStreamWaitEvent(side, as[0]->ev_pyr[o], 0));
             forked = true;
+            if (skew) {
+                // levels 4-5 in front of the octave's detection: they write planes of octave o alone (levels 4-5, gradient
+                // plane 2) and read levels 3-4, which the caller's stream no longer touches -- no buffer is shared with the
+                // launches of the octaves > o that now run beside them
+                e = octave_pyramid(as, n, o, ow, oh, !dogs, false, side, dogs, true, true, 4, 5);
+                if (e) return e;
+            }
 
             const int nseg = nm_divup(ow, NM_DET_SEG_W);
             const int n_blocks = oh * nseg;
