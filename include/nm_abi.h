@@ -195,9 +195,12 @@ NM_API int nm_find_keypoints3_compact_f32(const float *const dog[5], int width, 
 NM_API int nm_sift_set_detect_tall_min(int min_groups);
 /* Process-wide: issue order of detect/describe calls that take the per-octave launches (more frames than the octave tail
  * serves). 0: levels 1-5 of every octave on the caller's stream; 1: levels 4-5 go to the detection stream in front of the
- * octave's detection, so that the small octaves' launches run beside the large octaves'. Same launches and identical results
- * in either order (tests/test_gpu_frame_skew.py). Any other value restores the default (NM_FRAME_SKEW in the environment,
- * read once; 0 when unset). Returns the previous value. */
+ * octave's detection, so that the small octaves' launches run beside the large octaves'; 2 (cross): levels 4-5 go to a third
+ * stream (the arena's description stream) instead, detection stays beside the next octave's levels 1-3 -- the call then uses
+ * three streams, and a captured call is a graph with three parallel branches. Same launches and identical results in every
+ * order (tests/test_gpu_frame_skew.py, tests/test_gpu_frame_cross.py). Any other value restores the default (NM_FRAME_SKEW in
+ * the environment, read once; 0 when unset). Orders 1 and 2 apply to calls with one description pass that take the per-octave
+ * launches; every other call is issued in order 0. Returns the previous value. */
 NM_API int nm_sift_set_frame_skew(int mode);
 /* nm_compact_keypoints for three dense maps at once (three launches instead of nine); d_counts: 3 device ints. */
 NM_API size_t nm_compact3_workspace_bytes(int num_pixels);

@@ -464,8 +464,9 @@ def set_detect_tall_min(min_groups=-1):
 
 def set_frame_skew(mode=-1):
     """Issue order of many-frame detect/describe calls: 0 = every octave's five levels on the caller's stream, 1 = levels 4-5
-    on the detection stream (the small octaves run beside the large ones); -1 restores the default (NM_FRAME_SKEW, 0 when
-    unset). Returns the previous value. Results do not depend on it."""
+    on the detection stream (the small octaves run beside the large ones), 2 = levels 4-5 on a third stream (detection stays
+    beside the next octave's levels 1-3); -1 restores the default (NM_FRAME_SKEW, 0 when unset). Returns the previous value.
+    Results do not depend on it."""
     return lib().nm_sift_set_frame_skew(int(mode))
 
 

@@ -42,8 +42,10 @@ struct nm_sift_arena {
                                // pyramid is being computed, so the octaves cannot share planes
     float *dog[20][5];         // DoG planes PER OCTAVE: detection of octave o overlaps the pyramid of octave o+1
     hipStream_t side;          // detection / compaction stream forked off the caller's stream
-    hipStream_t desc;          // orientation + descriptors of the large octaves, beside the small octaves' pyramids / detection
+    hipStream_t desc;          // orientation + descriptors of the large octaves, beside the small octaves' pyramids / detection;
+                               // in the cross issue order (g_frame_skew 2) levels 4-5 of every octave instead
     hipEvent_t ev_pyr[20], ev_join, ev_det, ev_desc;
+    hipEvent_t ev_top[20];     // cross issue order: behind level 5 of octave o on the desc stream
     float *grad[20];           // per octave: 3 float2 planes
     size_t grad_off[20];       // grad[o] = grad[0] + grad_off[o]: the gradient planes of all octaves are one block
     size_t plane_stride[20];   // floats between consecutive levels / DoG planes of an octave (one block per octave)
@@ -92,6 +94,24 @@ static bool frame_driver_writes_dog()
 // NM_FRAME_SKEW (read once) is the default; nm_sift_set_frame_skew changes it per call. Off by default: measured, a 64-frame
 // call takes 7 904 us against 7 799 (profiles/r07_a_skew_alternation.txt) -- the side stream becomes one serial chain, and the
 // plain order's pairing of octave o's detection with octave o + 1's levels is lost.
+// 2 (cross): order 1 with levels 4-5 on a THIRD stream (the arena's desc stream, idle on this path), which keeps the plain
+// order's pairing: per octave o, levels 1-3 of octave o + 1 on the caller's stream, levels 4-5 of octave o on the third, detection
+// of octave o - 1 on the side stream. Caller's stream: base blur, levels 1-3 of every octave, ev_pyr[o] behind level 3. Third
+// stream: waits for ev_pyr[o], levels 4-5 of octave o, ev_top[o] behind level 5. Side stream: waits for ev_top[o], then detection,
+// scan and gather of octave o in octave order; the description follows on it, as in the plain order.
+// What the orders 1 and 2 rely on (each checked where the order is issued):
+//  * levels 4-5 read levels 3-4 of their own octave and write levels 4, 5 and gradient plane 2 of that octave; the caller's
+//    stream, past ev_pyr[o], touches none of octave o's planes again within the call (level 3's launch wrote the next octave's
+//    level 0 before the event);
+//  * the convolution launches have no scratch: two of them in flight share the (read-only) taps alone;
+//  * detection's staging, counts, offsets and the book are used on the side stream alone, in octave order;
+//  * the description reads gradient planes 0-1 written on the caller's stream and plane 2 written on the side (1) or third (2)
+//    stream: it runs on the side stream, which has waited for ev_pyr[o] (1) or for ev_top[o], recorded behind a wait for
+//    ev_pyr[o] (2), of EVERY octave, and carries every gather;
+//  * the octave-0 profile site begins in front of level 1 on the caller's stream and ends behind level 5 on the stream that
+//    issues it (octave_pyramid);
+//  * the next call on the same arenas starts on the caller's stream, which both helper streams join directly at the end of
+//    this call on every return path: its base blur and levels stand behind this call's third-stream and side-stream work.
 #ifndef NM_FRAME_SKEW_DEFAULT
 #define NM_FRAME_SKEW_DEFAULT 0
 #endif
@@ -100,7 +120,7 @@ static int frame_skew_default()
     static const int v = [] {
         const char *e = getenv("NM_FRAME_SKEW");
         const int m = e ? atoi(e) : NM_FRAME_SKEW_DEFAULT;
-        return (m == 0 || m == 1) ? m : NM_FRAME_SKEW_DEFAULT;
+        return (m >= 0 && m <= 2) ? m : NM_FRAME_SKEW_DEFAULT;
     }();
     return v;
 }
@@ -110,7 +130,7 @@ extern "C" {
 
 int nm_sift_set_frame_skew(int mode)
 {
-    const int prev = g_frame_skew.exchange((mode == 0 || mode == 1) ? mode : -1);
+    const int prev = g_frame_skew.exchange((mode >= 0 && mode <= 2) ? mode : -1);
     return prev < 0 ? frame_skew_default() : prev;
 }
 
@@ -177,7 +197,7 @@ int nm_sift_arena_create(int width, int height, int capacity, nm_sift_arena **ou
     a->mask = nullptr;
     a->device = -1;
     (void)hipGetDevice(&a->device);
-    for (int o = 0; o < 20; ++o) a->ev_pyr[o] = nullptr;
+    for (int o = 0; o < 20; ++o) a->ev_pyr[o] = a->ev_top[o] = nullptr;
     a->params = SiftParams(width, height);
     a->npix = (size_t)width * height;
     a->bytes = 0;
@@ -218,6 +238,7 @@ int nm_sift_arena_create(int width, int height, int capacity, nm_sift_arena **ou
         for (int o = 0; o < P._num_octaves; ++o) a->grad[o] = blk + a->grad_off[o];
     }
     for (int o = 0; !rc && o < P._num_octaves; ++o) rc = (int)hipEventCreateWithFlags(&a->ev_pyr[o], hipEventDisableTiming);
+    for (int o = 0; !rc && o < P._num_octaves; ++o) rc = (int)hipEventCreateWithFlags(&a->ev_top[o], hipEventDisableTiming);
     if (!rc) rc = (int)hipEventCreateWithFlags(&a->ev_join, hipEventDisableTiming);
     if (!rc) rc = (int)hipEventCreateWithFlags(&a->ev_det, hipEventDisableTiming);
     if (!rc) rc = (int)hipEventCreateWithFlags(&a->ev_desc, hipEventDisableTiming);
@@ -284,6 +305,8 @@ void nm_sift_arena_destroy(nm_sift_arena *a)
     if (a->ev_desc) (void)hipEventDestroy(a->ev_desc);
     for (int o = 0; o < 20; ++o)
         if (a->ev_pyr[o]) (void)hipEventDestroy(a->ev_pyr[o]);
+    for (int o = 0; o < 20; ++o)
+        if (a->ev_top[o]) (void)hipEventDestroy(a->ev_top[o]);
     if (a->ev_join) (void)hipEventDestroy(a->ev_join);
     for (void *p : a->allocs) (void)hipFree(p);
     delete a;
@@ -409,7 +432,7 @@ float *nm_sift_arena_level(nm_sift_arena *a, int l) { return (a && l >= 0 && l <
 float *nm_sift_arena_dog(nm_sift_arena *a, int d) { return (a && d >= 0 && d < 5) ? a->dog[0][d] : nullptr; }
 float *nm_sift_arena_grad(nm_sift_arena *a) { return a ? a->grad[0] : nullptr; }
 
-// i_first .. i_last: the levels this call computes (the skewed order issues 1-3 and 4-5 on different streams; the octave-0
+// i_first .. i_last: the levels this call computes (the skewed and cross orders issue 1-3 and 4-5 on different streams; the octave-0
 // profile site then begins in front of level 1 on the one and ends behind level 5 on the other)
 static int octave_pyramid(nm_sift_arena *const *as, int n, int o, int ow, int oh, bool store_top, bool decimate,
                           hipStream_t st, bool write_dog = true, bool per_octave = false, bool write_grad = true,
@@ -494,7 +517,7 @@ int nm_sift_detect_describe_batch(nm_sift_arena *const *as, int n, const float *
     }
     hipStream_t side = as[0]->side;          // every detection / description launch covers all frames of the call
     hipStream_t dstr = as[0]->desc;
-    bool forked = false, forked_desc = false;
+    bool forked = false, forked_desc = false, forked_top = false;
     const bool dogs = frame_driver_writes_dog();
     // NM_FRAME_SPLIT_DESCRIBE=2 (experiment, off by default): octaves 0 and 1 hold ~98 % of a frame's keypoints; their
     // orientation + descriptor pass then starts as soon as octave 1 has been detected, on a stream of its own, beside the
@@ -517,7 +540,8 @@ int nm_sift_detect_describe_batch(nm_sift_arena *const *as, int n, const float *
     for (int f = 0; f < n; ++f)
         use_tail = use_tail && as[f]->tail_ok && as[f]->tail.T == as[0]->tail.T && as[f]->tail.n_oct == as[0]->tail.n_oct;
     const int first_tail = use_tail ? as[0]->tail.T : P._num_octaves;
-    // the skewed issue order (see g_frame_skew) is for the per-octave path with one description pass
+    // the skewed and cross issue orders (see g_frame_skew) are for the per-octave path with one description pass (the
+    // description stream is then free to carry the cross order's levels 4-5)
     const int skew_cfg = g_frame_skew.load(std::memory_order_relaxed);
     const int skew = (use_tail || split) ? 0 : (skew_cfg < 0 ? frame_skew_default() : skew_cfg);
     // With the tail, the octaves < T (98 % of a frame's keypoints) are described on the description stream as soon as octave
@@ -558,9 +582,21 @@ int nm_sift_detect_describe_batch(nm_sift_arena *const *as, int n, const float *
                 e = nm_launch_tail(tail_args, st);
                 if (e) return e;
             }
-            NM_RETURN_IF(hipStreamWaitEvent(side, as[0]->ev_pyr[o], 0));
+            if (skew == 2) {
+                // cross order: levels 4-5 on the third stream behind level 3 (same planes as in the skewed order below: the
+                // caller's stream goes on with octave o + 1, the side stream is still detecting octave o - 1, neither touches
+                // them); the side stream then waits for ev_top[o], which stands behind ev_pyr[o] as well
+                NM_RETURN_IF(hipStreamWaitEvent(dstr, as[0]->ev_pyr[o], 0));
+                forked_top = true;
+                e = octave_pyramid(as, n, o, ow, oh, !dogs, false, dstr, dogs, true, true, 4, 5);
+                if (e) return e;
+                NM_RETURN_IF(hipEventRecord(as[0]->ev_top[o], dstr));
+                NM_RETURN_IF(hipStreamWaitEvent(side, as[0]->ev_top[o], 0));
+            } else {
+                NM_RETURN_IF(hipStreamWaitEvent(side, as[0]->ev_pyr[o], 0));
+            }
             forked = true;
-            if (skew) {
+            if (skew == 1) {
                 // levels 4-5 in front of the octave's detection: they write planes of octave o alone (levels 4-5, gradient
                 // plane 2) and read levels 3-4, which the caller's stream no longer touches -- no buffer is shared with the
                 // launches of the octaves > o that now run beside them
@@ -629,8 +665,9 @@ int nm_sift_detect_describe_batch(nm_sift_arena *const *as, int n, const float *
         return nm_launch_frame_describe(da, side);
     };
     rc = body();
-    if (forked_desc) {
-        // the description stream joins the CALLER's stream directly (also on an error path, like the side stream below).
+    if (forked_desc || forked_top) {
+        // the description stream (split description, or the cross order's levels 4-5) joins the CALLER's stream directly (also
+        // on an error path, like the side stream below).
         // Joining it into the side stream it was forked from -- an equivalent DAG -- makes this ROCm's stream capture
         // segfault (tools/capture_shapes.py: fork s2 -> s3, join s3 -> s2 -> s1 crashes, s3 -> s1 and s2 -> s1 works).
         const hipError_t e1 = hipEventRecord(as[0]->ev_desc, dstr);
