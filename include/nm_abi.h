@@ -738,6 +738,15 @@ NM_API int nm_sift_arena_launches_per_call(const nm_sift_arena *arena, int n);
  * frame, LDS bytes of the tail launch, of the scan launch, number of tail octaves. Returns the number of segments; 0 when the
  * geometry is not covered (too few octaves, radii other than the SIFT defaults, LDS) and takes the per-octave launches. */
 NM_API int nm_sift_tail_plan(int width, int height, int T, int *segments, int max_segments, int info[4]);
+/* HOST function (no device access): the schedule of one nm_sift_detect_describe[_batch] call as the frame driver walks it, for a
+ * RESOLVED configuration: num_octaves (1..20); first_tail = first octave of the octave tail, num_octaves without it; split =
+ * octaves described early (0: one description pass; with the tail split = first_tail); write_dog (NM_FRAME_DOG; never with the
+ * tail); order 0..2 (nm_sift_set_frame_skew; 0 with the tail or a split). ops: six ints per op in issue order -- kind (0 base
+ * blur, 1 levels lo..hi, 2 detect + scan + gather, 3 tail, 4 tail scan, 5 describe octaves [lo, hi), 6 record, 7 wait, 8 join:
+ * record on the helper stream, the caller's stream waits), stream (0 caller's, 1 side, 2 description), octave, lo, hi, event
+ * (-1 none, 0 ev_pyr[octave], 1 ev_top[octave], 2 ev_det, 3 ev_desc, 4 ev_join). At most max_ops ops are written. Returns the
+ * number of ops (<= 149), 0 for a configuration the driver never resolves to. Properties: tests/test_frame_plan.py. */
+NM_API int nm_sift_frame_plan(int num_octaves, int first_tail, int split, int write_dog, int order, int *ops, int max_ops);
 /* gray: width*height fp32 on the device. Outputs on the device: desc capacity x 128, x,y capacity (full-resolution
  * coordinates, descriptor.cu:75-77), d_num_items = number of descriptors written (<= capacity,
  * siftfunctions.cu:165-169). kpts (capacity float4) and orients (capacity float2) are optional (NULL).        */
