@@ -348,9 +348,14 @@ NM_API int nm_sift_match_batch_dev_phases_f32(int phases, int n, const float *co
  * tiles, partial-list slot, 1 if the segment completes its query block); returns the number of segments. For tests and
  * capacity planning. Sets of 2^22 (4 194 304) rows or more are outside the matcher's domain (32-bit byte offsets and unit
  * indices): nm_sift_match_plan returns an error status, nm_sift_match_plan_segments -1, and every matching entry point
- * returns an error status before any plan is made. */
+ * returns an error status before any plan is made.
+ * The _on forms take the geometry instead of the device's: n_wg persistent workgroups in n_xcd XCDs (both >= 1, else the same
+ * errors). (n_wg, n_xcd) = (CUs / XCDs, 1) is the one-group plan a pair runs under when it has an XCD to itself
+ * (nm_sift_match_pairs_per_launch): X = 1 and G <= n_wg. The plain forms are the _on forms on the device's CUs and XCDs. */
 NM_API int nm_sift_match_plan(int nA, int nB, int plan[10]);
 NM_API int nm_sift_match_plan_segments(int nA, int nB, int wg, int *segments, int max_segments);
+NM_API int nm_sift_match_plan_on(int nA, int nB, int n_wg, int n_xcd, int plan[10]);
+NM_API int nm_sift_match_plan_segments_on(int nA, int nB, int n_wg, int n_xcd, int wg, int *segments, int max_segments);
 NM_API int nm_sift_match_f32(const float *A, int nA, const float *B, int nB, float *distance, int *result,
                              float ambiguity, void *workspace, void *stream);
 /* Diagnostics: number of query rows of the LAST nm_sift_match_f32 / _shard_f32 call on `workspace` (same nA, nB) that took

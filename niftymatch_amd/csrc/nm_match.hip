@@ -286,21 +286,26 @@ int nm_sift_match_batch_dev_phases_f32(int phases, int n, const float *const *A,
     return run_fused_batch(jobs, n, ambiguity, nm_stream(stream), phases);
 }
 
-int nm_sift_match_plan(int nA, int nB, int plan[10])
+// HOST functions for tests: the plan for (nA, nB) on n_wg persistent workgroups in n_xcd XCDs, made as run_fused_batch makes it
+// (one caller, no reduction). (n_wg, n_xcd) = (nm_cu_count() / nm_xcd_count(), 1) is the one-group plan of a pair that has an XCD
+// to itself (pairs_share_xcds).
+int nm_sift_match_plan_on(int nA, int nB, int n_wg, int n_xcd, int plan[10])
 {
-    if (!plan || nA < 0 || nB < 0 || nA >= MATCH_MAX_ROWS || nB >= MATCH_MAX_ROWS) return (int)hipErrorInvalidValue;
-    const MatchPlan p = make_plan(nA, nB);
+    if (!plan || nA < 0 || nB < 0 || nA >= MATCH_MAX_ROWS || nB >= MATCH_MAX_ROWS || n_wg < 1 || n_xcd < 1) return (int)hipErrorInvalidValue;
+    const MatchPlan p = make_plan_on(nA, nB, n_wg, n_xcd, 0, 1, [](int v) { return v; });
     plan[0] = p.qblocks; plan[1] = p.T; plan[2] = p.G; plan[3] = p.S; plan[4] = p.X; plan[5] = p.Gx;
     plan[6] = p.Tc; plan[7] = p.C; plan[8] = p.q_base; plan[9] = p.q_rem;
     return 0;
 }
 
-// HOST function for tests: the segments workgroup `wg` processes, in order, as rows (query block, first tile, tiles, slot,
-// ends_block); returns their number (at most max_segments are written).
-int nm_sift_match_plan_segments(int nA, int nB, int wg, int *segments, int max_segments)
+int nm_sift_match_plan(int nA, int nB, int plan[10]) { return nm_sift_match_plan_on(nA, nB, nm_cu_count(), nm_xcd_count(), plan); }
+
+// The segments workgroup `wg` of that plan processes, in order, as rows (query block, first tile, tiles, slot, ends_block);
+// returns their number (at most max_segments are written).
+int nm_sift_match_plan_segments_on(int nA, int nB, int n_wg, int n_xcd, int wg, int *segments, int max_segments)
 {
-    if (nA < 0 || nB < 0 || wg < 0 || nA >= MATCH_MAX_ROWS || nB >= MATCH_MAX_ROWS) return -1;
-    const MatchPlan p = make_plan(nA, nB);
+    if (nA < 0 || nB < 0 || wg < 0 || nA >= MATCH_MAX_ROWS || nB >= MATCH_MAX_ROWS || n_wg < 1 || n_xcd < 1) return -1;
+    const MatchPlan p = make_plan_on(nA, nB, n_wg, n_xcd, 0, 1, [](int v) { return v; });
     if (wg >= p.G) return 0;
     const int xg = wg % p.X, vg = wg / p.X;
     const PlanGroup grp = plan_group(p, xg);
@@ -321,6 +326,11 @@ int nm_sift_match_plan_segments(int nA, int nB, int wg, int *segments, int max_s
         ++n;
     }
     return n;
+}
+
+int nm_sift_match_plan_segments(int nA, int nB, int wg, int *segments, int max_segments)
+{
+    return nm_sift_match_plan_segments_on(nA, nB, nm_cu_count(), nm_xcd_count(), wg, segments, max_segments);
 }
 
 int nm_sift_match_fallback_count(const void *workspace, int nA, int nB, int *host_count, void *stream)
