@@ -128,6 +128,22 @@ NM_API int nm_create_kernel_for_sigma(float sigma, float *taps);
  * `buffer` receives the row pass, `result` the column pass of `buffer`. `kernel` = 2r+1 taps in DEVICE memory.   */
 NM_API int nm_convolve_f32(float *result, const float *image, float *buffer, int width, int height,
                            const float *kernel, int kernel_radius, void *stream);
+/* HOST function (no device access): which kernel a Gaussian launch of ONE frame gets -- the decision nm_convolve_f32 and the frame
+ * driver's batched launches act on (niftymatch_amd/csrc/nm_conv_route.hpp). has_*: whether the pointer is given (the frame driver
+ * passes no buffer; nm_convolve_f32 passes result and buffer, no dog, no grad); image_low4 / out_low4: the low four address bits
+ * of the image / of result | buffer. In this precedence: an empty image is NONE whatever the radius; radius < 0 is INVALID; a
+ * radius outside {5, 7, 8, 10, 12, 13, 16} is GENERIC with a buffer and INVALID without; a buffer with dog or grad is INVALID;
+ * width % 4 == 0, a 16-byte aligned image and a plane below 4 GiB give PACKED without a buffer and PACKED_BUF with a result and
+ * 16-byte aligned result and buffer; everything else is TILE (scalar staging, size_t indices). A batch is ONE launch when every
+ * frame is PACKED with the same set of outputs, else frame by frame. Pinned by tests/test_conv_route.py. */
+#define NM_CONV_ROUTE_NONE 0       /* empty image: no launch */
+#define NM_CONV_ROUTE_PACKED 1     /* conv_pk_kernel */
+#define NM_CONV_ROUTE_PACKED_BUF 2 /* conv_pk_kernel<..., WRITE_BUF> */
+#define NM_CONV_ROUTE_TILE 3       /* conv_sep_kernel, the LDS tile fallback */
+#define NM_CONV_ROUTE_GENERIC 4    /* the two-pass any-radius kernels */
+#define NM_CONV_ROUTE_INVALID 5    /* the call is rejected */
+NM_API int nm_conv_route_of(int width, int height, int radius, int has_result, int has_buffer, int has_dog, int has_grad,
+                            unsigned image_low4, unsigned out_low4);
 /* downsample_by_2<float> (kernels/downsample.h:21-24, downsample.cu:20-29). */
 NM_API int nm_downsample2_f32(float *result, int result_width, int result_height, const float *source,
                               int source_width, int source_height, void *stream);

@@ -31,6 +31,7 @@ _SIGNATURES = {
     "nm_profile_events": (_I, [_I, _P, _P]),
     "nm_create_kernel_for_sigma": (_I, [_F, _P]),
     "nm_convolve_f32": (_I, [_P, _P, _P, _I, _I, _P, _I, _P]),
+    "nm_conv_route_of": (_I, [_I, _I, _I, _I, _I, _I, _I, C.c_uint, C.c_uint]),
     "nm_downsample2_f32": (_I, [_P, _I, _I, _P, _I, _I, _P]),
     "nm_subtract_f32": (_I, [_P, _P, _P, _I, _I, _P]),
     "nm_gradient_f32": (_I, [_P, _P, _I, _I, _P]),

@@ -65,14 +65,16 @@ struct NmGradBatch {            // up to 3 planes per launch (gradient levels 0.
     int n;
 };
 int nm_launch_gradient_batch(const NmGradBatch &b, int width, int height, hipStream_t stream);
-// Gaussian level + fused DoG (dog = result - image) + fused gradient of `image` (float2 plane); buffer, dog and grad
-// may be NULL. buffer (the materialised row pass of the API path) excludes dog/grad.
+// Gaussian level + fused DoG (dog = result - image) + fused gradient of `image` (float2 plane) of ONE frame, by the kernel
+// nm_conv_route (nm_conv_route.hpp) answers for it; buffer, dog and grad may be NULL. buffer (the materialised row pass of
+// the API path) excludes dog/grad.
 int nm_launch_convolve(float *result, const float *image, float *buffer, float *dog, float *grad, int width,
                        int height, const float *taps_dev, int radius, hipStream_t stream);
 
 // The same Gaussian launch over up to NM_MAX_BATCH equally sized frames (one grid; the frame index is the slow part of
 // blockIdx.x): 1080p octave 0 is only ~4 workgroups per CU, a frame pair or quad fills the chip and amortises the
 // launch / drain phases that bound a single frame.
+// One launch when every frame routes to the packed kernel with the same set of outputs, else frame by frame.
 #define NM_MAX_BATCH 64
 struct NmConvBatch {
     float *result[NM_MAX_BATCH];

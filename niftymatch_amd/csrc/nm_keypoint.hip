@@ -336,8 +336,10 @@ static void launch_detect_rows(NmDetectArgs &d, bool bands, hipStream_t stream)
     const dim3 grid(d.xcd_band ? 8 * d.xcd_band : groups, d.n);
     if (d.from_levels && d.any_mask) hipLaunchKernelGGL((detect_stage_kernel<false, true, true, ROWS>), grid, dim3(256), 0, stream, d);
     else if (d.from_levels) hipLaunchKernelGGL((detect_stage_kernel<false, true, false, ROWS>), grid, dim3(256), 0, stream, d);
-    else if (d.any_mask) hipLaunchKernelGGL((detect_stage_kernel<false, false, true, ROWS>), grid, dim3(256), 0, stream, d);
-    else hipLaunchKernelGGL((detect_stage_kernel<false, false, false, ROWS>), grid, dim3(256), 0, stream, d);
+    else if constexpr (ROWS == DET_ROWS) {            // the tall heights are taken from levels only (nm_launch_detect_octave)
+        if (d.any_mask) hipLaunchKernelGGL((detect_stage_kernel<false, false, true, ROWS>), grid, dim3(256), 0, stream, d);
+        else hipLaunchKernelGGL((detect_stage_kernel<false, false, false, ROWS>), grid, dim3(256), 0, stream, d);
+    }
 }
 
 int nm_launch_detect_octave(const NmDetectArgs &d_in, const NmScanArgs &s, const NmGatherArgs &g, hipStream_t stream)

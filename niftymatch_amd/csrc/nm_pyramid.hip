@@ -5,10 +5,15 @@
 #include <cstdlib>
 
 #include "nm_common.hpp"
+#include "nm_conv_route.hpp"
 #include "nm_fpspec.hpp"
 #include "nm_grad_dev.hpp"
 #include "nm_pk_dev.hpp"
 #include "../../include/nm_abi.h"
+
+static_assert(NM_CONV_NONE == NM_CONV_ROUTE_NONE && NM_CONV_PACKED == NM_CONV_ROUTE_PACKED && NM_CONV_PACKED_BUF == NM_CONV_ROUTE_PACKED_BUF &&
+              NM_CONV_TILE == NM_CONV_ROUTE_TILE && NM_CONV_GENERIC == NM_CONV_ROUTE_GENERIC && NM_CONV_INVALID == NM_CONV_ROUTE_INVALID,
+              "nm_abi.h follows nm_conv_route.hpp");
 
 using nmfp::fma32;
 using namespace nmgrad;
@@ -37,33 +42,34 @@ int nm_xcd_count()
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// Fused separable Gaussian. A workgroup (256 threads = 4 waves) walks over 64 x TH output tiles:
-//   fetch    global -> VGPRs: the (TH+2R) x (64+2RA) input tile of the NEXT tile is requested (float4, all loads in
+// Fused separable Gaussian: the fallback of the packed kernel below for what that one cannot take (odd widths, misaligned
+// planes, planes of 4 GiB and more: nm_conv_route.hpp). A workgroup (256 threads = 4 waves) walks over 64 x 32 output tiles:
+//   fetch    global -> VGPRs: the (32+2R) x (64+2RA) input tile of the NEXT tile is requested (scalar loads, all in
 //            flight together) before the current tile is computed, so HBM latency hides behind the FMA phases
 //   phase 1  VGPRs -> LDS (zero outside the image)
 //   phase 2  row pass LDS -> LDS: every thread makes 8 consecutive outputs of one row from registers
-//   phase 3  column pass LDS -> global: every thread makes TH/4 vertical outputs of one column; a wave writes
+//   phase 3  column pass LDS -> global: every thread makes 8 vertical outputs of one column; a wave writes
 //            whole 256-B row segments. DoG = output - input centre comes from the LDS tile for free, and so does
 //            the gradient (magnitude, angle) of the INPUT level (kernels/cudamath.cu:38-54), whose 4-neighbourhood is
 //            inside the staged halo: levels 1..3 get their gradients from the launch that blurs them into level+1.
 // Tiles are dealt so that workgroups sharing an XCD (blockIdx % 8) walk one contiguous band of the image: halo rows
 // re-read by vertical neighbours hit that XCD's L2. R is a template parameter: tap loops unroll, windows live in VGPRs.
-template <int R, int TH, bool WRITE_BUF, bool WRITE_DOG, bool WRITE_GRAD, bool VEC>
-__global__ __launch_bounds__(TH * 8) void conv_sep_kernel(float *__restrict__ result, const float *__restrict__ image,
+// All plane indices are size_t: this is the kernel that serves planes of 4 GiB and more.
+template <int R, bool WRITE_BUF, bool WRITE_DOG, bool WRITE_GRAD>
+__global__ __launch_bounds__(256) void conv_sep_kernel(float *__restrict__ result, const float *__restrict__ image,
                                                       float *__restrict__ buffer, float *__restrict__ dog,
                                                       float2 *__restrict__ grad, int width, int height,
                                                       const float *__restrict__ taps, int tiles_x, int ntiles, int nxcd)
 {
-    constexpr int TW = 64;
+    constexpr int TW = 64, TH = 32;
     constexpr int RA = (R + 3) & ~3;              // halo rounded up to 4 columns: 16-byte aligned row segments
     constexpr int IN_W = TW + 2 * RA;             // columns staged in LDS (image x = x0 - RA + c)
     constexpr int IN_P = IN_W + 4;                // row pitch: multiple of 4 (b128 reads) + 4 (bank skew)
     constexpr int OFF = RA - R;                   // first column the row pass reads
     constexpr int ROWS = TH + 2 * R;
     constexpr int NT = 2 * R + 1;
-    constexpr int V_PER_ROW = IN_W / 4;
-    constexpr int NE = VEC ? ROWS * V_PER_ROW : ROWS * IN_W;     // staged elements (float4 or float)
-    constexpr int NTH = TH * 8;                   // 256 threads for 64 x 32 tiles, 512 for 64 x 64
+    constexpr int NE = ROWS * IN_W;               // staged elements
+    constexpr int NTH = 256;
     constexpr int PER = (NE + NTH - 1) / NTH;
     __shared__ __attribute__((aligned(16))) float s_in[ROWS * IN_P];
     __shared__ __attribute__((aligned(16))) float s_mid[ROWS * TW];
@@ -78,26 +84,17 @@ __global__ __launch_bounds__(TH * 8) void conv_sep_kernel(float *__restrict__ re
     const int band = (ntiles + nxcd - 1) / nxcd;
     const int t_begin = xcd * band, t_end = min(t_begin + band, ntiles);
 
-    float4 pf4[VEC ? PER : 1];
-    float pf1[VEC ? 1 : PER];
+    float pf[PER];
     auto fetch = [&](int tile) {
         const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
         const int x0 = tx * TW, y0 = ty * TH;
 #pragma unroll
         for (int i = 0; i < PER; ++i) {
             const int idx = tid + NTH * i;
-            if (VEC) {
-                const int row = idx / V_PER_ROW, c4 = idx - row * V_PER_ROW;
-                const int gy = y0 - R + row, gx = x0 - RA + 4 * c4;
-                pf4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (idx < NE && gy >= 0 && gy < height && gx >= 0 && gx < width)
-                    pf4[i] = *reinterpret_cast<const float4 *>(image + (size_t)gy * width + gx);
-            } else {
-                const int row = idx / IN_W, c = idx - row * IN_W;
-                const int gy = y0 - R + row, gx = x0 - RA + c;
-                pf1[i] = 0.f;
-                if (idx < NE && gy >= 0 && gy < height && gx >= 0 && gx < width) pf1[i] = image[(size_t)gy * width + gx];
-            }
+            const int row = idx / IN_W, c = idx - row * IN_W;
+            const int gy = y0 - R + row, gx = x0 - RA + c;
+            pf[i] = 0.f;
+            if (idx < NE && gy >= 0 && gy < height && gx >= 0 && gx < width) pf[i] = image[(size_t)gy * width + gx];
         }
     };
 
@@ -111,13 +108,8 @@ __global__ __launch_bounds__(TH * 8) void conv_sep_kernel(float *__restrict__ re
 #pragma unroll
         for (int i = 0; i < PER; ++i) {
             const int idx = tid + NTH * i;
-            if (VEC) {
-                const int row = idx / V_PER_ROW, c4 = idx - row * V_PER_ROW;
-                if (idx < NE) *reinterpret_cast<float4 *>(&s_in[row * IN_P + 4 * c4]) = pf4[i];
-            } else {
-                const int row = idx / IN_W, c = idx - row * IN_W;
-                if (idx < NE) s_in[row * IN_P + c] = pf1[i];
-            }
+            const int row = idx / IN_W, c = idx - row * IN_W;
+            if (idx < NE) s_in[row * IN_P + c] = pf[i];
         }
         __syncthreads();
         if (tile + per_xcd < t_end) fetch(tile + per_xcd);        // next tile's loads fly during phases 2 and 3
@@ -560,39 +552,7 @@ __global__ __launch_bounds__(256) void conv_pk_kernel(NmConvBatch batch, int wid
 #endif
 }
 
-// (Round 6, measured and removed -- the version is in the repository's history, commit "Experiments (measured, negative)":
-// conv_pk_ring_kernel, ONE persistent workgroup per LDS slot walking the same XCD-banded tile list with a 2-deep LDS-DMA input
-// ring: the next tile's rows requested by buffer_load_dword ... lds (inline asm, so that hipcc places no vmcnt(0) in front of
-// the ds_reads) BEFORE the current tile's epilogue stores, `s_waitcnt vmcnt(#stores)` at the top of the next iteration so the
-// rows are waited for but not the stores behind them, raw s_barrier + lgkmcnt(0). Bit-exact (44 GPU tests), and 25-40 % SLOWER:
-// 65.2 / 66.0 / 73.6 us per frame at 8 / 3 / 2 workgroups per CU against 52.3 for the launches above (64-frame chain, same box,
-// alternating). The row-pair interleaved tile forces 4-BYTE DMA -- lane l lands row (l & 1), column l >> 1: 24 wave-instructions
-// per wave and tile where the register path issues 6 16-byte loads per thread -- and two input images leave 2-4 workgroups per CU
-// where 4-6 one-tile workgroups already overlap one another's loads (the guide's regime rule: LDS-DMA spans pay at ~1 block per CU,
-// not at high occupancy). profiles/r06_e_conv_ring_experiment.txt. Also measured, no effect (+-1 %, 16- and 64-frame chains):
-// the gradient planes stored non-temporally, so that they would not displace the level the next launch reads. And the frame
-// driver's chain in GROUPS of frames (the five launches of octave 0 / 1 for 8, 16 or 32 frames back to back, so that a level is
-// still in the 256 MB Infinity Cache when the next launch reads it): 56.1 / 53.9 / 52.6 against 51.9 us per frame.)
-// (Round 6, measured and removed: the frames of every other launch walked in REVERSE order, so that a launch starts on the planes
-// the previous one wrote last (256 MB of Infinity Cache = the last ~10 frames' outputs): 51.1-51.5 against 51.4-51.7 us per frame,
-// three alternations -- nothing. profiles/r06_z_conv_pingpong.txt)
-// (Round 5, measured and removed: issue priorities (s_setprio 3 while the tile's loads are issued / 2 or 1 in the epilogue / both):
-// 54.2-54.9 us per frame against 54.4-54.5, 64-frame chain, same box -- nothing beyond the run-to-run spread.)
-// (Round 5, measured and removed: 64-ROW tiles with 512 threads -- the share of halo rows the row pass filters and the loads
-// fetch drops from 1.81 to 1.41 at R = 13 and from 1.44 to 1.22 at R = 7, the row tasks mapped densely (row pair fastest) so
-// that whole waves skip the pass; bit-identical (60 GPU tests). 64-frame chain: 57.83 -> 57.91 us per frame with the DoG
-// planes, 51.9 -> 53.3 without, 42.1 -> 42.6 without the gradients. Per launch (octave 0, 64 frames): R = 10 with gradient
-// 589 -> 546 us (3 workgroups of 8 waves fit a CU where 5 of 4 did), R = 13 438 -> 467, R = 5 222 -> 240, the others +-1 %:
-// the launches follow the waves in flight and the workgroup granularity, not the FMA or load count -- like round 4's 48-row
-// tiles. profiles/r05_x_kpyr_tall.txt, r05_y_kpyr_tall{0,1}.txt)
-// (Round 3, measured and removed: a STREAMING form of this kernel -- a workgroup owns a 64-column strip segment and marches
-// down it in 32-row bands, fetching and row-filtering only the 32 new input rows per band, moving the last 2R rows of both LDS
-// tiles to their head, with the next band's rows prefetched into registers -- is bit-identical and does 38 % less staging
-// and row-pass work, but ran the 16-frame chain in 78-83 us per frame instead of 66-68 (segments of 4 / 6 / 9 / 17 bands:
-// 84.5 / 85 / 90 / 97). With its stores off 51, with the prefetch loads off 63, with both off 38 us: inside one workgroup the
-// phases of a band are strictly sequential, and on gfx950 stores count in vmcnt, so waiting for the prefetched rows also
-// waits for the previous band's stores. Many short workgroups overlap each other's memory phases better than few long
-// ones overlap their own. profiles/r03_c_conv_strip_experiment.txt)
+// (Measured and removed -- LDS-DMA ring, reversed frames, issue priorities, 64-row tiles, strips: docs/KERNEL_NOTES_conv_removed.md)
 
 // Exhaustive self-test of sqrt_rn's fast path against the IEEE expansion (tests/test_gpu_stages.py).
 __global__ __launch_bounds__(256) void selftest_sqrt_kernel(unsigned long long *mismatches)
@@ -657,157 +617,92 @@ __global__ __launch_bounds__(256) void conv_cols_generic(float *__restrict__ out
     if (dog) dog[(size_t)y * width + x] = sum - orig[(size_t)y * width + x];
 }
 
-template <int R, bool VEC, int TH>
-static int launch_conv_rvt(float *result, const float *image, float *buffer, float *dog, float *grad, int width,
-                           int height, const float *taps, hipStream_t stream)
+// One fixed-radius launch: the route's kernel with the outputs the batch asks for. NM_CONV_PACKED covers all b.n frames;
+// the other two routes are one frame, whose `buffer` travels in the down slot.
+template <int R>
+static int launch_conv_r(NmConvRoute route, const NmConvBatch &b, int width, int height, const float *taps, hipStream_t stream)
 {
-    const int tiles_x = nm_divup(width, 64), tiles_y = nm_divup(height, TH);
-    const int ntiles = tiles_x * tiles_y;
-    // one tile per workgroup up to the chip's residency; grid is a multiple of 8 (XCDs). (Measured on MI355X: more
-    // tiles per workgroup with register prefetch is slower than more resident workgroups.)
-    const int nxcd = nm_xcd_count();
-    const int blocks = nm_divup(ntiles, nxcd) * nxcd;
-    dim3 grid(blocks);
-    float2 *g2 = reinterpret_cast<float2 *>(grad);
-#define NM_CONV_LAUNCH(BUF, DOG, GRAD)                                                                              \
-    hipLaunchKernelGGL((conv_sep_kernel<R, TH, BUF, DOG, GRAD, VEC>), grid, dim3(TH * 8), 0, stream, result, image, \
-                       buffer, dog, g2, width, height, taps, tiles_x, ntiles, nxcd)
-    if (buffer) {
-        if (dog || grad || TH != 32) return (int)hipErrorInvalidValue;   // the API path never asks for the fused outputs
-        if (TH == 32) NM_CONV_LAUNCH(true, false, false);
-    } else if (dog && grad) {
-        NM_CONV_LAUNCH(false, true, true);
-    } else if (dog) {
-        NM_CONV_LAUNCH(false, true, false);
-    } else if (grad) {
-        NM_CONV_LAUNCH(false, false, true);
-    } else {
-        NM_CONV_LAUNCH(false, false, false);
-    }
+    const NmConvGrid g = nm_conv_grid(width, height, nm_xcd_count());
+    const bool tile = route == NM_CONV_TILE, buf = route == NM_CONV_PACKED_BUF || (tile && b.down[0]);
+    const bool dog = b.dog[0] != nullptr, grad = b.grad[0] != nullptr;
+    const dim3 grid(g.blocks_per_frame * b.n);
+#define NM_CONV_LAUNCH(DOG, GRAD, BUF)                                                                                  \
+    do {                                                                                                                \
+        if (tile)                                                                                                       \
+            hipLaunchKernelGGL((conv_sep_kernel<R, BUF, DOG, GRAD>), grid, dim3(256), 0, stream, b.result[0], b.image[0], \
+                               b.down[0], b.dog[0], reinterpret_cast<float2 *>(b.grad[0]), width, height, taps,        \
+                               g.tiles_x, g.ntiles, g.nxcd);                                                            \
+        else                                                                                                            \
+            hipLaunchKernelGGL((conv_pk_kernel<R, DOG, GRAD, BUF>), grid, dim3(256), 0, stream, b, width, height, taps, \
+                               g.tiles_x, g.ntiles, g.blocks_per_frame, g.nxcd);                                        \
+    } while (0)
+    if (buf) NM_CONV_LAUNCH(false, false, true);          // the route has excluded dog and grad
+    else if (dog && grad) NM_CONV_LAUNCH(true, true, false);
+    else if (dog) NM_CONV_LAUNCH(true, false, false);
+    else if (grad) NM_CONV_LAUNCH(false, true, false);    // frame driver: the DoG planes are not materialised (detection subtracts the levels)
+    else NM_CONV_LAUNCH(false, false, false);
 #undef NM_CONV_LAUNCH
     NM_LAUNCH_CHECK();
     return 0;
 }
 
-template <int R>
-static int launch_conv_pk(const NmConvBatch &b, int width, int height, const float *taps, hipStream_t stream)
-{
-    const int tiles_x = nm_divup(width, 64), tiles_y = nm_divup(height, 32);
-    const int ntiles = tiles_x * tiles_y;
-    const int nxcd = nm_xcd_count();
-    const bool dog = b.dog[0] != nullptr, grad = b.grad[0] != nullptr;
-    const int bpf = nm_divup(ntiles, nxcd) * nxcd;
-    dim3 grid(bpf * b.n);
-#define NM_PK_LAUNCH(DOG, GRAD)                                                                                     \
-    hipLaunchKernelGGL((conv_pk_kernel<R, DOG, GRAD>), grid, dim3(256), 0, stream, b, width, height, taps, tiles_x, \
-                       ntiles, bpf, nxcd)
-    if (dog && grad) NM_PK_LAUNCH(true, true);
-    else if (dog) NM_PK_LAUNCH(true, false);
-    else if (grad) NM_PK_LAUNCH(false, true);       // frame driver: the DoG planes are not materialised (detection subtracts the levels)
-    else NM_PK_LAUNCH(false, false);
-#undef NM_PK_LAUNCH
-    NM_LAUNCH_CHECK();
-    return 0;
-}
-
-template <int R>
-static int launch_conv_pk_buf(float *result, const float *image, float *buffer, int width, int height, const float *taps,
+static int launch_conv_radius(NmConvRoute route, const NmConvBatch &b, int width, int height, const float *taps, int radius,
                               hipStream_t stream)
 {
-    NmConvBatch b{};
-    b.result[0] = result; b.image[0] = image; b.down[0] = buffer; b.n = 1;
-    const int tiles_x = nm_divup(width, 64), tiles_y = nm_divup(height, 32);
-    const int ntiles = tiles_x * tiles_y;
-    const int nxcd = nm_xcd_count();
-    const int bpf = nm_divup(ntiles, nxcd) * nxcd;
-    hipLaunchKernelGGL((conv_pk_kernel<R, false, false, true>), dim3(bpf), dim3(256), 0, stream, b, width, height, taps,
-                       tiles_x, ntiles, bpf, nxcd);
-    NM_LAUNCH_CHECK();
-    return 0;
-}
-
-template <int R, bool VEC>
-static int launch_conv_rv(float *result, const float *image, float *buffer, float *dog, float *grad, int width,
-                          int height, const float *taps, hipStream_t stream)
-{
-    if (VEC && buffer && !dog && !grad && result && (size_t)width * height * 4 < (1ull << 32) &&
-        ((reinterpret_cast<uintptr_t>(buffer) | reinterpret_cast<uintptr_t>(result)) & 15) == 0)
-        return launch_conv_pk_buf<R>(result, image, buffer, width, height, taps, stream);
-    if (VEC && !buffer && (size_t)width * height * 4 < (1ull << 32)) {
-        NmConvBatch b{};
-        b.result[0] = result; b.image[0] = image; b.dog[0] = dog; b.grad[0] = grad; b.n = 1;
-        return launch_conv_pk<R>(b, width, height, taps, stream);
+    switch (radius) {
+#define NM_CONV_CASE(R) case R: return launch_conv_r<R>(route, b, width, height, taps, stream);
+        NM_CONV_RADII(NM_CONV_CASE)
+#undef NM_CONV_CASE
+        default: return (int)hipErrorInvalidValue;
     }
-    // 64 x 32 tiles with 256 threads, or 64 x 64 tiles with 512 threads (less halo re-reading and row-pass redundancy)
-    // once the image has enough tiles to fill the chip that way.
-    if (VEC && !buffer && (long)width * height >= 256L * 64 * 64)
-        return launch_conv_rvt<R, VEC, VEC ? 64 : 32>(result, image, buffer, dog, grad, width, height, taps, stream);
-    return launch_conv_rvt<R, VEC, 32>(result, image, buffer, dog, grad, width, height, taps, stream);
 }
 
-template <int R>
-static int launch_conv_r(float *result, const float *image, float *buffer, float *dog, float *grad, int width,
-                         int height, const float *taps, hipStream_t stream)
+static NmConvRoute route_of(const float *result, const float *image, const float *buffer, const float *dog, const float *grad,
+                            int width, int height, int radius)
 {
-    const bool vec = (width % 4 == 0) && ((reinterpret_cast<uintptr_t>(image) & 15) == 0);
-    return vec ? launch_conv_rv<R, true>(result, image, buffer, dog, grad, width, height, taps, stream)
-               : launch_conv_rv<R, false>(result, image, buffer, dog, grad, width, height, taps, stream);
+    return nm_conv_route(width, height, radius, result != nullptr, buffer != nullptr, dog != nullptr, grad != nullptr,
+                         (unsigned)(reinterpret_cast<uintptr_t>(image) & 15),
+                         (unsigned)((reinterpret_cast<uintptr_t>(result) | reinterpret_cast<uintptr_t>(buffer)) & 15));
 }
 
+// One frame by its route.
 int nm_launch_convolve(float *result, const float *image, float *buffer, float *dog, float *grad, int width,
                        int height, const float *taps, int radius, hipStream_t stream)
 {
-    if (width <= 0 || height <= 0) return 0;
-    if (radius < 0) return (int)hipErrorInvalidValue;
-    switch (radius) {
-        case 5: return launch_conv_r<5>(result, image, buffer, dog, grad, width, height, taps, stream);
-        case 7: return launch_conv_r<7>(result, image, buffer, dog, grad, width, height, taps, stream);
-        case 8: return launch_conv_r<8>(result, image, buffer, dog, grad, width, height, taps, stream);
-        case 10: return launch_conv_r<10>(result, image, buffer, dog, grad, width, height, taps, stream);
-        case 12: return launch_conv_r<12>(result, image, buffer, dog, grad, width, height, taps, stream);
-        case 13: return launch_conv_r<13>(result, image, buffer, dog, grad, width, height, taps, stream);
-        case 16: return launch_conv_r<16>(result, image, buffer, dog, grad, width, height, taps, stream);
-        default: break;
+    const NmConvRoute route = route_of(result, image, buffer, dog, grad, width, height, radius);
+    if (route == NM_CONV_NONE) return 0;
+    if (route == NM_CONV_INVALID) return (int)hipErrorInvalidValue;
+    if (route != NM_CONV_GENERIC) {
+        NmConvBatch b{};
+        b.result[0] = result; b.image[0] = image; b.dog[0] = dog; b.grad[0] = grad; b.down[0] = buffer; b.n = 1;
+        return launch_conv_radius(route, b, width, height, taps, radius, stream);
     }
-    // generic radius: the row pass needs a real intermediate. Without a caller buffer there is none to use.
-    if (!buffer) return (int)hipErrorInvalidValue;
     dim3 grid(nm_divup(width, 64), nm_divup(height, 4));
     hipLaunchKernelGGL(conv_rows_generic, grid, dim3(256), 0, stream, buffer, image, width, height, taps, radius);
     NM_LAUNCH_CHECK();
     hipLaunchKernelGGL(conv_cols_generic, grid, dim3(256), 0, stream, result, buffer, dog, image, width, height, taps, radius);
     NM_LAUNCH_CHECK();
     if (grad) {
-        NmGradBatch b{};
-        b.src[0] = image; b.dst[0] = grad; b.n = 1;
-        return nm_launch_gradient_batch(b, width, height, stream);
+        NmGradBatch gb{};
+        gb.src[0] = image; gb.dst[0] = grad; gb.n = 1;
+        return nm_launch_gradient_batch(gb, width, height, stream);
     }
     return 0;
 }
 
-// Batched form used by the frame driver: one launch for all frames when the packed kernel applies (same geometry, all
-// planes 16-byte aligned, same set of outputs), otherwise frame by frame.
+// Batched form used by the frame driver: one launch for all frames when every frame routes to the packed kernel with the
+// same set of outputs, otherwise frame by frame, each frame by its own route.
 int nm_launch_convolve_batch(const NmConvBatch &b, int width, int height, const float *taps, int radius, hipStream_t stream)
 {
     if (b.n <= 0 || width <= 0 || height <= 0) return 0;
     if (b.n > NM_MAX_BATCH) return (int)hipErrorInvalidValue;
-    bool pk = (width % 4 == 0) && (size_t)width * height * 4 < (1ull << 32);
+    bool one = true;
     for (int f = 0; f < b.n; ++f) {
-        pk = pk && ((reinterpret_cast<uintptr_t>(b.image[f]) & 15) == 0);
-        pk = pk && ((b.result[f] != nullptr) == (b.result[0] != nullptr)) && ((b.dog[f] != nullptr) == (b.dog[0] != nullptr)) &&
-             ((b.grad[f] != nullptr) == (b.grad[0] != nullptr)) && ((b.down[f] != nullptr) == (b.down[0] != nullptr));
+        one = one && route_of(b.result[f], b.image[f], nullptr, b.dog[f], b.grad[f], width, height, radius) == NM_CONV_PACKED;
+        one = one && ((b.result[f] != nullptr) == (b.result[0] != nullptr)) && ((b.dog[f] != nullptr) == (b.dog[0] != nullptr)) &&
+              ((b.grad[f] != nullptr) == (b.grad[0] != nullptr)) && ((b.down[f] != nullptr) == (b.down[0] != nullptr));
     }
-    if (pk) {
-        switch (radius) {
-            case 5: return launch_conv_pk<5>(b, width, height, taps, stream);
-            case 7: return launch_conv_pk<7>(b, width, height, taps, stream);
-            case 8: return launch_conv_pk<8>(b, width, height, taps, stream);
-            case 10: return launch_conv_pk<10>(b, width, height, taps, stream);
-            case 12: return launch_conv_pk<12>(b, width, height, taps, stream);
-            case 13: return launch_conv_pk<13>(b, width, height, taps, stream);
-            case 16: return launch_conv_pk<16>(b, width, height, taps, stream);
-            default: break;
-        }
-    }
+    if (one) return launch_conv_radius(NM_CONV_PACKED, b, width, height, taps, radius, stream);
     for (int f = 0; f < b.n; ++f) {
         const int rc = nm_launch_convolve(b.result[f], b.image[f], nullptr, b.dog[f], b.grad[f], width, height, taps, radius, stream);
         if (rc) return rc;
@@ -911,6 +806,12 @@ int nm_selftest_sqrt(unsigned long long *d_mismatches, void *stream)
     hipLaunchKernelGGL(selftest_sqrt_kernel, dim3(4096), dim3(256), 0, nm_stream(stream), d_mismatches);
     NM_LAUNCH_CHECK();
     return 0;
+}
+
+int nm_conv_route_of(int width, int height, int radius, int has_result, int has_buffer, int has_dog, int has_grad,
+                     unsigned image_low4, unsigned out_low4)
+{
+    return nm_conv_route(width, height, radius, has_result != 0, has_buffer != 0, has_dog != 0, has_grad != 0, image_low4, out_low4);
 }
 
 int nm_convolve_f32(float *result, const float *image, float *buffer, int width, int height, const float *kernel,

@@ -99,8 +99,13 @@ def _extreme_level0(w, h):
 
 @pytest.mark.parametrize("kind", ["blurred", "extreme"])
 def test_octave_pyramid_fused(nm, oracle, cuda, kind):
+    # 320 x 200 runs the packed kernel; 201 x 83 (odd width) the tile kernel with its DoG and gradient outputs, on the same inputs
+    for w, h in ((320, 200), (201, 83)):
+        _check_octave_pyramid_fused(nm, oracle, cuda, kind, w, h)
+
+
+def _check_octave_pyramid_fused(nm, oracle, cuda, kind, w, h):
     import torch
-    w, h = 320, 200
     if kind == "blurred":
         levels, dogs, grad = _octave(oracle, w, h, 3)
     else:
@@ -127,10 +132,10 @@ def test_octave_pyramid_fused(nm, oracle, cuda, kind):
     arena.octave_pyramid(w, h)
     torch.cuda.synchronize()
     for l in range(1, 6):
-        _eq(view(arena.level_ptr(l), n).reshape(h, w), levels[l], "level %d" % l)
+        _eq(view(arena.level_ptr(l), n).reshape(h, w), levels[l], "%d x %d level %d" % (w, h, l))
     for d in range(5):
-        _eq(view(arena.dog_ptr(d), n).reshape(h, w), dogs[d], "dog %d" % d)
-    _eq(view(arena.grad_ptr(), 6 * n).reshape(3, h, w, 2), grad, "grad")
+        _eq(view(arena.dog_ptr(d), n).reshape(h, w), dogs[d], "%d x %d dog %d" % (w, h, d))
+    _eq(view(arena.grad_ptr(), 6 * n).reshape(3, h, w, 2), grad, "%d x %d grad" % (w, h))
     arena.close()
 
 

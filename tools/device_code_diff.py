@@ -1,12 +1,15 @@
-"""Proof that a refactor left the device code alone: compile the device side of every kernel source of two revisions and
+r"""Proof that a refactor left the device code alone: compile the device side of every kernel source of two revisions and
 compare them kernel by kernel.
-    python tools/device_code_diff.py <rev_a> <rev_b> [--only REGEX]
+    python tools/device_code_diff.py <rev_a> <rev_b> [--only REGEX] [--rename PATTERN=REPLACEMENT ...]
 A revision is anything `git archive` takes, or WORKTREE for the files as they are. Sources are niftymatch_amd/csrc/*.hip
 (--only: those whose name matches), compiled with the build's FLAGS plus --cuda-device-only -S. Kernels are paired by base
 name and template arguments, whatever file or namespace holds them. For every kernel of <rev_a> there must be exactly one in
 <rev_b>, with the same
   * instruction stream (labels renumbered in order of appearance, comments dropped, mangled symbol names ignored);
   * kernel descriptor (.amdhsa_* fields) and metadata (register counts, LDS and scratch sizes, both spill counts).
+--rename PATTERN=REPLACEMENT (may be repeated) is re.sub(PATTERN, REPLACEMENT, key) on the kernel keys of <rev_b>, nothing else: a
+kernel whose template list was shortened can still be paired with its parent, e.g. with <rev_b> the parent
+  --rename 'conv_sep_kernel<(\d+), 32, (\w+, \w+, \w+), false>=conv_sep_kernel<\1, \2>'
 Prints one verdict per kernel; exit status 1 unless every kernel of <rev_a> is IDENTICAL."""
 import argparse, difflib, os, re, shutil, subprocess, sys, tempfile
 from concurrent.futures import ThreadPoolExecutor
@@ -84,7 +87,7 @@ def kernels_of(asm):
     return res
 
 
-def collect(rev, only):
+def collect(rev, only, renames=()):
     tmp = tempfile.mkdtemp(prefix="devdiff_")
     try:
         csrc = checkout(rev, tmp)
@@ -98,7 +101,9 @@ def collect(rev, only):
         ks = kernels_of(asm)
         names = demangle(list(ks)) if ks else {}
         for mangled, parts in ks.items():
-            found.setdefault(kernel_key(names[mangled]), []).append((os.path.basename(src), parts))
+            key = kernel_key(names[mangled])
+            for pattern, replacement in renames: key = re.sub(pattern, replacement, key)
+            found.setdefault(key, []).append((os.path.basename(src), parts))
     return found
 
 
@@ -107,8 +112,9 @@ def main():
     ap.add_argument("rev_a"); ap.add_argument("rev_b")
     ap.add_argument("--only", default="", help="regex on the source file names")
     ap.add_argument("--diff", action="store_true", help="print the first differing instruction lines")
+    ap.add_argument("--rename", action="append", default=[], metavar="PATTERN=REPLACEMENT", help="regex substitution on the kernel keys of rev_b")
     a = ap.parse_args()
-    A, Bk = collect(a.rev_a, a.only), collect(a.rev_b, a.only)
+    A, Bk = collect(a.rev_a, a.only), collect(a.rev_b, a.only, [r.split("=", 1) for r in a.rename])
     bad = 0
     for key in sorted(A):
         for file_a, pa in A[key]:
