@@ -624,6 +624,51 @@ NM_API int nm_sift_match_guided_host_f32(int n,
                                          float max_distance, int *const *result, int *count,
                                          float *const *best_distance);
 
+/* Batched mutual-nearest-neighbour filtering of a match list (the cross-check of a brute-force matcher; no reference
+ * counterpart: the reference's matcher tests one direction only, so several rows of A may claim the same row of B, and a
+ * client cross-checks with a second, swapped call and a comparison on the host). Given pair k's match list (e.g. the result
+ * of nm_sift_match_batch_dev_f32), a match i -> j is kept only when i is also the best row of A for column j. n <=
+ * NM_MATCH_MUTUAL_MAX_BATCH pairs in THREE launches on `stream` whatever n is (claims, scan, counts); no allocation, no
+ * synchronisation, no host read -- capturable into a HIP graph behind the matcher. It reads only the public inputs below,
+ * nothing of the blind matcher's plans, screens or workspace. Pair k (tables of n pointers, the tables in HOST memory):
+ *   A[k] / B[k]        descriptors, nA x 128 / nB x 128 row-major (an arena's desc);
+ *   d_nA[k], d_nB[k]   DEVICE ints, the row counts: nA = clip(*d_nA[k], 0, capA), nB = clip(*d_nB[k], 0, capB). Rows beyond
+ *                      them are never read;
+ *   matches[k]         device, capA ints: the list to filter (entries at and beyond nA are never read).
+ * Per pair, all fp32 (fma explicit, IEEE):
+ *   Distance: d(i, j) is the chain of nm_bf_distance_f32, acc = 0; acc = fmaf(t, t, acc) with t = A[i][q] - B[j][q],
+ *     q = 0 .. 127 in this order -- bit-equal to it.
+ *   Claim: row i < nA claims column j = matches[k][i] when 0 <= j < nB. Any other value (-1, below -1, >= nB) is no claim.
+ *   Keep: with tau = d(i, j), the claim is kept exactly when tau == tau (tau is not NaN), no i' < nA has d(i', j) < tau, and
+ *     no i' < i has d(i', j) == tau: i is the first minimum of column j in an ascending scan with strict <, the index
+ *     get_sift_matches' scan (kernels/match.cu:88-116) returns for the swapped call. A rival row with a NaN distance beats
+ *     nothing.
+ *   The chain never decreases (t * t >= 0, rounding is monotone, a NaN stays a NaN), so a rival row is abandoned as soon as
+ *     its partial sum, looked at every 16 dimensions, is no longer <= tau: this changes no result.
+ * Outputs: result[k] (device, capA ints; ALL capA entries are written: j for a kept claim, else -1, -1 beyond nA; it may
+ * alias no input), count (device, n ints: entries >= 0 of result[k]), forward_distance (optional table, may be NULL:
+ * forward_distance[k] device, capA floats = tau for a claiming row, +inf otherwise). The kept matches of a pair are
+ * injective (no two rows keep the same j). result[k] can go to nm_ransac_batch_dev_f32, nm_ransac_refit_batch_dev_f32 and
+ * nm_align_points as matches[k] as it is. A pair's outputs depend on that pair's inputs alone, never on n, on the pair's
+ * slot or on scheduling (no atomics; a beaten claim's -1 may be stored by several workgroups, always the same value).
+ * workspace: device, nm_sift_match_mutual_workspace_bytes(n, capA) bytes (0 for arguments out of range), no contents
+ * expected or preserved.
+ * Returns hipErrorInvalidValue, touching no device memory, for n not in [1, 64], capA or capB not in [1, 2^22), a NULL
+ * required pointer (every argument but forward_distance and stream) or a NULL among the first n entries of a table.
+ * nm_sift_match_mutual_host_f32: the same with every pointer in host memory (nA[k] / nB[k] point to host ints), no workspace
+ * and no stream, compiled from the same functions (csrc/nm_match_mutual_math.hpp): host and device results are identical
+ * bit for bit.                                                                                                            */
+#define NM_MATCH_MUTUAL_MAX_BATCH 64
+NM_API size_t nm_sift_match_mutual_workspace_bytes(int n, int capA);
+NM_API int nm_sift_match_mutual_batch_dev_f32(int n, const float *const *A, const int *const *d_nA, int capA,
+                                              const float *const *B, const int *const *d_nB, int capB,
+                                              const int *const *matches, int *const *result, int *count,
+                                              float *const *forward_distance, void *workspace, void *stream);
+NM_API int nm_sift_match_mutual_host_f32(int n, const float *const *A, const int *const *nA, int capA,
+                                         const float *const *B, const int *const *nB, int capB,
+                                         const int *const *matches, int *const *result, int *count,
+                                         float *const *forward_distance);
+
 /* ---- Mosaic plan and batched blend (no reference counterpart: the reference's client places frames on the host and
  * calls transform_blend once per frame). Together with nm_ransac_batch_dev_f32 the chain detect -> match -> RANSAC ->
  * plan -> blend runs on one stream with no host read and can be captured into one HIP graph.

@@ -112,6 +112,9 @@ _SIGNATURES = {
     "nm_ransac_refit_host_f32": (_I, [_I, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _F, _I, _P, _P, _P, _P, _P, _P]),
     "nm_sift_match_guided_batch_dev_f32": (_I, [_I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _P, _F, _F, _F, _P, _P, _P, _P]),
     "nm_sift_match_guided_host_f32": (_I, [_I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _P, _F, _F, _F, _P, _P, _P]),
+    "nm_sift_match_mutual_workspace_bytes": (_SZ, [_I, _I]),
+    "nm_sift_match_mutual_batch_dev_f32": (_I, [_I, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P]),
+    "nm_sift_match_mutual_host_f32": (_I, [_I, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P]),
     "nm_mosaic_plan_f32": (_I, [_I, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "nm_mosaic_plan_host_f32": (_I, [_I, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "nm_transform_blend_batch": (_I, [_P, _I, _I, _P, _I, _P, _I, _I, _P, _I, _P, _I, _P, _P]),
@@ -1005,6 +1008,102 @@ def sift_match_guided_host(As, axs, ays, nAs, Bs, bxs, bys, nBs, H, status=None,
                                                arr(list(best)) if want_distance else None),
            "nm_sift_match_guided_host_f32")
     return (result, count) + ((best,) if want_distance else ())
+
+
+MATCH_MUTUAL_MAX_BATCH = 64
+
+
+def _mutual_caps(n, lens, As, Bs, matches, capA, capB):
+    if n == 0 or any(l != n for l in lens) or n > MATCH_MUTUAL_MAX_BATCH:
+        raise NmError("bad batch")
+    if any(t.ndim != 2 or t.shape[1] != 128 for t in list(As) + list(Bs)):
+        raise NmError("descriptors must be (rows, 128)")
+    if any(t.ndim != 1 for t in matches):
+        raise NmError("a match list must be one-dimensional")
+    capA = min(min(t.shape[0] for t in As), min(t.shape[0] for t in matches)) if capA is None else capA
+    capB = min(t.shape[0] for t in Bs) if capB is None else capB
+    if not (1 <= capA < (1 << 22) and 1 <= capB < (1 << 22)):
+        raise NmError("capacity out of range")
+    if any(t.shape[0] < capA for t in list(As) + list(matches)) or any(t.shape[0] < capB for t in Bs):
+        raise NmError("a descriptor or match tensor is smaller than the capacity")
+    return capA, capB
+
+
+class MatchMutualWorkspace:
+    """Device scratch of sift_match_mutual_batch_dev for up to n pairs of capA rows (the compacted claims)."""
+
+    def __init__(self, n, capA, device=None):
+        torch = _torch()
+        need = lib().nm_sift_match_mutual_workspace_bytes(n, capA)
+        if need == 0:
+            raise NmError("mutual-match workspace: n %r / capA %r out of range" % (n, capA))
+        self.n, self.capA = n, capA
+        self.buf = torch.empty(need, dtype=torch.uint8, device=device if device is not None else "cuda")
+
+
+def sift_match_mutual_batch_dev(As, d_nAs, Bs, d_nBs, matches, capA=None, capB=None, results=None, workspace=None,
+                                want_distance=False):
+    """Mutual-nearest-neighbour filter of n = len(As) <= MATCH_MUTUAL_MAX_BATCH match lists
+    (nm_sift_match_mutual_batch_dev_f32): three launches on the current stream, no host read. As / Bs are float32 device
+    descriptors (rows, 128), d_nAs / d_nBs int32 DEVICE sizes (e.g. SiftArena.desc, .num_items), matches[k] the int32 device
+    list to filter (e.g. what sift_match_batch_dev wrote). Row i keeps its match j only when no row of A is nearer to column
+    j and no earlier row is as near. results: n int32 device tensors of >= capA rows to write into (default: new; none may
+    be a match list). workspace: a MatchMutualWorkspace (default: new). Returns (results, count[n]) and, with
+    want_distance, the list of float32 (capA,) forward distances (+inf for a row without a claim). results[k] plugs into
+    ransac_batch_dev, ransac_refit_batch_dev and align_points as matches."""
+    torch = _torch()
+    n = len(As)
+    lens = [len(v) for v in (d_nAs, Bs, d_nBs, matches)] + ([len(results)] if results is not None else [])
+    capA, capB = _mutual_caps(n, lens, As, Bs, matches, capA, capB)
+    device = As[0].device
+    if results is None:
+        results = [torch.empty(capA, dtype=torch.int32, device=device) for _ in range(n)]
+    if any(r.shape[0] < capA for r in results):
+        raise NmError("a result tensor is smaller than the capacity")
+    tensors = list(As) + list(d_nAs) + list(Bs) + list(d_nBs) + list(matches) + list(results)
+    if any(t.device != device for t in tensors) or device.type != "cuda" or torch.cuda.current_device() != device.index:
+        raise NmError("all tensors must live on the current device")
+    if any(c.numel() < 1 for c in list(d_nAs) + list(d_nBs)):
+        raise NmError("a device size tensor is empty")
+    if {r.data_ptr() for r in results} & {m.data_ptr() for m in matches}:
+        raise NmError("a result tensor is also a match list")
+    if workspace is None:
+        workspace = MatchMutualWorkspace(n, capA, device)
+    need = lib().nm_sift_match_mutual_workspace_bytes(n, capA)
+    if need == 0 or workspace.buf.numel() < need or workspace.buf.device != device:
+        raise NmError("mutual-match workspace too small or on another device")
+    count = torch.empty(n, dtype=torch.int32, device=device)
+    fwd = [torch.empty(capA, dtype=torch.float32, device=device) for _ in range(n)] if want_distance else None
+    arr = lambda ts, dt: (C.c_void_p * n)(*[_dev(t, dt) for t in ts])
+    f, i32 = torch.float32, torch.int32
+    _check(lib().nm_sift_match_mutual_batch_dev_f32(n, arr(As, f), arr(d_nAs, i32), capA, arr(Bs, f), arr(d_nBs, i32), capB,
+                                                    arr(matches, i32), arr(results, i32), _dev(count),
+                                                    arr(fwd, f) if want_distance else None, _dev(workspace.buf), _stream()),
+           "nm_sift_match_mutual_batch_dev_f32")
+    return (results, count) + ((fwd,) if want_distance else ())
+
+
+def sift_match_mutual_host(As, nAs, Bs, nBs, matches, capA=None, capB=None, want_distance=False):
+    """sift_match_mutual_batch_dev on the host (nm_sift_match_mutual_host_f32, the same functions): numpy in and out,
+    bit-identical results. nAs / nBs are host ints. Returns (results (n, capA) int32, count (n,)) and, with want_distance,
+    forward distances (n, capA) float32."""
+    import numpy as np
+    n = len(As)
+    lens = [len(v) for v in (nAs, Bs, nBs, matches)]
+    As, Bs = ([np.ascontiguousarray(v, dtype=np.float32) for v in vs] for vs in (As, Bs))
+    matches = [np.ascontiguousarray(v, dtype=np.int32) for v in matches]
+    capA, capB = _mutual_caps(n, lens, As, Bs, matches, capA, capB)
+    nA = np.array([int(v) for v in nAs], np.int32)
+    nB = np.array([int(v) for v in nBs], np.int32)
+    result = np.zeros((n, capA), np.int32)
+    count = np.zeros(n, np.int32)
+    fwd = np.zeros((n, capA), np.float32) if want_distance else None
+    arr = lambda vals: (C.c_void_p * n)(*[v.ctypes.data for v in vals])
+    _check(lib().nm_sift_match_mutual_host_f32(n, arr(As), arr([nA[k:k + 1] for k in range(n)]), capA, arr(Bs),
+                                               arr([nB[k:k + 1] for k in range(n)]), capB, arr(matches), arr(list(result)),
+                                               count.ctypes.data, arr(list(fwd)) if want_distance else None),
+           "nm_sift_match_mutual_host_f32")
+    return (result, count) + ((fwd,) if want_distance else ())
 
 
 MOSAIC_MAX_BATCH = 64
