@@ -6,6 +6,7 @@ multi-GPU launcher: it binds the C ABI with ctypes and uses torch only for devic
 torch.distributed. There is NO CPU fallback: if the library is missing, every entry point raises.
 """
 import ctypes as C
+import math
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -746,8 +747,115 @@ def ransac(model, sx, sy, dx, dy, rand_list, thr):
     return pos, Hb, H_all, inl
 
 
-RANSAC_MAX_BATCH = 64
+# ---- the pair-batch stages (batched RANSAC, inlier refit, guided and mutual matching): csrc/nm_pair_batch.hpp in Python ----
+# A call takes n <= 64 pairs as equally long lists of per-pair tensors; a capacity is the number of rows the kernels may
+# touch and lies in [1, 2^22); device wrappers want everything on the current device, host twins take numpy.
+_PAIR_MAX_BATCH = 64
+_PAIR_CAP_LIMIT = 1 << 22
+RANSAC_MAX_BATCH = MATCH_GUIDED_MAX_BATCH = MATCH_MUTUAL_MAX_BATCH = _PAIR_MAX_BATCH
 RANSAC_MAX_ITERATIONS = 1 << 20
+RANSAC_REFIT_MAX_ROUNDS = 4
+
+
+def _pair_count(*lists):
+    """n of a call: its per-pair lists (None: an optional list that was not given) are equally long, 0 < n <= 64."""
+    n = len(lists[0])
+    if any(len(v) != n for v in lists if v is not None) or not 0 < n <= _PAIR_MAX_BATCH:
+        raise NmError("pair batch: lists of one length in [1, %d] expected" % _PAIR_MAX_BATCH)
+    return n
+
+
+def _pair_cap(cap, tensors):
+    """A capacity (default: the smallest first dimension of `tensors`), in range and no larger than any of them."""
+    cap = min(t.shape[0] for t in tensors) if cap is None else cap
+    if not 1 <= cap < _PAIR_CAP_LIMIT:
+        raise NmError("pair batch: capacity %r outside [1, %d)" % (cap, _PAIR_CAP_LIMIT))
+    if any(t.shape[0] < cap for t in tensors):
+        raise NmError("pair batch: a tensor is smaller than the capacity %d" % cap)
+    return cap
+
+
+def _pair_model_shape(n, h_numel, status_numel):
+    if h_numel != 9 * n or status_numel not in (None, n):
+        raise NmError("pair batch: H must hold n x 9 floats and status n values")
+
+
+def _pair_descriptors(*lists):
+    if any(t.ndim != 2 or t.shape[1] != 128 for ts in lists for t in ts):
+        raise NmError("descriptors must be (rows, 128)")
+
+
+def _pair_device(tensors, sizes):
+    """The device of a call: every tensor (None: an optional one that was not given) on the current CUDA device, no
+    DEVICE size tensor empty."""
+    torch = _torch()
+    device = tensors[0].device
+    if any(t is not None and t.device != device for t in tensors) or device.type != "cuda" or \
+            torch.cuda.current_device() != device.index:
+        raise NmError("pair batch: all tensors must live on the current device")
+    if any(c.numel() < 1 for c in sizes):
+        raise NmError("pair batch: a device size tensor is empty")
+    return device
+
+
+def _pair_dev_table(tensors, dtype):
+    """Host table of the device pointers of contiguous `dtype` tensors (_dev's rules, checked for the table as a whole);
+    None (an optional table) stays None."""
+    if tensors is None:
+        return None
+    if not all(t.is_cuda and t.dtype == dtype and t.is_contiguous() for t in tensors):
+        raise NmError("pair batch: contiguous device tensors of dtype %s expected" % dtype)
+    return (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+def _pair_host_table(arrays):
+    return None if arrays is None else (C.c_void_p * len(arrays))(*[a.ctypes.data for a in arrays])
+
+
+def _pair_host_ptr(a):
+    return None if a is None else a.ctypes.data
+
+
+def _pair_host_arrays(values, dtype, flat=True):
+    import numpy as np
+    arrays = [np.ascontiguousarray(v, dtype=dtype) for v in values]
+    return [a.reshape(-1) for a in arrays] if flat else arrays
+
+
+def _pair_host_sizes(ns):
+    """Host sizes as the C entries take them, one pointer per pair: the one-element views of one int32 array."""
+    import numpy as np
+    a = np.array([int(v) for v in ns], np.int32)
+    return [a[k:k + 1] for k in range(a.size)]
+
+
+def _pair_host_model(n, H, status):
+    import numpy as np
+    H = np.ascontiguousarray(H, dtype=np.float32).reshape(-1)
+    status = None if status is None else np.ascontiguousarray(status, dtype=np.int32).reshape(-1)
+    _pair_model_shape(n, H.size, None if status is None else status.size)
+    return H, status
+
+
+def _pair_host_match_out(n, capA, want_distance):
+    import numpy as np
+    return np.zeros((n, capA), np.int32), np.zeros(n, np.int32), np.zeros((n, capA), np.float32) if want_distance else None
+
+
+def _pair_dev_match_out(n, capA, results, device, want_distance):
+    """results (given or new, no smaller than capA), count and the optional per-row distances of guided / mutual matching."""
+    torch = _torch()
+    if results is None:
+        results = [torch.empty(capA, dtype=torch.int32, device=device) for _ in range(n)]
+    _pair_cap(capA, results)
+    count = torch.empty(n, dtype=torch.int32, device=device)
+    dist = [torch.empty(capA, dtype=torch.float32, device=device) for _ in range(n)] if want_distance else None
+    return results, count, dist
+
+
+def _point_tables_dev(src_xs, src_ys, d_nAs, dst_xs, dst_ys, matches):
+    f, i32 = _torch().float32, _torch().int32
+    return [_pair_dev_table(ts, dt) for ts, dt in ((src_xs, f), (src_ys, f), (d_nAs, i32), (dst_xs, f), (dst_ys, f), (matches, i32))]
 
 
 class RansacBatchWorkspace:
@@ -775,24 +883,15 @@ def ransac_batch_dev(model, src_xs, src_ys, d_nAs, dst_xs, dst_ys, matches, iter
     error. seeds (host ints) default to range(n); capA to the rows of the source tensors. Returns (H_best[n, 9],
     best_inliers[n], position[n], status[n]) and, with want_all, also (homographies[n, iterations, 9], inliers[n, iterations])."""
     torch = _torch()
-    n = len(src_xs)
-    if not (n == len(src_ys) == len(d_nAs) == len(dst_xs) == len(dst_ys) == len(matches)) or not 0 < n <= RANSAC_MAX_BATCH:
-        raise NmError("bad batch")
+    n = _pair_count(src_xs, src_ys, d_nAs, dst_xs, dst_ys, matches)
     if model not in (0, 1, 2) or not 0 < iterations <= RANSAC_MAX_ITERATIONS:
         raise NmError("model %r / iterations %r out of range" % (model, iterations))
     seeds = list(range(n)) if seeds is None else [int(s) for s in seeds]
     if len(seeds) != n or any(not 0 <= s <= 0xFFFFFFFF for s in seeds):
         raise NmError("seeds: %d unsigned 32-bit values expected" % n)
-    capA = min(min(t.shape[0] for t in src_xs), min(t.shape[0] for t in src_ys), min(t.shape[0] for t in matches)) \
-        if capA is None else capA
-    if any(t.shape[0] < capA for t in list(src_xs) + list(src_ys) + list(matches)):
-        raise NmError("a source coordinate or match tensor is smaller than the capacity")
-    device = src_xs[0].device
-    tensors = list(src_xs) + list(src_ys) + list(d_nAs) + list(dst_xs) + list(dst_ys) + list(matches)
-    if any(t.device != device for t in tensors) or device.type != "cuda" or torch.cuda.current_device() != device.index:
-        raise NmError("all tensors must live on the current device")
-    if any(c.numel() < 1 for c in d_nAs):
-        raise NmError("a device size tensor is empty")
+    capA = _pair_cap(capA, list(src_xs) + list(src_ys) + list(matches))
+    device = _pair_device(list(src_xs) + list(src_ys) + list(d_nAs) + list(dst_xs) + list(dst_ys) + list(matches) +
+                          [workspace.buf if workspace is not None else None], d_nAs)
     if workspace is None:
         workspace = RansacBatchWorkspace(n, capA, iterations, device)
     need = lib().nm_ransac_batch_dev_workspace_bytes(n, capA, iterations)
@@ -802,13 +901,8 @@ def ransac_batch_dev(model, src_xs, src_ys, d_nAs, dst_xs, dst_ys, matches, iter
     best, pos, status = (torch.empty(n, dtype=torch.int32, device=device) for _ in range(3))
     H_all = torch.empty((n, iterations, 9), dtype=torch.float32, device=device) if want_all else None
     inl = torch.empty((n, iterations), dtype=torch.int32, device=device) if want_all else None
-    arr = lambda vals: (C.c_void_p * n)(*vals)
-    _check(lib().nm_ransac_batch_dev_f32(model, n, arr([_dev(t, torch.float32) for t in src_xs]),
-                                         arr([_dev(t, torch.float32) for t in src_ys]),
-                                         arr([_dev(t, torch.int32) for t in d_nAs]), capA,
-                                         arr([_dev(t, torch.float32) for t in dst_xs]),
-                                         arr([_dev(t, torch.float32) for t in dst_ys]),
-                                         arr([_dev(t, torch.int32) for t in matches]), iterations, threshold,
+    tables = _point_tables_dev(src_xs, src_ys, d_nAs, dst_xs, dst_ys, matches)
+    _check(lib().nm_ransac_batch_dev_f32(model, n, *tables[:3], capA, *tables[3:], iterations, threshold,
                                          (C.c_uint * n)(*seeds), _dev(H_best), _dev(best), _dev(pos), _dev(status),
                                          _dev(H_all) if want_all else None, _dev(inl) if want_all else None,
                                          _dev(workspace.buf), _stream()), "nm_ransac_batch_dev_f32")
@@ -817,15 +911,10 @@ def ransac_batch_dev(model, src_xs, src_ys, d_nAs, dst_xs, dst_ys, matches, iter
     return H_best, best, pos, status
 
 
-RANSAC_REFIT_MAX_ROUNDS = 4
-
-
-def _refit_check(model, n, lens, rounds, threshold):
-    if any(l != n for l in lens) or not 0 < n <= RANSAC_MAX_BATCH:
-        raise NmError("bad batch")
+def _refit_check(model, rounds, threshold):
     if model not in (0, 1, 2) or not 0 <= int(rounds) <= RANSAC_REFIT_MAX_ROUNDS or int(rounds) != rounds:
         raise NmError("model %r / rounds %r out of range" % (model, rounds))
-    if threshold != threshold or threshold in (float("inf"), float("-inf")):
+    if not math.isfinite(threshold):
         raise NmError("threshold must be finite")
 
 
@@ -837,32 +926,18 @@ def ransac_refit_batch_dev(model, src_xs, src_ys, d_nAs, dst_xs, dst_ys, matches
     the inlier count (and mask) of H itself. Returns (H_out[n, 9], count[n], status[n], rounds_done[n]) and then, when
     asked for, mask uint8 (n, capA) and rms float32 (n,)."""
     torch = _torch()
-    n = len(src_xs)
-    _refit_check(model, n, [len(v) for v in (src_ys, d_nAs, dst_xs, dst_ys, matches)], rounds, threshold)
-    capA = min(min(t.shape[0] for t in src_xs), min(t.shape[0] for t in src_ys), min(t.shape[0] for t in matches)) \
-        if capA is None else capA
-    if not 1 <= capA < (1 << 22) or any(t.shape[0] < capA for t in list(src_xs) + list(src_ys) + list(matches)):
-        raise NmError("a source coordinate or match tensor is smaller than the capacity, or the capacity is out of range")
-    device = src_xs[0].device
-    tensors = list(src_xs) + list(src_ys) + list(d_nAs) + list(dst_xs) + list(dst_ys) + list(matches) + [H] + \
-        ([status] if status is not None else [])
-    if any(t.device != device for t in tensors) or device.type != "cuda" or torch.cuda.current_device() != device.index:
-        raise NmError("all tensors must live on the current device")
-    if any(c.numel() < 1 for c in d_nAs):
-        raise NmError("a device size tensor is empty")
-    if H.numel() != 9 * n or (status is not None and status.numel() != n):
-        raise NmError("H must hold n x 9 floats and status n values")
+    n = _pair_count(src_xs, src_ys, d_nAs, dst_xs, dst_ys, matches)
+    _refit_check(model, rounds, threshold)
+    capA = _pair_cap(capA, list(src_xs) + list(src_ys) + list(matches))
+    _pair_model_shape(n, H.numel(), None if status is None else status.numel())
+    device = _pair_device(list(src_xs) + list(src_ys) + list(d_nAs) + list(dst_xs) + list(dst_ys) + list(matches) + [H, status],
+                          d_nAs)
     H_out = torch.empty((n, 9), dtype=torch.float32, device=device)
     count, st, done = (torch.empty(n, dtype=torch.int32, device=device) for _ in range(3))
     mask = torch.empty((n, capA), dtype=torch.uint8, device=device) if want_mask else None
     rms = torch.empty(n, dtype=torch.float32, device=device) if want_rms else None
-    arr = lambda vals: (C.c_void_p * n)(*vals)
-    _check(lib().nm_ransac_refit_batch_dev_f32(model, n, arr([_dev(t, torch.float32) for t in src_xs]),
-                                               arr([_dev(t, torch.float32) for t in src_ys]),
-                                               arr([_dev(t, torch.int32) for t in d_nAs]), capA,
-                                               arr([_dev(t, torch.float32) for t in dst_xs]),
-                                               arr([_dev(t, torch.float32) for t in dst_ys]),
-                                               arr([_dev(t, torch.int32) for t in matches]), _dev(H, torch.float32),
+    tables = _point_tables_dev(src_xs, src_ys, d_nAs, dst_xs, dst_ys, matches)
+    _check(lib().nm_ransac_refit_batch_dev_f32(model, n, *tables[:3], capA, *tables[3:], _dev(H, torch.float32),
                                                _dev(status, torch.int32) if status is not None else None, threshold,
                                                int(rounds), _dev(H_out), _dev(count), _dev(st), _dev(done),
                                                _dev(mask) if want_mask else None, _dev(rms) if want_rms else None,
@@ -875,61 +950,32 @@ def ransac_refit_host(model, src_xs, src_ys, nAs, dst_xs, dst_ys, matches, H, st
     """ransac_refit_batch_dev on the host (nm_ransac_refit_host_f32, the same functions): numpy in and out, bit-identical
     results. nAs are host ints."""
     import numpy as np
-    n = len(src_xs)
-    _refit_check(model, n, [len(v) for v in (src_ys, nAs, dst_xs, dst_ys, matches)], rounds, threshold)
-    f32 = lambda vs: [np.ascontiguousarray(v, dtype=np.float32).reshape(-1) for v in vs]
-    src_xs, src_ys, dst_xs, dst_ys = f32(src_xs), f32(src_ys), f32(dst_xs), f32(dst_ys)
-    matches = [np.ascontiguousarray(v, dtype=np.int32).reshape(-1) for v in matches]
-    capA = min(min(t.shape[0] for t in src_xs), min(t.shape[0] for t in src_ys), min(t.shape[0] for t in matches)) \
-        if capA is None else capA
-    if not 1 <= capA < (1 << 22) or any(t.shape[0] < capA for t in src_xs + src_ys + matches):
-        raise NmError("a source coordinate or match tensor is smaller than the capacity, or the capacity is out of range")
+    n = _pair_count(src_xs, src_ys, nAs, dst_xs, dst_ys, matches)
+    _refit_check(model, rounds, threshold)
+    src_xs, src_ys, dst_xs, dst_ys = (_pair_host_arrays(vs, np.float32) for vs in (src_xs, src_ys, dst_xs, dst_ys))
+    matches = _pair_host_arrays(matches, np.int32)
+    capA = _pair_cap(capA, src_xs + src_ys + matches)
     for m, x, y in zip(matches, dst_xs, dst_ys):
         if m.size and int(m.max()) >= min(x.size, y.size):
             raise NmError("a match points beyond the destination coordinates")
-    H = np.ascontiguousarray(H, dtype=np.float32).reshape(-1)
-    if status is not None:
-        status = np.ascontiguousarray(status, dtype=np.int32).reshape(-1)
-    if H.size != 9 * n or (status is not None and status.size != n):
-        raise NmError("H must hold n x 9 floats and status n values")
-    nA = np.array([int(v) for v in nAs], np.int32)
+    H, status = _pair_host_model(n, H, status)
+    nA = _pair_host_sizes(nAs)
     H_out = np.zeros((n, 9), np.float32)
     count, st, done = (np.zeros(n, np.int32) for _ in range(3))
     mask = np.zeros((n, capA), np.uint8) if want_mask else None
     rms = np.zeros(n, np.float32) if want_rms else None
-    arr = lambda vals: (C.c_void_p * n)(*[v.ctypes.data for v in vals])
-    ptr = lambda a: a.ctypes.data if a is not None else None
-    _check(lib().nm_ransac_refit_host_f32(model, n, arr(src_xs), arr(src_ys), arr([nA[k:k + 1] for k in range(n)]), capA,
-                                          arr(dst_xs), arr(dst_ys), arr(matches), ptr(H), ptr(status), threshold,
-                                          int(rounds), ptr(H_out), ptr(count), ptr(st), ptr(done), ptr(mask), ptr(rms)),
-           "nm_ransac_refit_host_f32")
+    arr, ptr = _pair_host_table, _pair_host_ptr
+    _check(lib().nm_ransac_refit_host_f32(model, n, arr(src_xs), arr(src_ys), arr(nA), capA, arr(dst_xs), arr(dst_ys),
+                                          arr(matches), ptr(H), ptr(status), threshold, int(rounds), ptr(H_out), ptr(count),
+                                          ptr(st), ptr(done), ptr(mask), ptr(rms)), "nm_ransac_refit_host_f32")
     return (H_out, count, st, done) + ((mask,) if want_mask else ()) + ((rms,) if want_rms else ())
 
 
-MATCH_GUIDED_MAX_BATCH = 64
-
-
-def _guided_check(n, lens, capA, capB, radius2, ambiguity, max_distance):
-    inf = float("inf")
-    if any(l != n for l in lens) or not 0 < n <= MATCH_GUIDED_MAX_BATCH:
-        raise NmError("bad batch")
-    if not (1 <= capA < (1 << 22) and 1 <= capB < (1 << 22)):
-        raise NmError("capacity out of range")
-    if radius2 != radius2 or ambiguity != ambiguity or radius2 in (inf, -inf) or ambiguity in (inf, -inf):
+def _guided_check(radius2, ambiguity, max_distance):
+    if not (math.isfinite(radius2) and math.isfinite(ambiguity)):
         raise NmError("radius2 and ambiguity must be finite")
     if max_distance != max_distance:
         raise NmError("max_distance must not be NaN")
-
-
-def _guided_caps(As, axs, ays, Bs, bxs, bys, capA, capB):
-    capA = min(min(t.shape[0] for t in As), min(t.shape[0] for t in axs), min(t.shape[0] for t in ays)) if capA is None else capA
-    capB = min(min(t.shape[0] for t in Bs), min(t.shape[0] for t in bxs), min(t.shape[0] for t in bys)) if capB is None else capB
-    if any(t.shape[0] < capA for t in list(As) + list(axs) + list(ays)) or \
-            any(t.shape[0] < capB for t in list(Bs) + list(bxs) + list(bys)):
-        raise NmError("a descriptor or coordinate tensor is smaller than the capacity")
-    if any(t.ndim != 2 or t.shape[1] != 128 for t in list(As) + list(Bs)):
-        raise NmError("descriptors must be (rows, 128)")
-    return capA, capB
 
 
 def sift_match_guided_batch_dev(As, axs, ays, d_nAs, Bs, bxs, bys, d_nBs, H, status=None, radius2=9.0, ambiguity=0.8,
@@ -943,35 +989,21 @@ def sift_match_guided_batch_dev(As, axs, ays, d_nAs, Bs, bxs, bys, d_nBs, H, sta
     Returns (results, count[n]) and, with want_distance, the list of float32 (capA,) best distances. results[k] plugs into
     ransac_refit_batch_dev(matches=...)."""
     torch = _torch()
-    n = len(As)
-    lens = [len(v) for v in (axs, ays, d_nAs, Bs, bxs, bys, d_nBs)] + ([len(results)] if results is not None else [])
-    if n == 0 or any(l != n for l in lens):
-        raise NmError("bad batch")
-    capA, capB = _guided_caps(As, axs, ays, Bs, bxs, bys, capA, capB)
-    _guided_check(n, lens, capA, capB, radius2, ambiguity, max_distance)
-    device = As[0].device
-    if results is None:
-        results = [torch.empty(capA, dtype=torch.int32, device=device) for _ in range(n)]
-    if any(r.shape[0] < capA for r in results):
-        raise NmError("a result tensor is smaller than the capacity")
-    tensors = list(As) + list(axs) + list(ays) + list(d_nAs) + list(Bs) + list(bxs) + list(bys) + list(d_nBs) + \
-        list(results) + [H] + ([status] if status is not None else [])
-    if any(t.device != device for t in tensors) or device.type != "cuda" or torch.cuda.current_device() != device.index:
-        raise NmError("all tensors must live on the current device")
-    if any(c.numel() < 1 for c in list(d_nAs) + list(d_nBs)):
-        raise NmError("a device size tensor is empty")
-    if H.numel() != 9 * n or (status is not None and status.numel() != n):
-        raise NmError("H must hold n x 9 floats and status n values")
-    count = torch.empty(n, dtype=torch.int32, device=device)
-    best = [torch.empty(capA, dtype=torch.float32, device=device) for _ in range(n)] if want_distance else None
-    arr = lambda ts, dt: (C.c_void_p * n)(*[_dev(t, dt) for t in ts])
-    f, i32 = torch.float32, torch.int32
+    n = _pair_count(As, axs, ays, d_nAs, Bs, bxs, bys, d_nBs, results)
+    capA = _pair_cap(capA, list(As) + list(axs) + list(ays))
+    capB = _pair_cap(capB, list(Bs) + list(bxs) + list(bys))
+    _pair_descriptors(As, Bs)
+    _guided_check(radius2, ambiguity, max_distance)
+    _pair_model_shape(n, H.numel(), None if status is None else status.numel())
+    device = _pair_device(list(As) + list(axs) + list(ays) + list(d_nAs) + list(Bs) + list(bxs) + list(bys) + list(d_nBs) +
+                          list(results or ()) + [H, status], list(d_nAs) + list(d_nBs))
+    results, count, best = _pair_dev_match_out(n, capA, results, device, want_distance)
+    arr, f, i32 = _pair_dev_table, torch.float32, torch.int32
     _check(lib().nm_sift_match_guided_batch_dev_f32(n, arr(As, f), arr(axs, f), arr(ays, f), arr(d_nAs, i32), capA,
                                                     arr(Bs, f), arr(bxs, f), arr(bys, f), arr(d_nBs, i32), capB,
                                                     _dev(H, f), _dev(status, i32) if status is not None else None,
                                                     radius2, ambiguity, max_distance, arr(results, i32), _dev(count),
-                                                    arr(best, f) if want_distance else None, _stream()),
-           "nm_sift_match_guided_batch_dev_f32")
+                                                    arr(best, f), _stream()), "nm_sift_match_guided_batch_dev_f32")
     return (results, count) + ((best,) if want_distance else ())
 
 
@@ -981,52 +1013,29 @@ def sift_match_guided_host(As, axs, ays, nAs, Bs, bxs, bys, nBs, H, status=None,
     bit-identical results. nAs / nBs are host ints. Returns (results (n, capA) int32, count (n,)) and, with want_distance,
     best distances (n, capA) float32."""
     import numpy as np
-    n = len(As)
-    lens = [len(v) for v in (axs, ays, nAs, Bs, bxs, bys, nBs)]
-    if n == 0 or any(l != n for l in lens):
-        raise NmError("bad batch")
-    f32 = lambda vs: [np.ascontiguousarray(v, dtype=np.float32) for v in vs]
-    As, Bs = f32(As), f32(Bs)
-    axs, ays, bxs, bys = ([v.reshape(-1) for v in f32(vs)] for vs in (axs, ays, bxs, bys))
-    capA, capB = _guided_caps(As, axs, ays, Bs, bxs, bys, capA, capB)
-    _guided_check(n, lens, capA, capB, radius2, ambiguity, max_distance)
-    H = np.ascontiguousarray(H, dtype=np.float32).reshape(-1)
-    if status is not None:
-        status = np.ascontiguousarray(status, dtype=np.int32).reshape(-1)
-    if H.size != 9 * n or (status is not None and status.size != n):
-        raise NmError("H must hold n x 9 floats and status n values")
-    nA = np.array([int(v) for v in nAs], np.int32)
-    nB = np.array([int(v) for v in nBs], np.int32)
-    result = np.zeros((n, capA), np.int32)
-    count = np.zeros(n, np.int32)
-    best = np.zeros((n, capA), np.float32) if want_distance else None
-    arr = lambda vals: (C.c_void_p * n)(*[v.ctypes.data for v in vals])
-    _check(lib().nm_sift_match_guided_host_f32(n, arr(As), arr(axs), arr(ays), arr([nA[k:k + 1] for k in range(n)]), capA,
-                                               arr(Bs), arr(bxs), arr(bys), arr([nB[k:k + 1] for k in range(n)]), capB,
-                                               H.ctypes.data, status.ctypes.data if status is not None else None, radius2,
-                                               ambiguity, max_distance, arr(list(result)), count.ctypes.data,
-                                               arr(list(best)) if want_distance else None),
+    n = _pair_count(As, axs, ays, nAs, Bs, bxs, bys, nBs)
+    As, Bs = (_pair_host_arrays(vs, np.float32, flat=False) for vs in (As, Bs))
+    axs, ays, bxs, bys = (_pair_host_arrays(vs, np.float32) for vs in (axs, ays, bxs, bys))
+    capA = _pair_cap(capA, As + axs + ays)
+    capB = _pair_cap(capB, Bs + bxs + bys)
+    _pair_descriptors(As, Bs)
+    _guided_check(radius2, ambiguity, max_distance)
+    H, status = _pair_host_model(n, H, status)
+    nA, nB = _pair_host_sizes(nAs), _pair_host_sizes(nBs)
+    result, count, best = _pair_host_match_out(n, capA, want_distance)
+    arr, ptr = _pair_host_table, _pair_host_ptr
+    _check(lib().nm_sift_match_guided_host_f32(n, arr(As), arr(axs), arr(ays), arr(nA), capA, arr(Bs), arr(bxs), arr(bys),
+                                               arr(nB), capB, ptr(H), ptr(status), radius2, ambiguity, max_distance,
+                                               arr(list(result)), ptr(count), arr(list(best)) if want_distance else None),
            "nm_sift_match_guided_host_f32")
     return (result, count) + ((best,) if want_distance else ())
 
 
-MATCH_MUTUAL_MAX_BATCH = 64
-
-
-def _mutual_caps(n, lens, As, Bs, matches, capA, capB):
-    if n == 0 or any(l != n for l in lens) or n > MATCH_MUTUAL_MAX_BATCH:
-        raise NmError("bad batch")
-    if any(t.ndim != 2 or t.shape[1] != 128 for t in list(As) + list(Bs)):
-        raise NmError("descriptors must be (rows, 128)")
+def _mutual_caps(As, Bs, matches, capA, capB):
+    _pair_descriptors(As, Bs)
     if any(t.ndim != 1 for t in matches):
         raise NmError("a match list must be one-dimensional")
-    capA = min(min(t.shape[0] for t in As), min(t.shape[0] for t in matches)) if capA is None else capA
-    capB = min(t.shape[0] for t in Bs) if capB is None else capB
-    if not (1 <= capA < (1 << 22) and 1 <= capB < (1 << 22)):
-        raise NmError("capacity out of range")
-    if any(t.shape[0] < capA for t in list(As) + list(matches)) or any(t.shape[0] < capB for t in Bs):
-        raise NmError("a descriptor or match tensor is smaller than the capacity")
-    return capA, capB
+    return _pair_cap(capA, list(As) + list(matches)), _pair_cap(capB, list(Bs))
 
 
 class MatchMutualWorkspace:
@@ -1052,34 +1061,22 @@ def sift_match_mutual_batch_dev(As, d_nAs, Bs, d_nBs, matches, capA=None, capB=N
     want_distance, the list of float32 (capA,) forward distances (+inf for a row without a claim). results[k] plugs into
     ransac_batch_dev, ransac_refit_batch_dev and align_points as matches."""
     torch = _torch()
-    n = len(As)
-    lens = [len(v) for v in (d_nAs, Bs, d_nBs, matches)] + ([len(results)] if results is not None else [])
-    capA, capB = _mutual_caps(n, lens, As, Bs, matches, capA, capB)
-    device = As[0].device
-    if results is None:
-        results = [torch.empty(capA, dtype=torch.int32, device=device) for _ in range(n)]
-    if any(r.shape[0] < capA for r in results):
-        raise NmError("a result tensor is smaller than the capacity")
-    tensors = list(As) + list(d_nAs) + list(Bs) + list(d_nBs) + list(matches) + list(results)
-    if any(t.device != device for t in tensors) or device.type != "cuda" or torch.cuda.current_device() != device.index:
-        raise NmError("all tensors must live on the current device")
-    if any(c.numel() < 1 for c in list(d_nAs) + list(d_nBs)):
-        raise NmError("a device size tensor is empty")
+    n = _pair_count(As, d_nAs, Bs, d_nBs, matches, results)
+    capA, capB = _mutual_caps(As, Bs, matches, capA, capB)
+    device = _pair_device(list(As) + list(d_nAs) + list(Bs) + list(d_nBs) + list(matches) + list(results or ()) +
+                          [workspace.buf if workspace is not None else None], list(d_nAs) + list(d_nBs))
+    results, count, fwd = _pair_dev_match_out(n, capA, results, device, want_distance)
     if {r.data_ptr() for r in results} & {m.data_ptr() for m in matches}:
         raise NmError("a result tensor is also a match list")
     if workspace is None:
         workspace = MatchMutualWorkspace(n, capA, device)
     need = lib().nm_sift_match_mutual_workspace_bytes(n, capA)
-    if need == 0 or workspace.buf.numel() < need or workspace.buf.device != device:
-        raise NmError("mutual-match workspace too small or on another device")
-    count = torch.empty(n, dtype=torch.int32, device=device)
-    fwd = [torch.empty(capA, dtype=torch.float32, device=device) for _ in range(n)] if want_distance else None
-    arr = lambda ts, dt: (C.c_void_p * n)(*[_dev(t, dt) for t in ts])
-    f, i32 = torch.float32, torch.int32
+    if need == 0 or workspace.buf.numel() < need:
+        raise NmError("mutual-match workspace too small")
+    arr, f, i32 = _pair_dev_table, torch.float32, torch.int32
     _check(lib().nm_sift_match_mutual_batch_dev_f32(n, arr(As, f), arr(d_nAs, i32), capA, arr(Bs, f), arr(d_nBs, i32), capB,
-                                                    arr(matches, i32), arr(results, i32), _dev(count),
-                                                    arr(fwd, f) if want_distance else None, _dev(workspace.buf), _stream()),
-           "nm_sift_match_mutual_batch_dev_f32")
+                                                    arr(matches, i32), arr(results, i32), _dev(count), arr(fwd, f),
+                                                    _dev(workspace.buf), _stream()), "nm_sift_match_mutual_batch_dev_f32")
     return (results, count) + ((fwd,) if want_distance else ())
 
 
@@ -1088,20 +1085,15 @@ def sift_match_mutual_host(As, nAs, Bs, nBs, matches, capA=None, capB=None, want
     bit-identical results. nAs / nBs are host ints. Returns (results (n, capA) int32, count (n,)) and, with want_distance,
     forward distances (n, capA) float32."""
     import numpy as np
-    n = len(As)
-    lens = [len(v) for v in (nAs, Bs, nBs, matches)]
-    As, Bs = ([np.ascontiguousarray(v, dtype=np.float32) for v in vs] for vs in (As, Bs))
-    matches = [np.ascontiguousarray(v, dtype=np.int32) for v in matches]
-    capA, capB = _mutual_caps(n, lens, As, Bs, matches, capA, capB)
-    nA = np.array([int(v) for v in nAs], np.int32)
-    nB = np.array([int(v) for v in nBs], np.int32)
-    result = np.zeros((n, capA), np.int32)
-    count = np.zeros(n, np.int32)
-    fwd = np.zeros((n, capA), np.float32) if want_distance else None
-    arr = lambda vals: (C.c_void_p * n)(*[v.ctypes.data for v in vals])
-    _check(lib().nm_sift_match_mutual_host_f32(n, arr(As), arr([nA[k:k + 1] for k in range(n)]), capA, arr(Bs),
-                                               arr([nB[k:k + 1] for k in range(n)]), capB, arr(matches), arr(list(result)),
-                                               count.ctypes.data, arr(list(fwd)) if want_distance else None),
+    n = _pair_count(As, nAs, Bs, nBs, matches)
+    As, Bs = (_pair_host_arrays(vs, np.float32, flat=False) for vs in (As, Bs))
+    matches = _pair_host_arrays(matches, np.int32, flat=False)
+    capA, capB = _mutual_caps(As, Bs, matches, capA, capB)
+    nA, nB = _pair_host_sizes(nAs), _pair_host_sizes(nBs)
+    result, count, fwd = _pair_host_match_out(n, capA, want_distance)
+    arr = _pair_host_table
+    _check(lib().nm_sift_match_mutual_host_f32(n, arr(As), arr(nA), capA, arr(Bs), arr(nB), capB, arr(matches),
+                                               arr(list(result)), _pair_host_ptr(count), arr(list(fwd)) if want_distance else None),
            "nm_sift_match_mutual_host_f32")
     return (result, count) + ((fwd,) if want_distance else ())
 

@@ -14,6 +14,7 @@
 
 #include "nm_common.hpp"
 #include "nm_match_guided_math.hpp"
+#include "nm_pair_batch.hpp"
 #include "../../include/nm_abi.h"
 
 #ifndef NMG_LIST
@@ -44,10 +45,6 @@ struct GdArgs {                            // 10 x 32 pointers: 2.5 KB of the 4 
     float *best[SLOTS];                    // all NULL without a best_distance table
 };
 static_assert(sizeof(GdArgs) + 96 < 4096, "guided-match kernel arguments exceed 4 KB");
-
-struct CtArgs {
-    const int *result[NM_MATCH_GUIDED_MAX_BATCH];
-};
 
 __global__ __launch_bounds__(TB) void match_guided_kernel(const GdArgs a, int first, int n, int capA, int capB,
                                                           const float *__restrict__ H, const int *__restrict__ status_in,
@@ -123,25 +120,6 @@ __global__ __launch_bounds__(TB) void match_guided_kernel(const GdArgs a, int fi
     }
 }
 
-// count[k] = entries >= 0 among the capA results of pair k: integer sums, one workgroup per pair
-__global__ __launch_bounds__(TB) void match_guided_count_kernel(const CtArgs a, int capA, int *__restrict__ count)
-{
-    __shared__ int part[TB / 64];
-    const int k = blockIdx.x, tid = threadIdx.x;
-    const int *__restrict__ res = a.result[k];
-    int c = 0;
-    for (int i = tid; i < capA; i += TB) c += res[i] >= 0 ? 1 : 0;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) c += __shfl_xor(c, d);
-    if ((tid & 63) == 0) part[tid >> 6] = c;
-    __syncthreads();
-    if (tid == 0) {
-        int t = 0;
-        for (int w = 0; w < TB / 64; ++w) t += part[w];
-        count[k] = t;
-    }
-}
-
 // ---- the host twin: the same functions, rows and candidates walked serially ----
 void host_guided_pair(const float *A, const float *ax, const float *ay, int nA, int capA, const float *B, const float *bx,
                       const float *by, int nB, const float *H, int status_in, float radius2, float ambiguity,
@@ -171,14 +149,9 @@ bool gd_args_ok(int n, const float *const *A, const float *const *ax, const floa
                 const float *H, float radius2, float ambiguity, float max_distance, int *const *result, const int *count,
                 float *const *best)
 {
-    if (n < 1 || n > NM_MATCH_GUIDED_MAX_BATCH || capA < 1 || capA >= (1 << 22) || capB < 1 || capB >= (1 << 22) ||
-        !std::isfinite(radius2) || !std::isfinite(ambiguity) || std::isnan(max_distance))
-        return false;
-    if (!A || !ax || !ay || !nA || !B || !bx || !by || !nB || !H || !result || !count) return false;
-    for (int k = 0; k < n; ++k)
-        if (!A[k] || !ax[k] || !ay[k] || !nA[k] || !B[k] || !bx[k] || !by[k] || !nB[k] || !result[k] || (best && !best[k]))
-            return false;
-    return true;
+    if (!std::isfinite(radius2) || !std::isfinite(ambiguity) || std::isnan(max_distance)) return false;
+    return nmp::range_ok(n, capA) && nmp::cap_ok(capB) &&
+           nmp::tables_ok(n, {A, ax, ay, nA, B, bx, by, nB, result}, {best}, {H, count});
 }
 
 }  // namespace
@@ -193,29 +166,21 @@ extern "C" int nm_sift_match_guided_batch_dev_f32(int n, const float *const *A, 
     if (!gd_args_ok(n, A, ax, ay, d_nA, capA, B, bx, by, d_nB, capB, H, radius2, ambiguity, max_distance, result, count,
                     best_distance))
         return (int)hipErrorInvalidValue;
-    for (int first = 0; first < NM_MATCH_GUIDED_MAX_BATCH; first += SLOTS) {
+    for (int first = 0; first < nmp::MAX_BATCH; first += SLOTS) {
         GdArgs a;
-        for (int s = 0; s < SLOTS; ++s) {
-            const int k = first + s;
-            const bool on = k < n;
-            a.A[s] = on ? A[k] : nullptr; a.ax[s] = on ? ax[k] : nullptr; a.ay[s] = on ? ay[k] : nullptr;
-            a.d_nA[s] = on ? d_nA[k] : nullptr;
-            a.B[s] = on ? B[k] : nullptr; a.bx[s] = on ? bx[k] : nullptr; a.by[s] = on ? by[k] : nullptr;
-            a.d_nB[s] = on ? d_nB[k] : nullptr;
-            a.result[s] = on ? result[k] : nullptr;
-            a.best[s] = (on && best_distance) ? best_distance[k] : nullptr;
-        }
+        nmp::fill_slots(a.A, A, first, n); nmp::fill_slots(a.ax, ax, first, n); nmp::fill_slots(a.ay, ay, first, n);
+        nmp::fill_slots(a.d_nA, d_nA, first, n);
+        nmp::fill_slots(a.B, B, first, n); nmp::fill_slots(a.bx, bx, first, n); nmp::fill_slots(a.by, by, first, n);
+        nmp::fill_slots(a.d_nB, d_nB, first, n);
+        nmp::fill_slots(a.result, result, first, n);
+        nmp::fill_slots(a.best, best_distance, first, n);
         const int pairs = n - first < 0 ? 0 : (n - first > SLOTS ? SLOTS : n - first);
         const dim3 grid = pairs ? dim3(nm_divup(capA, TB), pairs) : dim3(1, 1);
         hipLaunchKernelGGL(match_guided_kernel, grid, dim3(TB), 0, nm_stream(stream), a, first, n, capA, capB, H, status_in,
                            radius2, ambiguity, max_distance);
         NM_LAUNCH_CHECK();
     }
-    CtArgs c;
-    for (int k = 0; k < NM_MATCH_GUIDED_MAX_BATCH; ++k) c.result[k] = k < n ? result[k] : nullptr;
-    hipLaunchKernelGGL(match_guided_count_kernel, dim3(n), dim3(TB), 0, nm_stream(stream), c, capA, count);
-    NM_LAUNCH_CHECK();
-    return 0;
+    return nmp::launch_pair_count(n, result, capA, count, nm_stream(stream));
 }
 
 extern "C" int nm_sift_match_guided_host_f32(int n, const float *const *A, const float *const *ax, const float *const *ay,

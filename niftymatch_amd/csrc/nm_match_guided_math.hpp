@@ -8,22 +8,18 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "nm_pair_batch.hpp"
+
 namespace nmg {
+
+using nmp::clip;
+using nmp::finite9;
 
 struct Scan {
     float min1, min2;
     int idx;
     int seen;                               // gated candidates met so far (0 / 1)
 };
-
-__host__ __device__ __forceinline__ bool finite9(const float H[9])
-{
-    bool ok = true;
-    for (int q = 0; q < 9; ++q) ok = ok && __builtin_isfinite(H[q]);
-    return ok;
-}
-
-__host__ __device__ __forceinline__ int clip(int v, int cap) { return v < 0 ? 0 : (v > cap ? cap : v); }
 
 /* Where H sends (ax, ay): the first half of nmr_is_inlier */
 __host__ __device__ __forceinline__ void project(const float H[9], float ax, float ay, float &px, float &py)

@@ -19,6 +19,7 @@
 // counters). The arithmetic is nm_match_mutual_math.hpp, shared with the host twin below: both agree bit for bit.
 #include "nm_common.hpp"
 #include "nm_match_mutual_math.hpp"
+#include "nm_pair_batch.hpp"
 #include "../../include/nm_abi.h"
 
 namespace {
@@ -46,10 +47,6 @@ struct ScArgs {
     const int *d_nA[NM_MATCH_MUTUAL_MAX_BATCH];
     const float *B[NM_MATCH_MUTUAL_MAX_BATCH];
     int *result[NM_MATCH_MUTUAL_MAX_BATCH];
-};
-
-struct CtArgs {
-    const int *result[NM_MATCH_MUTUAL_MAX_BATCH];
 };
 
 __host__ __device__ inline size_t cap_rows(int capA) { return ((size_t)capA + 63) / 64 * 64; }
@@ -193,25 +190,6 @@ __global__ __launch_bounds__(TB) void match_mutual_scan_kernel(const ScArgs a, i
 #endif
 }
 
-// count[k] = entries >= 0 among the capA results of pair k: integer sums, one workgroup per pair
-__global__ __launch_bounds__(TB) void match_mutual_count_kernel(const CtArgs a, int capA, int *__restrict__ count)
-{
-    __shared__ int part[TB / 64];
-    const int k = blockIdx.x, tid = threadIdx.x;
-    const int *__restrict__ res = a.result[k];
-    int c = 0;
-    for (int i = tid; i < capA; i += TB) c += res[i] >= 0 ? 1 : 0;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) c += __shfl_xor(c, d);
-    if ((tid & 63) == 0) part[tid >> 6] = c;
-    __syncthreads();
-    if (tid == 0) {
-        int t = 0;
-        for (int w = 0; w < TB / 64; ++w) t += part[w];
-        count[k] = t;
-    }
-}
-
 // ---- the host twin: the same functions, claims and rival rows walked serially ----
 void host_mutual_pair(const float *A, int nA, int capA, const float *B, int nB, const int *matches, int *result, int *count,
                       float *fwd)
@@ -239,18 +217,14 @@ void host_mutual_pair(const float *A, int nA, int capA, const float *B, int nB, 
 bool mu_args_ok(int n, const float *const *A, const int *const *nA, int capA, const float *const *B, const int *const *nB,
                 int capB, const int *const *matches, int *const *result, const int *count, float *const *fwd)
 {
-    if (n < 1 || n > NM_MATCH_MUTUAL_MAX_BATCH || capA < 1 || capA >= (1 << 22) || capB < 1 || capB >= (1 << 22)) return false;
-    if (!A || !nA || !B || !nB || !matches || !result || !count) return false;
-    for (int k = 0; k < n; ++k)
-        if (!A[k] || !nA[k] || !B[k] || !nB[k] || !matches[k] || !result[k] || (fwd && !fwd[k])) return false;
-    return true;
+    return nmp::range_ok(n, capA) && nmp::cap_ok(capB) && nmp::tables_ok(n, {A, nA, B, nB, matches, result}, {fwd}, {count});
 }
 
 }  // namespace
 
 extern "C" size_t nm_sift_match_mutual_workspace_bytes(int n, int capA)
 {
-    if (n < 1 || n > NM_MATCH_MUTUAL_MAX_BATCH || capA < 1 || capA >= (1 << 22)) return 0;
+    if (!nmp::range_ok(n, capA)) return 0;
     return HEADER + (size_t)n * 3 * cap_rows(capA) * sizeof(int);
 }
 
@@ -263,26 +237,17 @@ extern "C" int nm_sift_match_mutual_batch_dev_f32(int n, const float *const *A, 
         return (int)hipErrorInvalidValue;
     ClArgs c;
     ScArgs s;
-    CtArgs t;
-    for (int k = 0; k < NM_MATCH_MUTUAL_MAX_BATCH; ++k) {
-        const bool on = k < n;
-        c.A[k] = s.A[k] = on ? A[k] : nullptr;
-        c.d_nA[k] = s.d_nA[k] = on ? d_nA[k] : nullptr;
-        c.B[k] = s.B[k] = on ? B[k] : nullptr;
-        c.d_nB[k] = on ? d_nB[k] : nullptr;
-        c.matches[k] = on ? matches[k] : nullptr;
-        c.result[k] = s.result[k] = on ? result[k] : nullptr;
-        t.result[k] = on ? result[k] : nullptr;
-        c.fwd[k] = (on && forward_distance) ? forward_distance[k] : nullptr;
-    }
+    nmp::fill_slots(c.A, A, 0, n); nmp::fill_slots(c.d_nA, d_nA, 0, n); nmp::fill_slots(c.B, B, 0, n);
+    nmp::fill_slots(c.d_nB, d_nB, 0, n); nmp::fill_slots(c.matches, matches, 0, n); nmp::fill_slots(c.result, result, 0, n);
+    nmp::fill_slots(c.fwd, forward_distance, 0, n);
+    nmp::fill_slots(s.A, A, 0, n); nmp::fill_slots(s.d_nA, d_nA, 0, n); nmp::fill_slots(s.B, B, 0, n);
+    nmp::fill_slots(s.result, result, 0, n);
     const int tiles = nm_divup(capA, TB);
     hipLaunchKernelGGL(match_mutual_claims_kernel, dim3(tiles, n), dim3(TB), 0, nm_stream(stream), c, capA, capB, workspace);
     NM_LAUNCH_CHECK();
     hipLaunchKernelGGL(match_mutual_scan_kernel, dim3(tiles, SPLIT, n), dim3(TB), 0, nm_stream(stream), s, capA, workspace);
     NM_LAUNCH_CHECK();
-    hipLaunchKernelGGL(match_mutual_count_kernel, dim3(n), dim3(TB), 0, nm_stream(stream), t, capA, count);
-    NM_LAUNCH_CHECK();
-    return 0;
+    return nmp::launch_pair_count(n, result, capA, count, nm_stream(stream));
 }
 
 extern "C" int nm_sift_match_mutual_host_f32(int n, const float *const *A, const int *const *nA, int capA,

@@ -10,13 +10,14 @@
 #include <hip/hip_runtime.h>
 
 #include "nm_match_guided_math.hpp"
+#include "nm_pair_batch.hpp"
 
 namespace nmm {
 
 constexpr int NMM_CHUNK = 16;                       // dimensions between two looks at the partial sum
 constexpr int NMM_CHUNKS = 128 / NMM_CHUNK;
 
-using nmg::clip;
+using nmp::clip;
 
 /* Row i claims column j = matches[i]: any value outside [0, nB) is no claim */
 __host__ __device__ __forceinline__ bool is_claim(int j, int nB) { return j >= 0 && j < nB; }

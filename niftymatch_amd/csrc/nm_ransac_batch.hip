@@ -15,6 +15,7 @@
 #include <cmath>
 
 #include "nm_common.hpp"
+#include "nm_pair_batch.hpp"
 #include "nm_ransac_math.hpp"
 #include "../../include/nm_abi.h"
 
@@ -60,24 +61,15 @@ inline RbLayout rb_layout(int n, int capA, int iterations)
     return L;
 }
 
-struct RbPrepArgs {                        // 6 x 64 pointers: 3 KB of the 4 KB of kernel arguments
-    const float *sx[NM_RANSAC_MAX_BATCH];
-    const float *sy[NM_RANSAC_MAX_BATCH];
-    const float *dx[NM_RANSAC_MAX_BATCH];
-    const float *dy[NM_RANSAC_MAX_BATCH];
-    const int *matches[NM_RANSAC_MAX_BATCH];
-    const int *d_nA[NM_RANSAC_MAX_BATCH];
-};
-static_assert(sizeof(RbPrepArgs) + 64 < 4096, "prep kernel arguments exceed 4 KB");
+static_assert(sizeof(nmp::PointTables) + 64 < 4096, "prep kernel arguments exceed 4 KB");
 
-__global__ __launch_bounds__(RB_PREP_THREADS) void ransac_batch_prep_kernel(const RbPrepArgs a, int capA,
+__global__ __launch_bounds__(RB_PREP_THREADS) void ransac_batch_prep_kernel(const nmp::PointTables a, int capA,
                                                                             RbHeader *__restrict__ hdr,
                                                                             float4 *__restrict__ pts)
 {
     __shared__ int s_cnt[RB_PREP_THREADS / 64];
     const int k = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    int nA = *a.d_nA[k];
-    nA = nA < 0 ? 0 : (nA > capA ? capA : nA);
+    const int nA = nmp::clip(*a.d_nA[k], capA);
     const float *__restrict__ sx = a.sx[k];
     const float *__restrict__ sy = a.sy[k];
     const float *__restrict__ dx = a.dx[k];
@@ -231,9 +223,7 @@ __global__ __launch_bounds__(64) void ransac_batch_finalize_kernel(int model, in
 
 extern "C" size_t nm_ransac_batch_dev_workspace_bytes(int n, int capA, int iterations)
 {
-    if (n < 1 || n > NM_RANSAC_MAX_BATCH || capA < 1 || capA >= (1 << 22) || iterations < 1 ||
-        iterations > NM_RANSAC_MAX_ITERATIONS)
-        return 0;
+    if (!nmp::range_ok(n, capA) || iterations < 1 || iterations > NM_RANSAC_MAX_ITERATIONS) return 0;
     return rb_layout(n, capA, iterations).total;
 }
 
@@ -252,25 +242,16 @@ extern "C" int nm_ransac_batch_dev_f32(int model, int n, const float *const *src
                                        int *best_inliers, int *position, int *status, float *homographies,
                                        int *inliers, void *workspace, void *stream)
 {
-    if (model < 0 || model > 2 || n < 1 || n > NM_RANSAC_MAX_BATCH || iterations < 1 ||
-        iterations > NM_RANSAC_MAX_ITERATIONS || capA < 1 || capA >= (1 << 22) || !std::isfinite(inlier_threshold))
+    if (model < 0 || model > 2 || iterations < 1 || iterations > NM_RANSAC_MAX_ITERATIONS || !std::isfinite(inlier_threshold))
         return (int)hipErrorInvalidValue;
-    if (!src_x || !src_y || !d_nA || !dst_x || !dst_y || !matches || !seeds || !H_best || !best_inliers || !position ||
-        !status || !workspace)
+    if (!nmp::range_ok(n, capA) ||
+        !nmp::tables_ok(n, {src_x, src_y, d_nA, dst_x, dst_y, matches}, {},
+                        {seeds, H_best, best_inliers, position, status, workspace}))
         return (int)hipErrorInvalidValue;
-    RbPrepArgs a;
+    nmp::PointTables a;
+    a.fill(n, src_x, src_y, dst_x, dst_y, matches, d_nA);
     RbSeeds sd;
-    for (int k = 0; k < n; ++k) {
-        if (!src_x[k] || !src_y[k] || !d_nA[k] || !dst_x[k] || !dst_y[k] || !matches[k]) return (int)hipErrorInvalidValue;
-        a.sx[k] = src_x[k]; a.sy[k] = src_y[k]; a.dx[k] = dst_x[k]; a.dy[k] = dst_y[k];
-        a.matches[k] = matches[k]; a.d_nA[k] = d_nA[k];
-        sd.seed[k] = seeds[k];
-    }
-    for (int k = n; k < NM_RANSAC_MAX_BATCH; ++k) {
-        a.sx[k] = a.sy[k] = a.dx[k] = a.dy[k] = nullptr;
-        a.matches[k] = a.d_nA[k] = nullptr;
-        sd.seed[k] = 0;
-    }
+    for (int k = 0; k < nmp::MAX_BATCH; ++k) sd.seed[k] = k < n ? seeds[k] : 0;
     const RbLayout L = rb_layout(n, capA, iterations);
     char *ws = static_cast<char *>(workspace);
     RbHeader *hdr = reinterpret_cast<RbHeader *>(ws + L.hdr);

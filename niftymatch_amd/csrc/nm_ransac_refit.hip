@@ -11,6 +11,7 @@
 
 #include "nm_common.hpp"
 #include "nm_ransac_refit_math.hpp"
+#include "nm_pair_batch.hpp"
 #include "../../include/nm_abi.h"
 
 namespace {
@@ -19,15 +20,7 @@ using namespace nmf;
 
 static_assert(NM_RANSAC_REFIT_MAX_ROUNDS == 4, "header and kernel disagree");
 
-struct RfArgs {                            // 6 x 64 pointers: 3 KB of the 4 KB of kernel arguments
-    const float *sx[NM_RANSAC_MAX_BATCH];
-    const float *sy[NM_RANSAC_MAX_BATCH];
-    const float *dx[NM_RANSAC_MAX_BATCH];
-    const float *dy[NM_RANSAC_MAX_BATCH];
-    const int *matches[NM_RANSAC_MAX_BATCH];
-    const int *d_nA[NM_RANSAC_MAX_BATCH];
-};
-static_assert(sizeof(RfArgs) + 96 < 4096, "refit kernel arguments exceed 4 KB");
+static_assert(sizeof(nmp::PointTables) + 96 < 4096, "refit kernel arguments exceed 4 KB");
 
 struct RfShared {
     double part[WAVES][NACC];
@@ -148,7 +141,7 @@ __device__ void solve_homography(const double *prm, RfShared &sh)
 }
 
 template <int MODEL>
-__global__ __launch_bounds__(LANES) void ransac_refit_kernel(const RfArgs a, int capA, float thr, int rounds,
+__global__ __launch_bounds__(LANES) void ransac_refit_kernel(const nmp::PointTables a, int capA, float thr, int rounds,
                                                              const float *H_in,
                                                              const int *__restrict__ status_in,
                                                              float *H_out, int *__restrict__ count_out,
@@ -173,8 +166,7 @@ __global__ __launch_bounds__(LANES) void ransac_refit_kernel(const RfArgs a, int
     }
     Pair P;
     P.sx = a.sx[k]; P.sy = a.sy[k]; P.dx = a.dx[k]; P.dy = a.dy[k]; P.mt = a.matches[k];
-    int nA = *a.d_nA[k];
-    P.nA = nA < 0 ? 0 : (nA > capA ? capA : nA);
+    P.nA = clip(*a.d_nA[k], capA);
     double sums[5];
     pass<PASS_SUMS>(P, H, thr, nullptr, sh, sums);
     int done = 0;
@@ -348,14 +340,9 @@ bool rf_args_ok(int model, int n, const float *const *src_x, const float *const 
                 const float *const *dst_x, const float *const *dst_y, const int *const *matches, const float *H_in,
                 float thr, int rounds, const float *H_out, const int *count, const int *status, const int *rounds_done)
 {
-    if (model < 0 || model > 2 || n < 1 || n > NM_RANSAC_MAX_BATCH || rounds < 0 || rounds > NM_RANSAC_REFIT_MAX_ROUNDS ||
-        capA < 1 || capA >= (1 << 22) || !std::isfinite(thr))
-        return false;
-    if (!src_x || !src_y || !d_nA || !dst_x || !dst_y || !matches || !H_in || !H_out || !count || !status || !rounds_done)
-        return false;
-    for (int k = 0; k < n; ++k)
-        if (!src_x[k] || !src_y[k] || !d_nA[k] || !dst_x[k] || !dst_y[k] || !matches[k]) return false;
-    return true;
+    if (model < 0 || model > 2 || rounds < 0 || rounds > NM_RANSAC_REFIT_MAX_ROUNDS || !std::isfinite(thr)) return false;
+    return nmp::range_ok(n, capA) && nmp::tables_ok(n, {src_x, src_y, d_nA, dst_x, dst_y, matches}, {},
+                                                    {H_in, H_out, count, status, rounds_done});
 }
 
 }  // namespace
@@ -370,12 +357,8 @@ extern "C" int nm_ransac_refit_batch_dev_f32(int model, int n, const float *cons
     if (!rf_args_ok(model, n, src_x, src_y, d_nA, capA, dst_x, dst_y, matches, H_in, inlier_threshold, rounds, H_out, count,
                     status, rounds_done))
         return (int)hipErrorInvalidValue;
-    RfArgs a;
-    for (int k = 0; k < NM_RANSAC_MAX_BATCH; ++k) {
-        a.sx[k] = k < n ? src_x[k] : nullptr; a.sy[k] = k < n ? src_y[k] : nullptr;
-        a.dx[k] = k < n ? dst_x[k] : nullptr; a.dy[k] = k < n ? dst_y[k] : nullptr;
-        a.matches[k] = k < n ? matches[k] : nullptr; a.d_nA[k] = k < n ? d_nA[k] : nullptr;
-    }
+    nmp::PointTables a;
+    a.fill(n, src_x, src_y, dst_x, dst_y, matches, d_nA);
     const auto kernel = model == 0 ? ransac_refit_kernel<0> : model == 1 ? ransac_refit_kernel<1> : ransac_refit_kernel<2>;
     hipLaunchKernelGGL(kernel, dim3(n), dim3(LANES), 0, nm_stream(stream), a, capA, inlier_threshold, rounds, H_in,
                        status_in, H_out, count, status, rounds_done, mask, rms);
@@ -395,8 +378,7 @@ extern "C" int nm_ransac_refit_host_f32(int model, int n, const float *const *sr
     for (int k = 0; k < n; ++k) {
         Pair P;
         P.sx = src_x[k]; P.sy = src_y[k]; P.dx = dst_x[k]; P.dy = dst_y[k]; P.mt = matches[k];
-        const int v = *nA[k];
-        P.nA = v < 0 ? 0 : (v > capA ? capA : v);
+        P.nA = clip(*nA[k], capA);
         host_refit_pair(model, P, capA, inlier_threshold, rounds, H_in + 9 * k, status_in ? status_in[k] : 1, H_out + 9 * k,
                         count + k, status + k, rounds_done + k, mask ? mask + (size_t)k * capA : nullptr, rms ? rms + k : nullptr);
     }

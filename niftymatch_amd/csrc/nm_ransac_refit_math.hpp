@@ -9,9 +9,13 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "nm_pair_batch.hpp"
 #include "nm_ransac_math.hpp"
 
 namespace nmf {
+
+using nmp::clip;
+using nmp::finite9;
 
 constexpr int LANES = 512;                  // virtual lanes of the summation order = threads of the device workgroup
 constexpr int WAVES = LANES / 64;
@@ -45,13 +49,6 @@ __host__ __device__ __forceinline__ bool is_inlier(const float H[9], float sx, f
     const float ex = dx - x, ey = dy - y;
     return __builtin_fmaf(ex, ex, ey * ey) < thr;
 #endif
-}
-
-__host__ __device__ __forceinline__ bool finite9(const float H[9])
-{
-    bool ok = true;
-    for (int q = 0; q < 9; ++q) ok = ok && __builtin_isfinite(H[q]);
-    return ok;
 }
 
 /* Row i of the pair when it is a valid row (RANSAC's rule) and an inlier of H */
