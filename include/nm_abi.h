@@ -144,10 +144,12 @@ NM_API int nm_convolve_f32(float *result, const float *image, float *buffer, int
 #define NM_CONV_ROUTE_INVALID 5    /* the call is rejected */
 NM_API int nm_conv_route_of(int width, int height, int radius, int has_result, int has_buffer, int has_dog, int has_grad,
                             unsigned image_low4, unsigned out_low4);
-/* downsample_by_2<float> (kernels/downsample.h:21-24, downsample.cu:20-29). */
+/* downsample_by_2<float> (kernels/downsample.h:21-24, downsample.cu:20-29): the one-plane case of the frame driver's batched
+ * decimation launch. */
 NM_API int nm_downsample2_f32(float *result, int result_width, int result_height, const float *source,
                               int source_width, int source_height, void *stream);
-/* subtract<float> (kernels/cudamath.h:56-60, cudamath.cu:57-67): C = A - B. */
+/* subtract<float> (kernels/cudamath.h:56-60, cudamath.cu:57-67): C = A - B. The one-plane case of nm_subtract_batch_f32's
+ * launch (at most 4096 workgroups; the batch: 2048 per plane). */
 NM_API int nm_subtract_f32(const float *A, const float *B, float *C, int width, int height, void *stream);
 /* gradient<float> (kernels/cudamath.h:71-75, cudamath.cu:72-80): result is float2 (magnitude, angle in (0,2pi]).
  * Deviation: the 1-pixel border, which the reference never writes, is written as (0,0).            */
@@ -176,7 +178,8 @@ NM_API int nm_find_keypoints_masked_f32(const float *current, const float *mask,
                                         int num_dogs, int dog, float *result, void *stream);
 /* PyramidData::gpu_collate_keypoints_for_level's thrust::copy_if (sift/pyramidata.cu:84-88): stable compaction
  * of the entries with w >= 0 among the first num_pixels of `dense` into `out`; the count is written to the
- * DEVICE int *d_count. workspace: nm_compact_workspace_bytes(num_pixels) bytes of device scratch.               */
+ * DEVICE int *d_count. workspace: nm_compact_workspace_bytes(num_pixels) bytes of device scratch. NULL dense, out,
+ * d_count or workspace: hipErrorInvalidValue (num_pixels <= 0 only needs d_count), as nm_compact_keypoints3.        */
 NM_API size_t nm_compact_workspace_bytes(int num_pixels);
 NM_API int nm_compact_keypoints(const float *dense, int num_pixels, float *out, int *d_count, void *workspace,
                                 void *stream);
@@ -225,10 +228,11 @@ NM_API int nm_compact_keypoints3(const float *const dense[3], int num_pixels, fl
 
 /* ---- orientation + descriptor ---- */
 /* detect_orientations (kernels/orientation.h:19-24, orientation.cu:219-230). `result` float2 per keypoint,
- * pre-filled with (-1,-1) by the caller (pyramidata.cu:90).                                                     */
+ * pre-filled with (-1,-1) by the caller (pyramidata.cu:90): only the peaks found are written (a kernel of its own; the
+ * *_levels launches below write -1 themselves).                                                                    */
 NM_API int nm_detect_orientations(const float *key_pts, const float *grad, int num_pts, int octave_width,
                                   int octave_height, float gauss_factor, float xper, float *result, void *stream);
-/* compute_sift_descriptors (kernels/descriptor.h:25-30, descriptor.cu:243-255). */
+/* compute_sift_descriptors (kernels/descriptor.h:25-30, descriptor.cu:243-255): the one-list case of the *_levels launch. */
 NM_API int nm_compute_sift_descriptors(const float *key_pts, const float *orients, const float *grad, int num_pts,
                                        int octave_width, int octave_height, int num_dogs, float xper, float *desc,
                                        float *x, float *y, void *stream);

@@ -442,7 +442,8 @@ __device__ __forceinline__ void describe_wave(const float4 kp, const float angle
     desc_run(d, desc, xp, yp, part);
 }
 
-// ---- API kernels (one octave, one level list per launch) ----
+// ---- API kernel: the orientations of one level list (the level-list kernel below measured 1.0 us slower on a 4.5k list:
+//      profiles/r11_a_single_forms_alternation.txt) ----
 __global__ __launch_bounds__(256) void orientations_kernel(const float4 *__restrict__ key_pts,
                                                           const float2 *__restrict__ grad, int num_pts, int ow, int oh,
                                                           float gauss_factor, float xper, float2 *__restrict__ result)
@@ -459,19 +460,8 @@ __global__ __launch_bounds__(256) void orientations_kernel(const float4 *__restr
     }
 }
 
-__global__ __launch_bounds__(64) void descriptors_kernel(const float4 *__restrict__ key_pts,
-                                                        const float2 *__restrict__ orients,
-                                                        const float2 *__restrict__ grad, int num_pts, int ow, int oh,
-                                                        int num_dogs, float xper, float *__restrict__ desc,
-                                                        float *__restrict__ xp, float *__restrict__ yp)
-{
-    __shared__ __attribute__((aligned(16))) float part[DESC_LDS];
-    for (int pt = blockIdx.x; pt < num_pts; pt += gridDim.x)
-        describe_wave(key_pts[pt], orients[pt].x, grad, ow, oh, num_dogs, xper, desc + (size_t)pt * 128, xp + pt,
-                      yp + pt, part);
-}
-
-// ---- API kernels, up to 3 level lists of one octave per launch (compute_orientations / compute_descriptors) ----
+// ---- API kernels: up to 3 level lists of one octave per launch (compute_orientations / compute_descriptors);
+//      nm_compute_sift_descriptors is the descriptor launch with n_levels = 1 ----
 struct NmLevelLists {
     const float4 *key_pts[3];
     float2 *orients[3];
@@ -755,6 +745,41 @@ int nm_launch_frame_describe(const NmDescribeArgs &a, hipStream_t stream)
     return 0;
 }
 
+// The level lists of an entry point: key_pts / orients of n_levels (1..3) lists, and the per-level outputs of the descriptor
+// stage where the entry has them. num_pts: the host counts, or NULL for the device-sized forms, which add their own fields.
+// Returns the keypoints the host counts add up to (negative counts are none), which size the host-counted grids.
+static int fill_level_lists(NmLevelLists &a, int n_levels, const float *const *key_pts, const float *const *orients,
+                            const int *num_pts, float *const *desc = nullptr, float *const *x = nullptr, float *const *y = nullptr)
+{
+    int sum = 0;
+    a.n_levels = n_levels;
+    for (int l = 0; l < n_levels; ++l) {
+        a.key_pts[l] = reinterpret_cast<const float4 *>(key_pts[l]);
+        a.orients[l] = const_cast<float2 *>(reinterpret_cast<const float2 *>(orients[l]));
+        if (desc) { a.desc[l] = desc[l]; a.x[l] = x[l]; a.y[l] = y[l]; }
+        if (num_pts) { a.num_pts[l] = num_pts[l]; sum += max(num_pts[l], 0); }
+    }
+    return sum;
+}
+
+static int launch_orientations(const NmLevelLists &a, int blocks, const float *grad, int ow, int oh, float gauss_factor,
+                               float xper, void *stream)
+{
+    hipLaunchKernelGGL(orientations_levels_kernel, dim3(blocks), dim3(256), 0, nm_stream(stream), a,
+                       reinterpret_cast<const float2 *>(grad), ow, oh, gauss_factor, xper);
+    NM_LAUNCH_CHECK();
+    return 0;
+}
+
+static int launch_descriptors(const NmLevelLists &a, int blocks, const float *grad, int ow, int oh, int num_dogs, float xper,
+                              void *stream)
+{
+    hipLaunchKernelGGL(descriptors_levels_kernel, dim3(blocks), dim3(64), 0, nm_stream(stream), a,
+                       reinterpret_cast<const float2 *>(grad), ow, oh, num_dogs, xper);
+    NM_LAUNCH_CHECK();
+    return 0;
+}
+
 extern "C" {
 
 int nm_selftest_expw(unsigned long long *d_out, void *stream)
@@ -796,22 +821,9 @@ int nm_detect_orientations_levels(int n_levels, const float *const *key_pts, con
     if (n_levels <= 0) return 0;
     if (n_levels > 3 || !key_pts || !num_pts || !result) return (int)hipErrorInvalidValue;
     NmLevelLists a{};
-    int most = 0;
-    a.n_levels = n_levels;
-    for (int l = 0; l < n_levels; ++l) {
-        a.key_pts[l] = reinterpret_cast<const float4 *>(key_pts[l]);
-        a.orients[l] = reinterpret_cast<float2 *>(result[l]);
-        a.num_pts[l] = num_pts[l];
-        most = max(most, num_pts[l]);
-    }
-    if (most <= 0) return 0;
-    int sum = 0;
-    for (int l = 0; l < n_levels; ++l) sum += num_pts[l] > 0 ? num_pts[l] : 0;
-    hipLaunchKernelGGL(orientations_levels_kernel, dim3(min(nm_divup(sum, 4), 4096)), dim3(256), 0,
-                       nm_stream(stream), a, reinterpret_cast<const float2 *>(grad), octave_width, octave_height,
-                       gauss_factor, xper);
-    NM_LAUNCH_CHECK();
-    return 0;
+    const int sum = fill_level_lists(a, n_levels, key_pts, result, num_pts);
+    if (sum <= 0) return 0;
+    return launch_orientations(a, min(nm_divup(sum, 4), 4096), grad, octave_width, octave_height, gauss_factor, xper, stream);
 }
 
 // The device-sized forms (lazy_count.h): the three level counts are read on the device, nothing comes back to the host except
@@ -823,16 +835,9 @@ int nm_detect_orientations_levels_dev(const float *const *key_pts, const int *d_
 {
     if (!key_pts || !d_counts || !result || max_pts <= 0) return (int)hipErrorInvalidValue;
     NmLevelLists a{};
-    a.n_levels = 3;
-    for (int l = 0; l < 3; ++l) {
-        a.key_pts[l] = reinterpret_cast<const float4 *>(key_pts[l]);
-        a.orients[l] = reinterpret_cast<float2 *>(result[l]);
-    }
+    fill_level_lists(a, 3, key_pts, result, nullptr);
     a.d_counts = d_counts; a.max_pts = max_pts; a.h_counts = h_counts;
-    hipLaunchKernelGGL(orientations_levels_kernel, dim3(min(nm_divup(max_pts, 4), 1024)), dim3(256), 0, nm_stream(stream), a,
-                       reinterpret_cast<const float2 *>(grad), octave_width, octave_height, gauss_factor, xper);
-    NM_LAUNCH_CHECK();
-    return 0;
+    return launch_orientations(a, min(nm_divup(max_pts, 4), 1024), grad, octave_width, octave_height, gauss_factor, xper, stream);
 }
 
 // desc / x / y: the CONTAINER's arrays (slot 0); the running item count is read from d_base_in (NULL: host_base) and the new
@@ -844,18 +849,11 @@ int nm_compute_sift_descriptors_levels_dev(const float *const *key_pts, const fl
 {
     if (!key_pts || !orients || !d_counts || !desc || !x || !y || max_pts <= 0 || capacity <= 0) return (int)hipErrorInvalidValue;
     NmLevelLists a{};
-    a.n_levels = 3;
-    for (int l = 0; l < 3; ++l) {
-        a.key_pts[l] = reinterpret_cast<const float4 *>(key_pts[l]);
-        a.orients[l] = const_cast<float2 *>(reinterpret_cast<const float2 *>(orients[l]));
-    }
+    fill_level_lists(a, 3, key_pts, orients, nullptr);
     a.desc[0] = desc; a.x[0] = x; a.y[0] = y;
     a.d_counts = d_counts; a.max_pts = max_pts; a.d_base_in = d_base_in; a.host_base = host_base; a.capacity = capacity;
     a.d_items_out = d_items_out; a.h_items = h_items;
-    hipLaunchKernelGGL(descriptors_levels_kernel, dim3(min(min(max_pts, capacity), 4096)), dim3(64), 0, nm_stream(stream), a,
-                       reinterpret_cast<const float2 *>(grad), octave_width, octave_height, num_dogs, xper);
-    NM_LAUNCH_CHECK();
-    return 0;
+    return launch_descriptors(a, min(min(max_pts, capacity), 4096), grad, octave_width, octave_height, num_dogs, xper, stream);
 }
 
 // compute_sift_descriptors for up to three level lists of one octave in one launch.
@@ -867,36 +865,18 @@ int nm_compute_sift_descriptors_levels(int n_levels, const float *const *key_pts
     if (n_levels <= 0) return 0;
     if (n_levels > 3 || !key_pts || !orients || !num_pts || !desc || !x || !y) return (int)hipErrorInvalidValue;
     NmLevelLists a{};
-    int most = 0;
-    a.n_levels = n_levels;
-    for (int l = 0; l < n_levels; ++l) {
-        a.key_pts[l] = reinterpret_cast<const float4 *>(key_pts[l]);
-        a.orients[l] = const_cast<float2 *>(reinterpret_cast<const float2 *>(orients[l]));
-        a.desc[l] = desc[l]; a.x[l] = x[l]; a.y[l] = y[l];
-        a.num_pts[l] = num_pts[l];
-        most = max(most, num_pts[l]);
-    }
-    if (most <= 0) return 0;
-    int sum = 0;
-    for (int l = 0; l < n_levels; ++l) sum += num_pts[l] > 0 ? num_pts[l] : 0;
-    hipLaunchKernelGGL(descriptors_levels_kernel, dim3(min(sum, 4096)), dim3(64), 0, nm_stream(stream), a,
-                       reinterpret_cast<const float2 *>(grad), octave_width, octave_height, num_dogs, xper);
-    NM_LAUNCH_CHECK();
-    return 0;
+    const int sum = fill_level_lists(a, n_levels, key_pts, orients, num_pts, desc, x, y);
+    if (sum <= 0) return 0;
+    return launch_descriptors(a, min(sum, 4096), grad, octave_width, octave_height, num_dogs, xper, stream);
 }
 
 int nm_compute_sift_descriptors(const float *key_pts, const float *orients, const float *grad, int num_pts,
                                 int octave_width, int octave_height, int num_dogs, float xper, float *desc, float *x,
                                 float *y, void *stream)
 {
-    if (num_pts <= 0) return 0;
-    const int blocks = min(num_pts, 4096);
-    hipLaunchKernelGGL(descriptors_kernel, dim3(blocks), dim3(64), 0, nm_stream(stream),
-                       reinterpret_cast<const float4 *>(key_pts), reinterpret_cast<const float2 *>(orients),
-                       reinterpret_cast<const float2 *>(grad), num_pts, octave_width, octave_height, num_dogs, xper, desc,
-                       x, y);
-    NM_LAUNCH_CHECK();
-    return 0;
+    NmLevelLists a{};
+    if (fill_level_lists(a, 1, &key_pts, &orients, &num_pts, &desc, &x, &y) <= 0) return 0;
+    return launch_descriptors(a, min(num_pts, 4096), grad, octave_width, octave_height, num_dogs, xper, stream);
 }
 
 }  // extern "C"

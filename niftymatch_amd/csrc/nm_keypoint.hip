@@ -527,7 +527,9 @@ size_t nm_compact_workspace_bytes(int num_pixels)
 int nm_compact_keypoints(const float *dense, int num_pixels, float *out, int *d_count, void *workspace, void *stream)
 {
     hipStream_t st = nm_stream(stream);
-    if (num_pixels <= 0) return (int)hipMemsetAsync(d_count, 0, sizeof(int), st);
+    if (!d_count) return (int)hipErrorInvalidValue;
+    if (num_pixels <= 0) return (int)hipMemsetAsync(d_count, 0, sizeof(int), st);      // (an empty map may have no storage)
+    if (!dense || !out || !workspace) return (int)hipErrorInvalidValue;
     const int nb = nm_divup(num_pixels, 256);
     int *counts = static_cast<int *>(workspace), *offsets = counts + nb;
     hipLaunchKernelGGL(count_valid_kernel, dim3(nb), dim3(256), 0, st, reinterpret_cast<const float4 *>(dense), num_pixels, counts);

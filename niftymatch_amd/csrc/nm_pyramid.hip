@@ -718,14 +718,6 @@ int nm_launch_convolve_batch(const NmConvBatch &b, int width, int height, const 
 }
 
 // ------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void downsample2_kernel(float *__restrict__ result, int rw, int rh,
-                                                         const float *__restrict__ source, int sw)
-{
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x >= rw || y >= rh) return;
-    result[(size_t)y * rw + x] = source[(size_t)(y * 2) * sw + (x * 2)];
-}
-
 __global__ __launch_bounds__(256) void downsample2_batch_kernel(NmPlaneBatch b, int rw, int rh, int sw)
 {
     const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
@@ -745,14 +737,7 @@ int nm_launch_downsample2_batch(const NmPlaneBatch &b, int rw, int rh, int sw, h
     return 0;
 }
 
-__global__ __launch_bounds__(256) void subtract_kernel(const float *__restrict__ A, const float *__restrict__ B,
-                                                      float *__restrict__ C, size_t n)
-{
-    size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    const size_t stride = (size_t)gridDim.x * 256;
-    for (; i < n; i += stride) C[i] = A[i] - B[i];
-}
-
+// C[k] = A[k] - B[k] for the planes k = blockIdx.y of a launch; a single plane is the batch of one (nm_subtract_f32).
 struct NmSubBatch { const float *A[8]; const float *B[8]; float *C[8]; };
 __global__ __launch_bounds__(256) void subtract_batch_kernel(NmSubBatch b, size_t n)
 {
@@ -761,6 +746,16 @@ __global__ __launch_bounds__(256) void subtract_batch_kernel(NmSubBatch b, size_
     size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     const size_t stride = (size_t)gridDim.x * 256;
     for (; i < n; i += stride) C[i] = A[i] - B[i];
+}
+
+// planes: 1..8 filled entries of b; max_blocks: the entry point's cap on the workgroups per plane (grid-stride beyond it).
+static int launch_subtract(const NmSubBatch &b, int planes, size_t npx, int max_blocks, hipStream_t stream)
+{
+    int blocks = (int)((npx + 255) / 256);
+    if (blocks > max_blocks) blocks = max_blocks;
+    hipLaunchKernelGGL(subtract_batch_kernel, dim3(blocks, planes), dim3(256), 0, stream, b, npx);
+    NM_LAUNCH_CHECK();
+    return 0;
 }
 
 // gradient: g = 0.5*sqrt(dx^2+dy^2), theta = mod_2pi(atan2(dy,dx) + 2pi) in (0, 2pi], 0 when g == 0; border = (0,0).
@@ -824,22 +819,18 @@ int nm_convolve_f32(float *result, const float *image, float *buffer, int width,
 int nm_downsample2_f32(float *result, int rw, int rh, const float *source, int sw, int sh, void *stream)
 {
     (void)sh;
-    if (rw <= 0 || rh <= 0) return 0;
-    dim3 grid(nm_divup(rw, 64), nm_divup(rh, 4));
-    hipLaunchKernelGGL(downsample2_kernel, grid, dim3(256), 0, nm_stream(stream), result, rw, rh, source, sw);
-    NM_LAUNCH_CHECK();
-    return 0;
+    NmPlaneBatch b{};
+    b.dst[0] = result; b.src[0] = source; b.n = 1;
+    return nm_launch_downsample2_batch(b, rw, rh, sw, nm_stream(stream));
 }
 
 int nm_subtract_f32(const float *A, const float *B, float *C, int width, int height, void *stream)
 {
-    const size_t n = (size_t)width * height;
-    if (n == 0) return 0;
-    int blocks = (int)((n + 255) / 256);
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(subtract_kernel, dim3(blocks), dim3(256), 0, nm_stream(stream), A, B, C, n);
-    NM_LAUNCH_CHECK();
-    return 0;
+    const size_t npx = (size_t)width * height;
+    if (npx == 0) return 0;
+    NmSubBatch b{};
+    b.A[0] = A; b.B[0] = B; b.C[0] = C;
+    return launch_subtract(b, 1, npx, 4096, nm_stream(stream));
 }
 
 // compute_dog's loop (sift/siftfunctions.cu:42-51) as one launch: C[k] = A[k] - B[k] for n <= 8 planes.
@@ -851,11 +842,7 @@ int nm_subtract_batch_f32(int n, const float *const *A, const float *const *B, f
     if (n > 8 || !A || !B || !C) return (int)hipErrorInvalidValue;
     NmSubBatch b{};
     for (int k = 0; k < n; ++k) { b.A[k] = A[k]; b.B[k] = B[k]; b.C[k] = C[k]; }
-    int blocks = (int)((npx + 255) / 256);
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(subtract_batch_kernel, dim3(blocks, n), dim3(256), 0, nm_stream(stream), b, npx);
-    NM_LAUNCH_CHECK();
-    return 0;
+    return launch_subtract(b, n, npx, 2048, nm_stream(stream));
 }
 
 // compute_gradients' loop (sift/siftfunctions.cu:53-63) as one launch: n <= 3 planes.

@@ -175,14 +175,7 @@ void PyramidData::gpu_collate_keypoints_for_level(int level, int num_pixels)
 void PyramidData::gpu_collate_keypoints_for_octave(int num_pixels, int counts[3], hipStream_t stream)
 {
     _lazy_rec.reset(); _lazy_octave = -1;
-    const float *dense[3];
-    float *out[3];
-    for (int l = 0; l < 3; ++l) {
-        dense[l] = reinterpret_cast<const float *>(_key_pts[l].data());
-        out[l] = reinterpret_cast<float *>(_collated_kpts[l].data());
-    }
-    nm_check(nm_compact_keypoints3(dense, num_pixels, out, _count.data(), _compact_ws.data(), stream),
-             "Keypoint collation failed");
+    gpu_collate_keypoints_for_octave_dev(num_pixels, stream);
     int *host = _host_counts.get();
     nm_check((int)hipMemcpyAsync(host, _count.data(), 3 * sizeof(int), hipMemcpyDeviceToHost, stream), "Keypoint count D2H");
     nm_check((int)hipStreamSynchronize(stream), "Keypoint count D2H");

@@ -305,6 +305,14 @@ void compute_descriptors(PyramidData &pydata, const SiftParams &params, const in
         data._num_items.defer(items);
         return;
     }
+    auto flush = [&]() {                       // one launch for the (at most three) level lists gathered so far
+        if (levels > 0)
+            nm_check(nm_compute_sift_descriptors_levels(levels, kp, ori, n, reinterpret_cast<const float *>(pydata._grad.data()),
+                                                        octave_width, octave_height, params._num_dog_levels, xper, desc, xs,
+                                                        ys, stream),
+                     "SIFT descriptor detection launch failed");
+        levels = 0;
+    };
     for (int i = 0; i < params._num_dog_levels; ++i) {
         if (pydata._orientations[i].size() == 0) break;       // siftfunctions.cu:160
         int num_pts = (int)pydata._orientations[i].size();
@@ -319,17 +327,7 @@ void compute_descriptors(PyramidData &pydata, const SiftParams &params, const in
             n[levels++] = num_pts;
             data._num_items += num_pts;
         }
-        if (levels == 3 || i + 1 == params._num_dog_levels) {
-            nm_check(nm_compute_sift_descriptors_levels(levels, kp, ori, n, reinterpret_cast<const float *>(pydata._grad.data()),
-                                                        octave_width, octave_height, params._num_dog_levels, xper, desc,
-                                                        xs, ys, stream),
-                     "SIFT descriptor detection launch failed");
-            levels = 0;
-        }
+        if (levels == 3) flush();
     }
-    if (levels > 0)
-        nm_check(nm_compute_sift_descriptors_levels(levels, kp, ori, n, reinterpret_cast<const float *>(pydata._grad.data()),
-                                                    octave_width, octave_height, params._num_dog_levels, xper, desc, xs,
-                                                    ys, stream),
-                 "SIFT descriptor detection launch failed");
+    flush();
 }

@@ -1,8 +1,8 @@
 """Every kernel family of csrc/nm_describe.hip against the binary64 model of tests/describe_ref.py, on the cases of
 tests/test_describe_float64.py (the oracle only builds the input planes there; nothing here compares with it).
 
-Families: "api" (orientations_kernel / descriptors_kernel), "levels" (the *_levels launchers with host counts), "levels_dev" (device
-counts; descriptors into container slots) and the frame driver (frame_orient_kernel / frame_desc_kernel, its own test).
+Families: "api" (the one-list entries: orientations_kernel / descriptors_levels_kernel with one level), "levels" (the *_levels
+launchers with host counts), "levels_dev" (device counts; descriptors into container slots) and the frame driver (frame_orient_kernel / frame_desc_kernel, its own test).
 nm_detect_orientations writes found peaks only, so an unset slot keeps the caller's fill; the level launchers write -1 there.
 Descriptor rows that are not processed are left as found by every family. Outputs start as a sentinel."""
 import ctypes as C
@@ -165,8 +165,8 @@ def test_case_d_short_lists(nm, oracle, cuda, length, family):
 
 
 def test_case_d_lists_past_the_grid_caps(nm, oracle, cuda):
-    """One length past each grid cap, where the grid-stride loops run: 16 389 keypoints through orientations_kernel (4 per block,
-    4096 blocks), 4 101 through descriptors_kernel (4096 blocks), 4 101 with max_pts and capacity above it through both
+    """One length past each grid cap, where the grid-stride loops run: 16 389 keypoints through orientations_kernel (4 per
+    block, 4096 blocks), 4 101 through the one-list descriptor entry (4096 blocks), 4 101 with max_pts and capacity above it through both
     *_levels_dev kernels (1024 blocks of 4; 4096 blocks). Case A's list tiled: the model ran once per distinct row."""
     kp, ori, w, h, xper, mo, md = T.case_a(T.TEETH)
     g = T.plane(w, h)

@@ -1,5 +1,7 @@
-"""Timings of the stages either side of the hot path at 1080p / 12k points: element-wise front end,
-warps, RANSAC. Each op is timed over back-to-back launches on one stream."""
+"""Timings of the stages either side of the hot path at 1080p / 12k points: the one-item drop-in entry
+points (a 1080p plane, 4.5k keypoints: the first five rows; --single-forms prints only those), element-wise front end, warps,
+RANSAC. Each op is timed over back-to-back launches on one stream."""
+import ctypes as C
 import os
 import sys
 import time
@@ -26,6 +28,32 @@ def timeit(fn, n=50):
     return (time.perf_counter() - t0) / n * 1e6
 
 
+def single_forms():
+    """The C entry points themselves on preallocated buffers: the time of a launch, not of the wrapper's allocations."""
+    lib, f32 = nm.lib(), torch.float32
+    a, b = torch.rand((H, W), device=dev) * 255, torch.rand((H, W), device=dev) * 255
+    half, diff = torch.empty((H // 2, W // 2), device=dev), torch.empty((H, W), device=dev)
+    print("downsample f32 1080p       %7.1f us" % timeit(lambda: lib.nm_downsample2_f32(half.data_ptr(), W // 2, H // 2, a.data_ptr(), W, H, None), 200))
+    print("subtract 1080p             %7.1f us" % timeit(lambda: lib.nm_subtract_f32(a.data_ptr(), b.data_ptr(), diff.data_ptr(), W, H, None), 200))
+    npts = 4500
+    where = np.sort(rng.choice(W * H, npts, replace=False))
+    kp = np.stack([where % W + 0.25, where // W + 0.25, rng.uniform(1.6, 3.2, npts), rng.integers(0, 3, npts)], 1).astype(np.float32)
+    dense = torch.full((W * H, 4), -1.0, dtype=f32, device=dev)
+    dense[torch.from_numpy(where).to(dev)] = torch.from_numpy(kp).to(dev)
+    kpts, cnt = torch.empty((W * H, 4), dtype=f32, device=dev), torch.zeros(1, dtype=torch.int32, device=dev)
+    ws = torch.empty(lib.nm_compact_workspace_bytes(W * H), dtype=torch.uint8, device=dev)
+    print("compaction 1080p, 4.5k kept%7.1f us" % timeit(lambda: lib.nm_compact_keypoints(dense.data_ptr(), W * H, kpts.data_ptr(), cnt.data_ptr(), ws.data_ptr(), None), 200))
+    assert int(cnt.item()) == npts
+    grad = torch.stack([nm.gradient(torch.rand((H, W), device=dev) * 255) for _ in range(3)]).contiguous()
+    ori = torch.full((npts, 2), -1.0, dtype=f32, device=dev)
+    print("orientations 4.5k          %7.1f us" % timeit(lambda: lib.nm_detect_orientations(kpts.data_ptr(), grad.data_ptr(), npts, W, H, C.c_float(1.5), C.c_float(1.0), ori.data_ptr(), None), 200))
+    desc, xs, ys = torch.empty((npts, 128), dtype=f32, device=dev), torch.empty(npts, dtype=f32, device=dev), torch.empty(npts, dtype=f32, device=dev)
+    print("descriptors 4.5k           %7.1f us" % timeit(lambda: lib.nm_compute_sift_descriptors(kpts.data_ptr(), ori.data_ptr(), grad.data_ptr(), npts, W, H, 3, C.c_float(1.0), desc.data_ptr(), xs.data_ptr(), ys.data_ptr(), None), 200))
+
+
+single_forms()
+if "--single-forms" in sys.argv:
+    sys.exit(0)
 bgra = torch.from_numpy(rng.integers(0, 256, (H, W, 4), dtype=np.uint8)).to(dev)
 plane = torch.rand((H, W), device=dev) * 255
 print("grayscale 1080p            %7.1f us" % timeit(lambda: nm.grayscale(bgra)))
