@@ -673,6 +673,71 @@ NM_API int nm_sift_match_mutual_host_f32(int n, const float *const *A, const int
                                          const int *const *matches, int *const *result, int *count,
                                          float *const *forward_distance);
 
+/* ---- Descriptor finish (no reference counterpart: the reference's descriptors stay raw fp32 histograms, its
+ * normalize_histogram in kernels/descriptor.cu is never called). nm_sift_desc_finish_batch_dev turns the raw rows of
+ * n in [1, NM_DESC_FINISH_MAX_BATCH] frames into the standard SIFT form in ONE launch on `stream` (the frame is a grid
+ * dimension): no allocation, no synchronisation, no host read, so it can be captured into a HIP graph behind the frame
+ * driver. desc, d_num_items, out_f32, out_u8: HOST tables of n device pointers.
+ *   desc[k]         capacity x 128 floats, row-major (an arena's desc);
+ *   d_num_items[k]  DEVICE int, the row count: rows = clip(*d_num_items[k], 0, capacity). Rows at and beyond it are neither
+ *                   read nor written;
+ *   out_f32[k]      capacity x 128 floats, out_u8[k] capacity x 128 unsigned chars. Either table may be NULL, not both;
+ *                   out_f32[k] may be desc[k] (in place). Outputs overlap nothing else.
+ * Per row, all IEEE binary32, fused only where fmaf is written (csrc/nm_desc_finish_math.hpp), v = the 128 elements:
+ *   sum(p): the row is held as 64 pairs, pair l = elements (2 l, 2 l + 1), each with one partial p[l]; then for
+ *     d = 32, 16, 8, 4, 2, 1 in this order every p[l] becomes p[l] + p[l ^ d] (the xor butterfly of a wave with one pair
+ *     per lane); the sum is p[0].
+ *   NM_DESC_L2:
+ *     1. s = sum(fmaf(v[2l+1], v[2l+1], v[2l] * v[2l])).
+ *     2. If s is zero or not finite (it is zero also when every square underflows: elements below about 1e-23), every
+ *        output element of the row is 0 (fp32 +0, code 0).
+ *     3. v = v / sqrtf(s) element by element; v = fminf(v, 0.2f); then steps 1 and 3's division once more on the clipped row.
+ *     4. code = min(255, (int)rintf(512 * v)), round half to even; anything not above zero is code 0.
+ *   NM_DESC_ROOT (RootSIFT): steps 1-3, then t = sum(v[2l] + v[2l+1]), v = sqrtf(v / t) (the row has unit L2 norm), then 4.
+ * The domain is the non-negative histogram the describe stage writes. A negative element keeps its sign through L2 and gets
+ * code 0; RootSIFT makes a NaN of it (code 0).
+ * Returns hipErrorInvalidValue, before anything is launched or dereferenced, for n not in [1, 64], capacity not in
+ * [1, 2^22), a mode other than the two, desc or d_num_items NULL, both output tables NULL, or a NULL among the first n
+ * entries of a given table.
+ * nm_sift_desc_finish_host: the same with every pointer in host memory and no stream, compiled from the same functions:
+ * host and device results are identical bit for bit.                                                                    */
+#define NM_DESC_FINISH_MAX_BATCH 64
+#define NM_DESC_L2 0
+#define NM_DESC_ROOT 1
+NM_API int nm_sift_desc_finish_batch_dev(int n, const float *const *desc, const int *const *d_num_items, int capacity,
+                                         float *const *out_f32, unsigned char *const *out_u8, int mode, void *stream);
+NM_API int nm_sift_desc_finish_host(int n, const float *const *desc, const int *const *num_items, int capacity,
+                                    float *const *out_f32, unsigned char *const *out_u8, int mode);
+
+/* ---- Brute-force matching of unsigned-char descriptors on the i8 matrix cores (no reference counterpart: the reference
+ * matches fp32 rows). n in [1, NM_MATCH_U8_MAX_BATCH] pairs in TWO launches on `stream` whatever n is (row norms, match);
+ * no allocation, no synchronisation, no host read. Pair k (HOST tables of n device pointers):
+ *   A[k] / B[k]        capA x 128 / capB x 128 unsigned chars, row-major, 16-byte aligned (out_u8 of the finish);
+ *   d_nA[k], d_nB[k]   DEVICE ints: nA = clip(*d_nA[k], 0, capA), nB = clip(*d_nB[k], 0, capB). Rows beyond them are never
+ *                      read. A pair with nA <= 0 or nB <= 0 is a no-op;
+ *   result[k]          device, capA ints; entries at and beyond nA are not written.
+ * Semantics: result[k] is what nm_sift_match_f32 writes for the same pair when its inputs are the float copies of the u8
+ * rows and result is pre-filled the same way. In full: d(i, j) = sum over q of (A[i][q] - B[j][q])^2 as an exact integer
+ * (<= 128 * 255^2 < 2^23, so also an exact float); the scan of kernels/match.cu:88-116 runs on those values as floats:
+ * min1 = d(i, 0), index 0, min2 = 2139095040.0f; for j = 1 .. nB - 1 a d < min1 moves min1 to min2 and takes (d, j), else
+ * a d < min2 replaces min2 -- the first minimum wins ties; a row whose min2 is 0 is left unwritten; otherwise
+ * result[i] = (min1 / min2 < ambiguity) ? index : -1 with an fp32 divide. A pair's result depends on that pair's inputs
+ * alone, never on n, the slot or scheduling (no atomics).
+ * workspace: device, 16-byte aligned, nm_sift_match_u8_workspace_bytes(n, capA, capB) bytes (0 for arguments out of
+ * range), no contents expected or preserved.
+ * Returns hipErrorInvalidValue, touching no device memory, for n not in [1, 64], capA or capB not in [1, 2^22), a NULL
+ * table, workspace or entry among the first n of a table, or a descriptor pointer or workspace that is not 16-byte aligned.
+ * nm_sift_match_u8_host: the same with every pointer in host memory (no alignment rule), no workspace and no stream; the
+ * same argument checks and the same last step, results identical to the device entry's.                               */
+#define NM_MATCH_U8_MAX_BATCH 64
+NM_API size_t nm_sift_match_u8_workspace_bytes(int n, int capA, int capB);
+NM_API int nm_sift_match_u8_batch_dev(int n, const unsigned char *const *A, const int *const *d_nA, int capA,
+                                      const unsigned char *const *B, const int *const *d_nB, int capB,
+                                      int *const *result, float ambiguity, void *workspace, void *stream);
+NM_API int nm_sift_match_u8_host(int n, const unsigned char *const *A, const int *const *nA, int capA,
+                                 const unsigned char *const *B, const int *const *nB, int capB, int *const *result,
+                                 float ambiguity);
+
 /* ---- Mosaic plan and batched blend (no reference counterpart: the reference's client places frames on the host and
  * calls transform_blend once per frame). Together with nm_ransac_batch_dev_f32 the chain detect -> match -> RANSAC ->
  * plan -> blend runs on one stream with no host read and can be captured into one HIP graph.

@@ -116,6 +116,11 @@ _SIGNATURES = {
     "nm_sift_match_mutual_workspace_bytes": (_SZ, [_I, _I]),
     "nm_sift_match_mutual_batch_dev_f32": (_I, [_I, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P]),
     "nm_sift_match_mutual_host_f32": (_I, [_I, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P]),
+    "nm_sift_desc_finish_batch_dev": (_I, [_I, _P, _P, _I, _P, _P, _I, _P]),
+    "nm_sift_desc_finish_host": (_I, [_I, _P, _P, _I, _P, _P, _I]),
+    "nm_sift_match_u8_workspace_bytes": (_SZ, [_I, _I, _I]),
+    "nm_sift_match_u8_batch_dev": (_I, [_I, _P, _P, _I, _P, _P, _I, _P, _F, _P, _P]),
+    "nm_sift_match_u8_host": (_I, [_I, _P, _P, _I, _P, _P, _I, _P, _F]),
     "nm_mosaic_plan_f32": (_I, [_I, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "nm_mosaic_plan_host_f32": (_I, [_I, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "nm_transform_blend_batch": (_I, [_P, _I, _I, _P, _I, _P, _I, _I, _P, _I, _P, _I, _P, _P]),
@@ -1096,6 +1101,132 @@ def sift_match_mutual_host(As, nAs, Bs, nBs, matches, capA=None, capB=None, want
                                                arr(list(result)), _pair_host_ptr(count), arr(list(fwd)) if want_distance else None),
            "nm_sift_match_mutual_host_f32")
     return (result, count) + ((fwd,) if want_distance else ())
+
+
+# ---- descriptor finish and the u8 matcher ----
+DESC_L2, DESC_ROOT = 0, 1
+DESC_FINISH_MAX_BATCH = MATCH_U8_MAX_BATCH = _PAIR_MAX_BATCH
+
+
+def _finish_mode(mode):
+    modes = {"l2": DESC_L2, "root": DESC_ROOT, DESC_L2: DESC_L2, DESC_ROOT: DESC_ROOT}
+    if isinstance(mode, bool) or mode not in modes:
+        raise NmError("descriptor finish: mode must be DESC_L2 / 'l2' or DESC_ROOT / 'root', got %r" % (mode,))
+    return modes[mode]
+
+
+def desc_finish_batch_dev(descs, d_counts, mode=DESC_L2, out_f32=None, out_u8=None, capacity=None):
+    """The standard SIFT form of the raw descriptors of n = len(descs) <= DESC_FINISH_MAX_BATCH frames
+    (nm_sift_desc_finish_batch_dev): L2-normalise, clip at 0.2, renormalise, with DESC_ROOT also RootSIFT; one launch on the
+    current stream, no host read. descs: float32 device tensors (rows, 128) (SiftArena.desc), d_counts: int32 DEVICE row
+    counts (SiftArena.num_items). out_f32 / out_u8: None (not wanted), True (new tensors) or a list of n device tensors
+    (capacity, 128) float32 / uint8 to write into; out_f32 may be descs itself (in place). At least one is needed. Rows at
+    and beyond a frame's count are not written (new tensors are zero-filled). u8 = min(255, rint(512 v)). Returns
+    (out_f32, out_u8), None for the one not asked for."""
+    torch = _torch()
+    mode = _finish_mode(mode)
+    f32_given, u8_given = isinstance(out_f32, (list, tuple)), isinstance(out_u8, (list, tuple))
+    n = _pair_count(descs, d_counts, out_f32 if f32_given else None, out_u8 if u8_given else None)
+    _pair_descriptors(descs, out_f32 if f32_given else (), out_u8 if u8_given else ())
+    if (out_f32 is None or out_f32 is False) and (out_u8 is None or out_u8 is False):
+        raise NmError("descriptor finish: ask for out_f32, out_u8 or both")
+    capacity = _pair_cap(capacity, list(descs) + (list(out_f32) if f32_given else []) + (list(out_u8) if u8_given else []))
+    device = _pair_device(list(descs) + list(d_counts) + (list(out_f32) if f32_given else []) +
+                          (list(out_u8) if u8_given else []), list(d_counts))
+    if out_f32 is True:
+        out_f32 = [torch.zeros((capacity, 128), dtype=torch.float32, device=device) for _ in range(n)]
+    if out_u8 is True:
+        out_u8 = [torch.zeros((capacity, 128), dtype=torch.uint8, device=device) for _ in range(n)]
+    out_f32, out_u8 = out_f32 or None, out_u8 or None
+    arr = _pair_dev_table
+    _check(lib().nm_sift_desc_finish_batch_dev(n, arr(descs, torch.float32), arr(d_counts, torch.int32), capacity,
+                                               arr(out_f32, torch.float32), arr(out_u8, torch.uint8), mode, _stream()),
+           "nm_sift_desc_finish_batch_dev")
+    return out_f32, out_u8
+
+
+def desc_finish_host(descs, counts, mode=DESC_L2, want_f32=True, want_u8=True, capacity=None, in_place=False):
+    """desc_finish_batch_dev on the host (nm_sift_desc_finish_host, the same functions): numpy in and out, bit-identical
+    results. counts are host ints. Returns (out_f32 (n, capacity, 128) float32 or None, out_u8 (n, capacity, 128) uint8 or
+    None); rows at and beyond a count stay zero. in_place: the fp32 result is written over a copy of the input itself (the
+    aliased call), rows at and beyond the count then keep the input's values."""
+    import numpy as np
+    mode = _finish_mode(mode)
+    n = _pair_count(descs, counts)
+    descs = _pair_host_arrays(descs, np.float32, flat=False)
+    _pair_descriptors(descs)
+    if not (want_f32 or want_u8):
+        raise NmError("descriptor finish: ask for out_f32, out_u8 or both")
+    capacity = _pair_cap(capacity, descs)
+    if in_place:
+        descs = [d[:capacity].copy() for d in descs]
+    cnt = _pair_host_sizes(counts)
+    f32 = (np.stack(descs) if in_place else np.zeros((n, capacity, 128), np.float32)) if want_f32 else None
+    u8 = np.zeros((n, capacity, 128), np.uint8) if want_u8 else None
+    src = list(f32) if in_place and want_f32 else descs
+    arr = _pair_host_table
+    _check(lib().nm_sift_desc_finish_host(n, arr(src), arr(cnt), capacity, arr(list(f32)) if want_f32 else None,
+                                          arr(list(u8)) if want_u8 else None, mode), "nm_sift_desc_finish_host")
+    return f32, u8
+
+
+def _u8_caps(As, Bs, results, capA, capB):
+    _pair_descriptors(As, Bs)
+    return _pair_cap(capA, list(As) + list(results or ())), _pair_cap(capB, list(Bs))
+
+
+class MatchU8Workspace:
+    """Device scratch of sift_match_u8_batch_dev for up to n pairs of capA x capB rows (the integer row norms)."""
+
+    def __init__(self, n, capA, capB, device=None):
+        torch = _torch()
+        need = lib().nm_sift_match_u8_workspace_bytes(n, capA, capB)
+        if need == 0:
+            raise NmError("u8-match workspace: n %r / capA %r / capB %r out of range" % (n, capA, capB))
+        self.n, self.capA, self.capB = n, capA, capB
+        self.buf = torch.empty(need, dtype=torch.uint8, device=device if device is not None else "cuda")
+
+
+def sift_match_u8_batch_dev(As, d_nAs, Bs, d_nBs, results=None, ambiguity=0.8, workspace=None, capA=None, capB=None):
+    """Brute-force ratio-test matching of n = len(As) <= MATCH_U8_MAX_BATCH pairs of uint8 descriptors on the i8 matrix cores
+    (nm_sift_match_u8_batch_dev): two launches on the current stream, no host read. As / Bs are uint8 device tensors
+    (rows, 128) (out_u8 of desc_finish_batch_dev), d_nAs / d_nBs int32 DEVICE sizes. results: n int32 device tensors of
+    >= capA rows to write into (default: new, filled with -1); a row whose second-best distance is 0 keeps its entry, rows
+    at and beyond nA too. The result equals sift_match_batch_dev on float copies of the same bytes. workspace: a
+    MatchU8Workspace (default: new). Returns results."""
+    torch = _torch()
+    n = _pair_count(As, d_nAs, Bs, d_nBs, results)
+    capA, capB = _u8_caps(As, Bs, results, capA, capB)
+    device = _pair_device(list(As) + list(d_nAs) + list(Bs) + list(d_nBs) + list(results or ()) +
+                          [workspace.buf if workspace is not None else None], list(d_nAs) + list(d_nBs))
+    if results is None:
+        results = [torch.full((capA,), -1, dtype=torch.int32, device=device) for _ in range(n)]
+    if workspace is None:
+        workspace = MatchU8Workspace(n, capA, capB, device)
+    need = lib().nm_sift_match_u8_workspace_bytes(n, capA, capB)
+    if need == 0 or workspace.buf.numel() < need:
+        raise NmError("u8-match workspace too small")
+    arr, u8, i32 = _pair_dev_table, torch.uint8, torch.int32
+    _check(lib().nm_sift_match_u8_batch_dev(n, arr(As, u8), arr(d_nAs, i32), capA, arr(Bs, u8), arr(d_nBs, i32), capB,
+                                            arr(results, i32), float(ambiguity), _dev(workspace.buf), _stream()),
+           "nm_sift_match_u8_batch_dev")
+    return results
+
+
+def sift_match_u8_host(As, nAs, Bs, nBs, ambiguity=0.8, capA=None, capB=None, prior=-1):
+    """sift_match_u8_batch_dev on the host (nm_sift_match_u8_host): numpy in and out, identical results. nAs / nBs are host
+    ints. prior: what the result rows are pre-filled with (a value, or an (n, capA) array). Returns (n, capA) int32."""
+    import numpy as np
+    n = _pair_count(As, nAs, Bs, nBs)
+    As, Bs = (_pair_host_arrays(vs, np.uint8, flat=False) for vs in (As, Bs))
+    capA, capB = _u8_caps(As, Bs, None, capA, capB)
+    result = np.empty((n, capA), np.int32)
+    result[...] = prior
+    nA, nB = _pair_host_sizes(nAs), _pair_host_sizes(nBs)
+    arr = _pair_host_table
+    _check(lib().nm_sift_match_u8_host(n, arr(As), arr(nA), capA, arr(Bs), arr(nB), capB, arr(list(result)),
+                                       float(ambiguity)), "nm_sift_match_u8_host")
+    return result
 
 
 MOSAIC_MAX_BATCH = 64

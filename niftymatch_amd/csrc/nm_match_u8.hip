@@ -1,0 +1,277 @@
+// nm_match_u8.hip -- batched brute-force matching of unsigned-char descriptors on the gfx950 i8 matrix pipe (no reference
+// counterpart: the reference matches fp32 rows only, kernels/match.cu). The squared distance of two u8 rows is an integer
+// <= 128 * 255^2 = 8 323 200 < 2^23, computed EXACTLY in i32, so the result is what the reference's scan (match.cu:88-116)
+// makes of the same distances as floats, with no error bound, no second pass and no fallback.
+// TWO launches per call whatever n is, on the caller's stream, no allocation, no synchronisation, no host read:
+//   1. norms (grid ceil(rows / 256) x 2 x n): one lane per row, |row - 128|^2 as an int into the workspace. Rows of B at and
+//      beyond nB (up to the next multiple of 32) get PAD_NORM, which puts their distances above every real one.
+//   2. match (grid ceil(capA / 256) x n): a wave owns 64 queries as two groups of 32 and keeps their four k-step fragments
+//      (bytes - 128 as signed i8, 16 bytes per lane and step) in 32 registers as the B operand of
+//      v_mfma_i32_32x32x32_i8; it streams the candidates in tiles of 32 as the A operand straight from global memory
+//      (a tile is 4 KB, one 16-byte read per lane and k step; the next tile is requested before this one is multiplied).
+//      The accumulator holds a query on its column (lane & 31) and the candidates (e & 3) + 8 (e >> 2) + 4 (lane >> 5) in
+//      its 16 registers e; d = |a|^2 + |b|^2 - 2 a.b. Per tile the two smallest keys (d << 4 | e) are found with min / max
+//      and merged into the lane's running (min1, index, min2) only when the wave votes that some lane needs it. Ascending
+//      e is ascending candidate index inside a lane, tiles ascend, and every comparison that replaces is strict, so the
+//      lowest index wins a tie; the two lane halves (same query, disjoint candidates) are merged at the end by
+//      (distance, index). The last step is the reference's: min2 starts at 2139095040.0f, a row with min2 == 0 is left
+//      unwritten, result = min1 / min2 < ambiguity ? index : -1 with an fp32 divide.
+// No LDS, no atomics. The lane -> (row, k) map of the i8 operands is checked by tools/micro/mfma_i8_model.hip.
+#include "nm_common.hpp"
+#include "nm_pair_batch.hpp"
+#include "../../include/nm_abi.h"
+
+#include <cstdint>
+
+namespace {
+
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int DIM = 128;
+constexpr int TB = 256;                     // four waves
+constexpr int QG = 2;                       // query groups of 32 per wave
+constexpr int QW = 32 * QG;                 // queries per wave
+constexpr int QB = QW * TB / 64;            // queries per workgroup
+constexpr int TILE = 32;                    // candidates per MFMA tile
+constexpr int PAD_NORM = 1 << 25;           // norm of a candidate row that does not exist: d >= 2^25 - 2^22 > 2^23
+constexpr int NO_SECOND = 1 << 24;          // a min2 at or above this is "no second candidate"
+constexpr int KEY_INF = 0x7fffffff;
+constexpr float MIN2_INIT = 2139095040.0f;  // match.cu:91, the int 0x7f800000 converted
+static_assert(NM_MATCH_U8_MAX_BATCH == nmp::MAX_BATCH, "public header and pair-batch convention disagree");
+static_assert(DIM * 255 * 255 < (1 << 23) && ((PAD_NORM + (1 << 23)) >> 27) == 0, "keys (d << 4 | e) stay positive ints");
+
+struct NormArgs {
+    const unsigned char *A[NM_MATCH_U8_MAX_BATCH];
+    const int *d_nA[NM_MATCH_U8_MAX_BATCH];
+    const unsigned char *B[NM_MATCH_U8_MAX_BATCH];
+    const int *d_nB[NM_MATCH_U8_MAX_BATCH];
+};
+struct MatchArgs {                          // 5 x 64 pointers: 2.5 KB of the 4 KB of kernel arguments
+    const unsigned char *A[NM_MATCH_U8_MAX_BATCH];
+    const int *d_nA[NM_MATCH_U8_MAX_BATCH];
+    const unsigned char *B[NM_MATCH_U8_MAX_BATCH];
+    const int *d_nB[NM_MATCH_U8_MAX_BATCH];
+    int *result[NM_MATCH_U8_MAX_BATCH];
+};
+static_assert(sizeof(MatchArgs) + 64 < 4096, "match kernel arguments exceed 4 KB");
+
+__host__ __device__ inline size_t rows_a(int capA) { return ((size_t)capA + QB - 1) / QB * QB; }
+__host__ __device__ inline size_t rows_b(int capB) { return ((size_t)capB + TILE - 1) / TILE * TILE; }
+// pair k's norms: rows_a(capA) ints of A, then rows_b(capB) ints of B
+__host__ __device__ inline int *norms_of(void *ws, int k, int capA, int capB)
+{
+    return static_cast<int *>(ws) + (size_t)k * (rows_a(capA) + rows_b(capB));
+}
+
+// The reference's last step on exact integer distances (every one of them is also an exact float): m1 at the lowest index
+// idx, m2 = the smallest of the others or NO_SECOND. The scan's min2 starts at MIN2_INIT and is overwritten at every
+// replacement of the minimum, so the start value survives only while the minimum sits at candidate 0; every real distance
+// is below it, so it shows only for nB == 1.
+__host__ __device__ __forceinline__ void emit_u8(int m1, int idx, int m2, float ambiguity, int *__restrict__ out)
+{
+    const float f1 = (float)m1;
+    const float f2 = m2 >= NO_SECOND ? MIN2_INIT : (float)m2;
+    if (f2 > 0.0f) {
+        const float q = f1 / f2;
+        *out = (q < ambiguity) ? idx : -1;
+    }
+}
+
+__device__ __forceinline__ int row_norm(const unsigned char *__restrict__ row)
+{
+    int s = 0;
+#pragma unroll
+    for (int q = 0; q < DIM / 16; ++q) {
+        const uint4 u = reinterpret_cast<const uint4 *>(row)[q];
+        const unsigned w[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                const int v = (int)((w[e] >> (8 * b)) & 255u) - 128;
+                s += v * v;
+            }
+    }
+    return s;
+}
+
+__global__ __launch_bounds__(TB) void match_u8_norms_kernel(const NormArgs a, int capA, int capB, void *__restrict__ ws)
+{
+    const int k = blockIdx.z, side = blockIdx.y;
+    const size_t row = (size_t)blockIdx.x * TB + threadIdx.x;
+    int *__restrict__ na = norms_of(ws, k, capA, capB);
+    if (side == 0) {
+        const int nA = nmp::clip(*a.d_nA[k], capA);
+        if (row < rows_a(capA)) na[row] = row < (size_t)nA ? row_norm(a.A[k] + row * DIM) : 0;
+    } else {
+        const int nB = nmp::clip(*a.d_nB[k], capB);
+        if (row < rows_b(capB)) na[rows_a(capA) + row] = row < (size_t)nB ? row_norm(a.B[k] + row * DIM) : PAD_NORM;
+    }
+}
+
+struct Frag { i32x4 s[4]; };                // one lane's 4 k steps of a row: bytes 32 t + 16 h .. + 15, minus 128
+
+__device__ __forceinline__ Frag load_frag(const unsigned char *__restrict__ row, int h)
+{
+    Frag f;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const i32x4 u = *reinterpret_cast<const i32x4 *>(row + 32 * t + 16 * h);
+        f.s[t] = u ^ (int)0x80808080;       // byte - 128 as a signed byte
+    }
+    return f;
+}
+
+struct Norm16 { i32x4 g[4]; };              // the tile's 16 candidate norms of this lane half: rows 8 g + 4 h + 0..3
+
+__device__ __forceinline__ Norm16 load_norms(const int *__restrict__ nb, int c0, int h)
+{
+    Norm16 n;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) n.g[g] = *reinterpret_cast<const i32x4 *>(nb + c0 + 8 * g + 4 * h);
+    return n;
+}
+
+__global__ __launch_bounds__(TB) void match_u8_kernel(const MatchArgs a, int capA, int capB, float ambiguity,
+                                                      void *__restrict__ ws)
+{
+    const int k = blockIdx.y, lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
+    const int nA = nmp::clip(*a.d_nA[k], capA), nB = nmp::clip(*a.d_nB[k], capB);
+    if (nA <= 0 || nB <= 0) return;                                  // a pair without rows is a no-op
+    const int q0 = blockIdx.x * QB + (threadIdx.x >> 6) * QW;
+    if (q0 >= nA) return;                                            // uniform over the wave; no barrier follows
+    const unsigned char *__restrict__ Ad = a.A[k];
+    const unsigned char *__restrict__ Bd = a.B[k];
+    const int *__restrict__ na = norms_of(ws, k, capA, capB);
+    const int *__restrict__ nb = na + rows_a(capA);
+
+    Frag qf[QG];
+    int nq[QG], m1[QG], i1[QG], m2[QG];
+#pragma unroll
+    for (int g = 0; g < QG; ++g) {
+        const int qi = q0 + 32 * g + r, qrow = qi < nA ? qi : nA - 1;   // a lane past nA repeats the last row and writes nothing
+        qf[g] = load_frag(Ad + (size_t)qrow * DIM, h);
+        nq[g] = na[qrow];
+        m1[g] = KEY_INF; m2[g] = KEY_INF; i1[g] = 0;
+    }
+
+    const int tiles = (nB + TILE - 1) / TILE;
+    auto cand_row = [&](int t) { const int c = t * TILE + r; return Bd + (size_t)(c < nB ? c : nB - 1) * DIM; };
+    Frag cf = load_frag(cand_row(0), h);
+    Norm16 cn = load_norms(nb, 0, h);
+    for (int t = 0; t < tiles; ++t) {
+        const int tn = t + 1 < tiles ? t + 1 : t;                    // the last tile asks for itself
+        const Frag nf = load_frag(cand_row(tn), h);
+        const Norm16 nn = load_norms(nb, tn * TILE, h);
+#pragma unroll
+        for (int g = 0; g < QG; ++g) {
+            i32x16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+            for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(cf.s[s], qf[g].s[s], acc, 0, 0, 0);
+            int g1 = KEY_INF, g2 = KEY_INF;
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int d = nq[g] + cn.g[e >> 2][e & 3] - 2 * acc[e];
+                const int key = (d << 4) | e;
+                g2 = min(g2, max(g1, key));
+                g1 = min(g1, key);
+            }
+            const int d1 = g1 >> 4;
+            if (__any(d1 < m2[g])) {
+                const int d2 = g2 >> 4, e1 = g1 & 15;
+                if (d1 < m1[g]) {
+                    m2[g] = min(m1[g], d2);
+                    m1[g] = d1;
+                    i1[g] = t * TILE + (e1 & 3) + 8 * (e1 >> 2) + 4 * h;
+                } else {
+                    m2[g] = min(m2[g], d1);
+                }
+            }
+        }
+        cf = nf; cn = nn;
+    }
+
+#pragma unroll
+    for (int g = 0; g < QG; ++g) {
+        const int o1 = __shfl_xor(m1[g], 32), oi = __shfl_xor(i1[g], 32), o2 = __shfl_xor(m2[g], 32);
+        const bool take = o1 < m1[g] || (o1 == m1[g] && oi < i1[g]);
+        const int lo = take ? o1 : m1[g], hi = take ? m1[g] : o1, s2 = take ? o2 : m2[g];
+        const int idx = take ? oi : i1[g];
+        const int qi = q0 + 32 * g + r;
+        if (h == 0 && qi < nA) emit_u8(lo, idx, min(hi, s2), ambiguity, a.result[k] + qi);
+    }
+}
+
+// ---- the host twin: exact integer distances, the first minimum and the smallest of the others, the same last step ----
+void host_match_pair(const unsigned char *A, int nA, const unsigned char *B, int nB, float ambiguity, int *result)
+{
+    if (nA <= 0 || nB <= 0) return;
+    for (int i = 0; i < nA; ++i) {
+        int m1 = KEY_INF, m2 = KEY_INF, idx = 0;
+        for (int j = 0; j < nB; ++j) {
+            int d = 0;
+            for (int q = 0; q < DIM; ++q) {
+                const int t = (int)A[(size_t)i * DIM + q] - (int)B[(size_t)j * DIM + q];
+                d += t * t;
+            }
+            if (d < m1) { m2 = m1; m1 = d; idx = j; }
+            else if (d < m2) m2 = d;
+        }
+        emit_u8(m1, idx, m2, ambiguity, result + i);
+    }
+}
+
+bool aligned16(int n, const unsigned char *const *t)
+{
+    for (int k = 0; k < n; ++k)
+        if (reinterpret_cast<uintptr_t>(t[k]) & 15u) return false;
+    return true;
+}
+
+bool u8_args_ok(int n, const unsigned char *const *A, const int *const *nA, int capA, const unsigned char *const *B,
+                const int *const *nB, int capB, int *const *result)
+{
+    return nmp::range_ok(n, capA) && nmp::cap_ok(capB) && nmp::tables_ok(n, {A, nA, B, nB, result}, {}, {});
+}
+
+}  // namespace
+
+extern "C" size_t nm_sift_match_u8_workspace_bytes(int n, int capA, int capB)
+{
+    if (!nmp::range_ok(n, capA) || !nmp::cap_ok(capB)) return 0;
+    return (size_t)n * (rows_a(capA) + rows_b(capB)) * sizeof(int);
+}
+
+extern "C" int nm_sift_match_u8_batch_dev(int n, const unsigned char *const *A, const int *const *d_nA, int capA,
+                                          const unsigned char *const *B, const int *const *d_nB, int capB,
+                                          int *const *result, float ambiguity, void *workspace, void *stream)
+{
+    if (!u8_args_ok(n, A, d_nA, capA, B, d_nB, capB, result) || !workspace || !aligned16(n, A) || !aligned16(n, B) ||
+        (reinterpret_cast<uintptr_t>(workspace) & 15u))
+        return (int)hipErrorInvalidValue;
+    NormArgs p;
+    MatchArgs m;
+    nmp::fill_slots(p.A, A, 0, n); nmp::fill_slots(p.d_nA, d_nA, 0, n); nmp::fill_slots(p.B, B, 0, n);
+    nmp::fill_slots(p.d_nB, d_nB, 0, n);
+    nmp::fill_slots(m.A, A, 0, n); nmp::fill_slots(m.d_nA, d_nA, 0, n); nmp::fill_slots(m.B, B, 0, n);
+    nmp::fill_slots(m.d_nB, d_nB, 0, n); nmp::fill_slots(m.result, result, 0, n);
+    const size_t rows = rows_a(capA) > rows_b(capB) ? rows_a(capA) : rows_b(capB);
+    hipLaunchKernelGGL(match_u8_norms_kernel, dim3((unsigned)((rows + TB - 1) / TB), 2, n), dim3(TB), 0, nm_stream(stream), p,
+                       capA, capB, workspace);
+    NM_LAUNCH_CHECK();
+    hipLaunchKernelGGL(match_u8_kernel, dim3(nm_divup(capA, QB), n), dim3(TB), 0, nm_stream(stream), m, capA, capB, ambiguity,
+                       workspace);
+    NM_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int nm_sift_match_u8_host(int n, const unsigned char *const *A, const int *const *nA, int capA,
+                                     const unsigned char *const *B, const int *const *nB, int capB, int *const *result,
+                                     float ambiguity)
+{
+    if (!u8_args_ok(n, A, nA, capA, B, nB, capB, result)) return (int)hipErrorInvalidValue;
+    for (int k = 0; k < n; ++k)
+        host_match_pair(A[k], nmp::clip(*nA[k], capA), B[k], nmp::clip(*nB[k], capB), ambiguity, result[k]);
+    return 0;
+}
