@@ -738,6 +738,51 @@ NM_API int nm_sift_match_u8_host(int n, const unsigned char *const *A, const int
                                  const unsigned char *const *B, const int *const *nB, int capB, int *const *result,
                                  float ambiguity);
 
+/* ---- Mutual-nearest-neighbour filtering of a match list over unsigned-char descriptors on the i8 matrix cores: the
+ * cross-check of the byte pipeline (finish -> nm_sift_match_u8_batch_dev -> this -> RANSAC), no reference counterpart. It is
+ * nm_sift_match_mutual_batch_dev_f32 on bytes: given pair k's match list, a match i -> j is kept only when i is also the
+ * best row of A for column j. n in [1, NM_MATCH_MUTUAL_U8_MAX_BATCH] pairs in THREE launches on `stream` whatever n is
+ * (claims with the row norms, scan, counts); no allocation, no synchronisation, no host read -- capturable into a HIP graph
+ * behind the matcher. Pair k (tables of n pointers, the tables in HOST memory):
+ *   A[k] / B[k]        capA x 128 / capB x 128 unsigned chars, row-major, 16-byte aligned (out_u8 of the finish);
+ *   d_nA[k], d_nB[k]   DEVICE ints, the row counts: nA = clip(*d_nA[k], 0, capA), nB = clip(*d_nB[k], 0, capB). Rows beyond
+ *                      them are never read;
+ *   matches[k]         device, capA ints: the list to filter (entries at and beyond nA are never read).
+ * Per pair, all integers:
+ *   Distance: d(i, j) = sum over q of (A[i][q] - B[j][q])^2, exact (<= 128 * 255^2 = 8 323 200 < 2^23).
+ *   Claim: row i < nA claims column j = matches[k][i] when 0 <= j < nB. Any other value (-1, below -1, >= nB) is no claim.
+ *   Keep: with tau = d(i, j), the claim is kept exactly when no i' < nA has d(i', j) < tau and no i' < i has
+ *     d(i', j) == tau: i is the first minimum of column j in an ascending scan with strict <.
+ *   There is no NaN case: bytes have none, every distance is a number and every claim has a tau.
+ * Outputs: result[k] (device, capA ints; ALL capA entries are written: j for a kept claim, else -1, -1 beyond nA; it may
+ * alias no input), count (device, n ints: entries >= 0 of result[k]), forward_distance (optional table, may be NULL:
+ * forward_distance[k] device, capA floats = (float)tau, which is exact, for a claiming row and +inf otherwise). A pair with
+ * nA <= 0 or nB <= 0 still gets its result filled with -1, its forward distances with +inf and count 0. The kept matches
+ * of a pair are injective. result[k] can go to nm_ransac_batch_dev_f32, nm_ransac_refit_batch_dev_f32 and nm_align_points
+ * as matches[k] as it is. A pair's outputs depend on that pair's inputs alone, never on n, on the pair's slot or on
+ * scheduling (no atomics; a beaten claim's -1 may be stored by several workgroups, always the same value).
+ * Equivalence: result, count and forward_distance equal those of nm_sift_match_mutual_batch_dev_f32 on float copies of the
+ * same bytes, bit for bit: differences are <= 255, squares <= 65 025 and partial sums < 2^24, so every step of that
+ * entry's fmaf chain is exact and its NaN rules never apply.
+ * workspace: device, 16-byte aligned, nm_sift_match_mutual_u8_workspace_bytes(n, capA, capB) bytes (0 for arguments out of
+ * range), no contents expected or preserved.
+ * Returns hipErrorInvalidValue, before anything is launched or dereferenced, for n not in [1, 64], capA or capB not in
+ * [1, 2^22), a NULL required pointer (every argument but forward_distance and stream), a NULL among the first n entries of
+ * a table, or a descriptor pointer or workspace that is not 16-byte aligned.
+ * nm_sift_match_mutual_u8_host: the same with every pointer in host memory (nA[k] / nB[k] point to host ints, no alignment
+ * rule), no workspace and no stream: a plain loop over int distances with the same claim and keep predicates and the same
+ * argument checks; results identical to the device entry's.                                                            */
+#define NM_MATCH_MUTUAL_U8_MAX_BATCH 64
+NM_API size_t nm_sift_match_mutual_u8_workspace_bytes(int n, int capA, int capB);
+NM_API int nm_sift_match_mutual_u8_batch_dev(int n, const unsigned char *const *A, const int *const *d_nA, int capA,
+                                             const unsigned char *const *B, const int *const *d_nB, int capB,
+                                             const int *const *matches, int *const *result, int *count,
+                                             float *const *forward_distance, void *workspace, void *stream);
+NM_API int nm_sift_match_mutual_u8_host(int n, const unsigned char *const *A, const int *const *nA, int capA,
+                                        const unsigned char *const *B, const int *const *nB, int capB,
+                                        const int *const *matches, int *const *result, int *count,
+                                        float *const *forward_distance);
+
 /* ---- Mosaic plan and batched blend (no reference counterpart: the reference's client places frames on the host and
  * calls transform_blend once per frame). Together with nm_ransac_batch_dev_f32 the chain detect -> match -> RANSAC ->
  * plan -> blend runs on one stream with no host read and can be captured into one HIP graph.

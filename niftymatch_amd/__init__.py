@@ -121,6 +121,9 @@ _SIGNATURES = {
     "nm_sift_match_u8_workspace_bytes": (_SZ, [_I, _I, _I]),
     "nm_sift_match_u8_batch_dev": (_I, [_I, _P, _P, _I, _P, _P, _I, _P, _F, _P, _P]),
     "nm_sift_match_u8_host": (_I, [_I, _P, _P, _I, _P, _P, _I, _P, _F]),
+    "nm_sift_match_mutual_u8_workspace_bytes": (_SZ, [_I, _I, _I]),
+    "nm_sift_match_mutual_u8_batch_dev": (_I, [_I, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P]),
+    "nm_sift_match_mutual_u8_host": (_I, [_I, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P]),
     "nm_mosaic_plan_f32": (_I, [_I, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "nm_mosaic_plan_host_f32": (_I, [_I, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "nm_transform_blend_batch": (_I, [_P, _I, _I, _P, _I, _P, _I, _I, _P, _I, _P, _I, _P, _P]),
@@ -1105,7 +1108,7 @@ def sift_match_mutual_host(As, nAs, Bs, nBs, matches, capA=None, capB=None, want
 
 # ---- descriptor finish and the u8 matcher ----
 DESC_L2, DESC_ROOT = 0, 1
-DESC_FINISH_MAX_BATCH = MATCH_U8_MAX_BATCH = _PAIR_MAX_BATCH
+DESC_FINISH_MAX_BATCH = MATCH_U8_MAX_BATCH = MATCH_MUTUAL_U8_MAX_BATCH = _PAIR_MAX_BATCH
 
 
 def _finish_mode(mode):
@@ -1227,6 +1230,68 @@ def sift_match_u8_host(As, nAs, Bs, nBs, ambiguity=0.8, capA=None, capB=None, pr
     _check(lib().nm_sift_match_u8_host(n, arr(As), arr(nA), capA, arr(Bs), arr(nB), capB, arr(list(result)),
                                        float(ambiguity)), "nm_sift_match_u8_host")
     return result
+
+
+class MatchMutualU8Workspace:
+    """Device scratch of sift_match_mutual_u8_batch_dev for up to n pairs of capA x capB rows (the integer norms of A's
+    rows and the compacted claims)."""
+
+    def __init__(self, n, capA, capB, device=None):
+        torch = _torch()
+        need = lib().nm_sift_match_mutual_u8_workspace_bytes(n, capA, capB)
+        if need == 0:
+            raise NmError("mutual-u8 workspace: n %r / capA %r / capB %r out of range" % (n, capA, capB))
+        self.n, self.capA, self.capB = n, capA, capB
+        self.buf = torch.empty(need, dtype=torch.uint8, device=device if device is not None else "cuda")
+
+
+def sift_match_mutual_u8_batch_dev(As, d_nAs, Bs, d_nBs, matches, capA=None, capB=None, results=None, workspace=None,
+                                   want_distance=False):
+    """Mutual-nearest-neighbour filter of n = len(As) <= MATCH_MUTUAL_U8_MAX_BATCH match lists over uint8 descriptors on the
+    i8 matrix cores (nm_sift_match_mutual_u8_batch_dev): three launches on the current stream, no host read. As / Bs are
+    uint8 device descriptors (rows, 128) (out_u8 of desc_finish_batch_dev), d_nAs / d_nBs int32 DEVICE sizes, matches[k] the
+    int32 device list to filter (e.g. what sift_match_u8_batch_dev wrote). Row i keeps its match j only when no row of A is
+    nearer to column j and no earlier row is as near; distances are exact integers. results: n int32 device tensors of
+    >= capA rows to write into (default: new; none may be a match list). workspace: a MatchMutualU8Workspace (default: new).
+    Returns (results, count[n]) and, with want_distance, the list of float32 (capA,) forward distances (+inf for a row
+    without a claim). The outputs equal sift_match_mutual_batch_dev's on float copies of the same bytes bit for bit.
+    results[k] plugs into ransac_batch_dev, ransac_refit_batch_dev and align_points as matches."""
+    torch = _torch()
+    n = _pair_count(As, d_nAs, Bs, d_nBs, matches, results)
+    capA, capB = _mutual_caps(As, Bs, matches, capA, capB)
+    device = _pair_device(list(As) + list(d_nAs) + list(Bs) + list(d_nBs) + list(matches) + list(results or ()) +
+                          [workspace.buf if workspace is not None else None], list(d_nAs) + list(d_nBs))
+    results, count, fwd = _pair_dev_match_out(n, capA, results, device, want_distance)
+    if {r.data_ptr() for r in results} & {m.data_ptr() for m in matches}:
+        raise NmError("a result tensor is also a match list")
+    if workspace is None:
+        workspace = MatchMutualU8Workspace(n, capA, capB, device)
+    need = lib().nm_sift_match_mutual_u8_workspace_bytes(n, capA, capB)
+    if need == 0 or workspace.buf.numel() < need:
+        raise NmError("mutual-u8 workspace too small")
+    arr, u8, f, i32 = _pair_dev_table, torch.uint8, torch.float32, torch.int32
+    _check(lib().nm_sift_match_mutual_u8_batch_dev(n, arr(As, u8), arr(d_nAs, i32), capA, arr(Bs, u8), arr(d_nBs, i32), capB,
+                                                   arr(matches, i32), arr(results, i32), _dev(count), arr(fwd, f),
+                                                   _dev(workspace.buf), _stream()), "nm_sift_match_mutual_u8_batch_dev")
+    return (results, count) + ((fwd,) if want_distance else ())
+
+
+def sift_match_mutual_u8_host(As, nAs, Bs, nBs, matches, capA=None, capB=None, want_distance=False):
+    """sift_match_mutual_u8_batch_dev on the host (nm_sift_match_mutual_u8_host): numpy in and out, identical results.
+    nAs / nBs are host ints. Returns (results (n, capA) int32, count (n,)) and, with want_distance, forward distances
+    (n, capA) float32."""
+    import numpy as np
+    n = _pair_count(As, nAs, Bs, nBs, matches)
+    As, Bs = (_pair_host_arrays(vs, np.uint8, flat=False) for vs in (As, Bs))
+    matches = _pair_host_arrays(matches, np.int32, flat=False)
+    capA, capB = _mutual_caps(As, Bs, matches, capA, capB)
+    nA, nB = _pair_host_sizes(nAs), _pair_host_sizes(nBs)
+    result, count, fwd = _pair_host_match_out(n, capA, want_distance)
+    arr = _pair_host_table
+    _check(lib().nm_sift_match_mutual_u8_host(n, arr(As), arr(nA), capA, arr(Bs), arr(nB), capB, arr(matches),
+                                              arr(list(result)), _pair_host_ptr(count), arr(list(fwd)) if want_distance else None),
+           "nm_sift_match_mutual_u8_host")
+    return (result, count) + ((fwd,) if want_distance else ())
 
 
 MOSAIC_MAX_BATCH = 64

@@ -16,8 +16,10 @@
 //      lowest index wins a tie; the two lane halves (same query, disjoint candidates) are merged at the end by
 //      (distance, index). The last step is the reference's: min2 starts at 2139095040.0f, a row with min2 == 0 is left
 //      unwritten, result = min1 / min2 < ambiguity ? index : -1 with an fp32 divide.
-// No LDS, no atomics. The lane -> (row, k) map of the i8 operands is checked by tools/micro/mfma_i8_model.hip.
+// No LDS, no atomics. The lane -> (row, k) map of the i8 operands is checked by tools/micro/mfma_i8_model.hip. The operand
+// fragments, the row norm and PAD_NORM are nm_match_u8_dev.hpp, shared with the mutual filter (nm_match_mutual_u8.hip).
 #include "nm_common.hpp"
+#include "nm_match_u8_dev.hpp"
 #include "nm_pair_batch.hpp"
 #include "../../include/nm_abi.h"
 
@@ -25,21 +27,15 @@
 
 namespace {
 
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x16 __attribute__((ext_vector_type(16)));
+using namespace nmu8;
 
-constexpr int DIM = 128;
 constexpr int TB = 256;                     // four waves
 constexpr int QG = 2;                       // query groups of 32 per wave
 constexpr int QW = 32 * QG;                 // queries per wave
 constexpr int QB = QW * TB / 64;            // queries per workgroup
-constexpr int TILE = 32;                    // candidates per MFMA tile
-constexpr int PAD_NORM = 1 << 25;           // norm of a candidate row that does not exist: d >= 2^25 - 2^22 > 2^23
 constexpr int NO_SECOND = 1 << 24;          // a min2 at or above this is "no second candidate"
-constexpr int KEY_INF = 0x7fffffff;
 constexpr float MIN2_INIT = 2139095040.0f;  // match.cu:91, the int 0x7f800000 converted
 static_assert(NM_MATCH_U8_MAX_BATCH == nmp::MAX_BATCH, "public header and pair-batch convention disagree");
-static_assert(DIM * 255 * 255 < (1 << 23) && ((PAD_NORM + (1 << 23)) >> 27) == 0, "keys (d << 4 | e) stay positive ints");
 
 struct NormArgs {
     const unsigned char *A[NM_MATCH_U8_MAX_BATCH];
@@ -78,24 +74,6 @@ __host__ __device__ __forceinline__ void emit_u8(int m1, int idx, int m2, float 
     }
 }
 
-__device__ __forceinline__ int row_norm(const unsigned char *__restrict__ row)
-{
-    int s = 0;
-#pragma unroll
-    for (int q = 0; q < DIM / 16; ++q) {
-        const uint4 u = reinterpret_cast<const uint4 *>(row)[q];
-        const unsigned w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-#pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                const int v = (int)((w[e] >> (8 * b)) & 255u) - 128;
-                s += v * v;
-            }
-    }
-    return s;
-}
-
 __global__ __launch_bounds__(TB) void match_u8_norms_kernel(const NormArgs a, int capA, int capB, void *__restrict__ ws)
 {
     const int k = blockIdx.z, side = blockIdx.y;
@@ -108,29 +86,6 @@ __global__ __launch_bounds__(TB) void match_u8_norms_kernel(const NormArgs a, in
         const int nB = nmp::clip(*a.d_nB[k], capB);
         if (row < rows_b(capB)) na[rows_a(capA) + row] = row < (size_t)nB ? row_norm(a.B[k] + row * DIM) : PAD_NORM;
     }
-}
-
-struct Frag { i32x4 s[4]; };                // one lane's 4 k steps of a row: bytes 32 t + 16 h .. + 15, minus 128
-
-__device__ __forceinline__ Frag load_frag(const unsigned char *__restrict__ row, int h)
-{
-    Frag f;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        const i32x4 u = *reinterpret_cast<const i32x4 *>(row + 32 * t + 16 * h);
-        f.s[t] = u ^ (int)0x80808080;       // byte - 128 as a signed byte
-    }
-    return f;
-}
-
-struct Norm16 { i32x4 g[4]; };              // the tile's 16 candidate norms of this lane half: rows 8 g + 4 h + 0..3
-
-__device__ __forceinline__ Norm16 load_norms(const int *__restrict__ nb, int c0, int h)
-{
-    Norm16 n;
-#pragma unroll
-    for (int g = 0; g < 4; ++g) n.g[g] = *reinterpret_cast<const i32x4 *>(nb + c0 + 8 * g + 4 * h);
-    return n;
 }
 
 __global__ __launch_bounds__(TB) void match_u8_kernel(const MatchArgs a, int capA, int capB, float ambiguity,
@@ -220,13 +175,6 @@ void host_match_pair(const unsigned char *A, int nA, const unsigned char *B, int
         }
         emit_u8(m1, idx, m2, ambiguity, result + i);
     }
-}
-
-bool aligned16(int n, const unsigned char *const *t)
-{
-    for (int k = 0; k < n; ++k)
-        if (reinterpret_cast<uintptr_t>(t[k]) & 15u) return false;
-    return true;
 }
 
 bool u8_args_ok(int n, const unsigned char *const *A, const int *const *nA, int capA, const unsigned char *const *B,

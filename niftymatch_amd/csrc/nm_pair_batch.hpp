@@ -1,5 +1,5 @@
 // nm_pair_batch.hpp -- the convention of the per-pair stages behind the blind matcher (nm_ransac_batch.hip,
-// nm_ransac_refit.hip, nm_match_guided.hip, nm_match_mutual.hip), stated once. A call takes n <= MAX_BATCH pairs. A pair is
+// nm_ransac_refit.hip, nm_match_guided.hip, nm_match_mutual.hip, nm_match_mutual_u8.hip), stated once. A call takes n <= MAX_BATCH pairs. A pair is
 // a row of host tables of device pointers; the tables travel to the kernels as [MAX_BATCH] pointer arrays inside the kernel
 // arguments, unused slots null. Sizes are device ints clipped to a capacity below CAP_LIMIT. A bad argument is refused
 // with hipErrorInvalidValue before anything is launched and before any device pointer is dereferenced; a host twin runs
@@ -17,7 +17,7 @@ namespace nmp {
 constexpr int MAX_BATCH = 64;               // pairs per call
 constexpr int CAP_LIMIT = 1 << 22;          // capacities (rows per pair) lie in [1, CAP_LIMIT)
 static_assert(NM_RANSAC_MAX_BATCH == MAX_BATCH && NM_MATCH_GUIDED_MAX_BATCH == MAX_BATCH &&
-              NM_MATCH_MUTUAL_MAX_BATCH == MAX_BATCH, "public header and pair-batch convention disagree");
+              NM_MATCH_MUTUAL_MAX_BATCH == MAX_BATCH && NM_MATCH_MUTUAL_U8_MAX_BATCH == MAX_BATCH, "public header and pair-batch convention disagree");
 
 /* A device size as the kernels (and the host twins) use it */
 __host__ __device__ __forceinline__ int clip(int v, int cap) { return v < 0 ? 0 : (v > cap ? cap : v); }
