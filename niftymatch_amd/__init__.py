@@ -866,16 +866,35 @@ def _point_tables_dev(src_xs, src_ys, d_nAs, dst_xs, dst_ys, matches):
     return [_pair_dev_table(ts, dt) for ts, dt in ((src_xs, f), (src_ys, f), (d_nAs, i32), (dst_xs, f), (dst_ys, f), (matches, i32))]
 
 
-class RansacBatchWorkspace:
+class _PairWorkspace:
+    """Device scratch of a pair-batch stage: `buf` holds what the stage's *_workspace_bytes asks for the shape, which is
+    kept as attributes. A subclass names the C function, the stage (for messages) and how it words a refused shape."""
+    _bytes_fn = _what = _shape_text = None
+
+    def _alloc(self, device, **shape):
+        need = getattr(lib(), self._bytes_fn)(*shape.values())
+        if need == 0:
+            raise NmError("%s: %s out of range" % (self._what, self._shape_text % tuple(shape.values())))
+        self.__dict__.update(shape)
+        self.buf = _torch().empty(need, dtype=_torch().uint8, device=device if device is not None else "cuda")
+
+
+def _pair_workspace(cls, workspace, device, *shape):
+    """The workspace of a call: the given one, or a new `cls`; never smaller than the stage asks for this shape."""
+    if workspace is None:
+        workspace = cls(*shape, device)
+    need = getattr(lib(), cls._bytes_fn)(*shape)
+    if need == 0 or workspace.buf.numel() < need:
+        raise NmError(cls._what + " too small")
+    return workspace
+
+
+class RansacBatchWorkspace(_PairWorkspace):
     """Device scratch for nm_ransac_batch_dev_f32: n pairs of at most capA rows and `iterations` hypotheses."""
+    _bytes_fn, _what, _shape_text = "nm_ransac_batch_dev_workspace_bytes", "RANSAC batch workspace", "n=%d capA=%d iterations=%d"
 
     def __init__(self, n, capA, iterations, device):
-        torch = _torch()
-        need = lib().nm_ransac_batch_dev_workspace_bytes(n, capA, iterations)
-        if need == 0:
-            raise NmError("RANSAC batch workspace: n=%d capA=%d iterations=%d out of range" % (n, capA, iterations))
-        self.n, self.capA, self.iterations = n, capA, iterations
-        self.buf = torch.empty(need, dtype=torch.uint8, device=device)
+        self._alloc(device, n=n, capA=capA, iterations=iterations)
 
 
 def ransac_batch_sample(seed, hypothesis, sample, samples, m):
@@ -900,11 +919,7 @@ def ransac_batch_dev(model, src_xs, src_ys, d_nAs, dst_xs, dst_ys, matches, iter
     capA = _pair_cap(capA, list(src_xs) + list(src_ys) + list(matches))
     device = _pair_device(list(src_xs) + list(src_ys) + list(d_nAs) + list(dst_xs) + list(dst_ys) + list(matches) +
                           [workspace.buf if workspace is not None else None], d_nAs)
-    if workspace is None:
-        workspace = RansacBatchWorkspace(n, capA, iterations, device)
-    need = lib().nm_ransac_batch_dev_workspace_bytes(n, capA, iterations)
-    if need == 0 or workspace.buf.numel() < need:
-        raise NmError("RANSAC batch workspace too small")
+    workspace = _pair_workspace(RansacBatchWorkspace, workspace, device, n, capA, iterations)
     H_best = torch.empty((n, 9), dtype=torch.float32, device=device)
     best, pos, status = (torch.empty(n, dtype=torch.int32, device=device) for _ in range(3))
     H_all = torch.empty((n, iterations, 9), dtype=torch.float32, device=device) if want_all else None
@@ -1046,16 +1061,46 @@ def _mutual_caps(As, Bs, matches, capA, capB):
     return _pair_cap(capA, list(As) + list(matches)), _pair_cap(capB, list(Bs))
 
 
-class MatchMutualWorkspace:
+class MatchMutualWorkspace(_PairWorkspace):
     """Device scratch of sift_match_mutual_batch_dev for up to n pairs of capA rows (the compacted claims)."""
+    _bytes_fn, _what, _shape_text = "nm_sift_match_mutual_workspace_bytes", "mutual-match workspace", "n %r / capA %r"
 
     def __init__(self, n, capA, device=None):
-        torch = _torch()
-        need = lib().nm_sift_match_mutual_workspace_bytes(n, capA)
-        if need == 0:
-            raise NmError("mutual-match workspace: n %r / capA %r out of range" % (n, capA))
-        self.n, self.capA = n, capA
-        self.buf = torch.empty(need, dtype=torch.uint8, device=device if device is not None else "cuda")
+        self._alloc(device, n=n, capA=capA)
+
+
+def _mutual_dev(dtype, entry, ws_cls, ws_shape, As, d_nAs, Bs, d_nBs, matches, capA, capB, results, workspace, want_distance):
+    """The device call of both mutual filters: descriptors of `dtype`, the C entry `entry`, a workspace of class `ws_cls`
+    whose shape is ws_shape(n, capA, capB)."""
+    torch = _torch()
+    n = _pair_count(As, d_nAs, Bs, d_nBs, matches, results)
+    capA, capB = _mutual_caps(As, Bs, matches, capA, capB)
+    device = _pair_device(list(As) + list(d_nAs) + list(Bs) + list(d_nBs) + list(matches) + list(results or ()) +
+                          [workspace.buf if workspace is not None else None], list(d_nAs) + list(d_nBs))
+    results, count, fwd = _pair_dev_match_out(n, capA, results, device, want_distance)
+    if {r.data_ptr() for r in results} & {m.data_ptr() for m in matches}:
+        raise NmError("a result tensor is also a match list")
+    workspace = _pair_workspace(ws_cls, workspace, device, *ws_shape(n, capA, capB))
+    arr, f, i32 = _pair_dev_table, torch.float32, torch.int32
+    _check(getattr(lib(), entry)(n, arr(As, dtype), arr(d_nAs, i32), capA, arr(Bs, dtype), arr(d_nBs, i32), capB,
+                                 arr(matches, i32), arr(results, i32), _dev(count), arr(fwd, f), _dev(workspace.buf),
+                                 _stream()), entry)
+    return (results, count) + ((fwd,) if want_distance else ())
+
+
+def _mutual_host(np_dtype, entry, As, nAs, Bs, nBs, matches, capA, capB, want_distance):
+    """The host twin of both mutual filters: descriptors of `np_dtype`, the C entry `entry`."""
+    import numpy as np
+    n = _pair_count(As, nAs, Bs, nBs, matches)
+    As, Bs = (_pair_host_arrays(vs, np_dtype, flat=False) for vs in (As, Bs))
+    matches = _pair_host_arrays(matches, np.int32, flat=False)
+    capA, capB = _mutual_caps(As, Bs, matches, capA, capB)
+    nA, nB = _pair_host_sizes(nAs), _pair_host_sizes(nBs)
+    result, count, fwd = _pair_host_match_out(n, capA, want_distance)
+    arr = _pair_host_table
+    _check(getattr(lib(), entry)(n, arr(As), arr(nA), capA, arr(Bs), arr(nB), capB, arr(matches), arr(list(result)),
+                                 _pair_host_ptr(count), arr(list(fwd)) if want_distance else None), entry)
+    return (result, count) + ((fwd,) if want_distance else ())
 
 
 def sift_match_mutual_batch_dev(As, d_nAs, Bs, d_nBs, matches, capA=None, capB=None, results=None, workspace=None,
@@ -1068,42 +1113,16 @@ def sift_match_mutual_batch_dev(As, d_nAs, Bs, d_nBs, matches, capA=None, capB=N
     be a match list). workspace: a MatchMutualWorkspace (default: new). Returns (results, count[n]) and, with
     want_distance, the list of float32 (capA,) forward distances (+inf for a row without a claim). results[k] plugs into
     ransac_batch_dev, ransac_refit_batch_dev and align_points as matches."""
-    torch = _torch()
-    n = _pair_count(As, d_nAs, Bs, d_nBs, matches, results)
-    capA, capB = _mutual_caps(As, Bs, matches, capA, capB)
-    device = _pair_device(list(As) + list(d_nAs) + list(Bs) + list(d_nBs) + list(matches) + list(results or ()) +
-                          [workspace.buf if workspace is not None else None], list(d_nAs) + list(d_nBs))
-    results, count, fwd = _pair_dev_match_out(n, capA, results, device, want_distance)
-    if {r.data_ptr() for r in results} & {m.data_ptr() for m in matches}:
-        raise NmError("a result tensor is also a match list")
-    if workspace is None:
-        workspace = MatchMutualWorkspace(n, capA, device)
-    need = lib().nm_sift_match_mutual_workspace_bytes(n, capA)
-    if need == 0 or workspace.buf.numel() < need:
-        raise NmError("mutual-match workspace too small")
-    arr, f, i32 = _pair_dev_table, torch.float32, torch.int32
-    _check(lib().nm_sift_match_mutual_batch_dev_f32(n, arr(As, f), arr(d_nAs, i32), capA, arr(Bs, f), arr(d_nBs, i32), capB,
-                                                    arr(matches, i32), arr(results, i32), _dev(count), arr(fwd, f),
-                                                    _dev(workspace.buf), _stream()), "nm_sift_match_mutual_batch_dev_f32")
-    return (results, count) + ((fwd,) if want_distance else ())
+    return _mutual_dev(_torch().float32, "nm_sift_match_mutual_batch_dev_f32", MatchMutualWorkspace,
+                       lambda n, capA, capB: (n, capA), As, d_nAs, Bs, d_nBs, matches, capA, capB, results, workspace,
+                       want_distance)
 
 
 def sift_match_mutual_host(As, nAs, Bs, nBs, matches, capA=None, capB=None, want_distance=False):
     """sift_match_mutual_batch_dev on the host (nm_sift_match_mutual_host_f32, the same functions): numpy in and out,
     bit-identical results. nAs / nBs are host ints. Returns (results (n, capA) int32, count (n,)) and, with want_distance,
     forward distances (n, capA) float32."""
-    import numpy as np
-    n = _pair_count(As, nAs, Bs, nBs, matches)
-    As, Bs = (_pair_host_arrays(vs, np.float32, flat=False) for vs in (As, Bs))
-    matches = _pair_host_arrays(matches, np.int32, flat=False)
-    capA, capB = _mutual_caps(As, Bs, matches, capA, capB)
-    nA, nB = _pair_host_sizes(nAs), _pair_host_sizes(nBs)
-    result, count, fwd = _pair_host_match_out(n, capA, want_distance)
-    arr = _pair_host_table
-    _check(lib().nm_sift_match_mutual_host_f32(n, arr(As), arr(nA), capA, arr(Bs), arr(nB), capB, arr(matches),
-                                               arr(list(result)), _pair_host_ptr(count), arr(list(fwd)) if want_distance else None),
-           "nm_sift_match_mutual_host_f32")
-    return (result, count) + ((fwd,) if want_distance else ())
+    return _mutual_host("float32", "nm_sift_match_mutual_host_f32", As, nAs, Bs, nBs, matches, capA, capB, want_distance)
 
 
 # ---- descriptor finish and the u8 matcher ----
@@ -1178,16 +1197,12 @@ def _u8_caps(As, Bs, results, capA, capB):
     return _pair_cap(capA, list(As) + list(results or ())), _pair_cap(capB, list(Bs))
 
 
-class MatchU8Workspace:
+class MatchU8Workspace(_PairWorkspace):
     """Device scratch of sift_match_u8_batch_dev for up to n pairs of capA x capB rows (the integer row norms)."""
+    _bytes_fn, _what, _shape_text = "nm_sift_match_u8_workspace_bytes", "u8-match workspace", "n %r / capA %r / capB %r"
 
     def __init__(self, n, capA, capB, device=None):
-        torch = _torch()
-        need = lib().nm_sift_match_u8_workspace_bytes(n, capA, capB)
-        if need == 0:
-            raise NmError("u8-match workspace: n %r / capA %r / capB %r out of range" % (n, capA, capB))
-        self.n, self.capA, self.capB = n, capA, capB
-        self.buf = torch.empty(need, dtype=torch.uint8, device=device if device is not None else "cuda")
+        self._alloc(device, n=n, capA=capA, capB=capB)
 
 
 def sift_match_u8_batch_dev(As, d_nAs, Bs, d_nBs, results=None, ambiguity=0.8, workspace=None, capA=None, capB=None):
@@ -1204,11 +1219,7 @@ def sift_match_u8_batch_dev(As, d_nAs, Bs, d_nBs, results=None, ambiguity=0.8, w
                           [workspace.buf if workspace is not None else None], list(d_nAs) + list(d_nBs))
     if results is None:
         results = [torch.full((capA,), -1, dtype=torch.int32, device=device) for _ in range(n)]
-    if workspace is None:
-        workspace = MatchU8Workspace(n, capA, capB, device)
-    need = lib().nm_sift_match_u8_workspace_bytes(n, capA, capB)
-    if need == 0 or workspace.buf.numel() < need:
-        raise NmError("u8-match workspace too small")
+    workspace = _pair_workspace(MatchU8Workspace, workspace, device, n, capA, capB)
     arr, u8, i32 = _pair_dev_table, torch.uint8, torch.int32
     _check(lib().nm_sift_match_u8_batch_dev(n, arr(As, u8), arr(d_nAs, i32), capA, arr(Bs, u8), arr(d_nBs, i32), capB,
                                             arr(results, i32), float(ambiguity), _dev(workspace.buf), _stream()),
@@ -1232,17 +1243,13 @@ def sift_match_u8_host(As, nAs, Bs, nBs, ambiguity=0.8, capA=None, capB=None, pr
     return result
 
 
-class MatchMutualU8Workspace:
+class MatchMutualU8Workspace(_PairWorkspace):
     """Device scratch of sift_match_mutual_u8_batch_dev for up to n pairs of capA x capB rows (the integer norms of A's
     rows and the compacted claims)."""
+    _bytes_fn, _what, _shape_text = "nm_sift_match_mutual_u8_workspace_bytes", "mutual-u8 workspace", "n %r / capA %r / capB %r"
 
     def __init__(self, n, capA, capB, device=None):
-        torch = _torch()
-        need = lib().nm_sift_match_mutual_u8_workspace_bytes(n, capA, capB)
-        if need == 0:
-            raise NmError("mutual-u8 workspace: n %r / capA %r / capB %r out of range" % (n, capA, capB))
-        self.n, self.capA, self.capB = n, capA, capB
-        self.buf = torch.empty(need, dtype=torch.uint8, device=device if device is not None else "cuda")
+        self._alloc(device, n=n, capA=capA, capB=capB)
 
 
 def sift_match_mutual_u8_batch_dev(As, d_nAs, Bs, d_nBs, matches, capA=None, capB=None, results=None, workspace=None,
@@ -1256,42 +1263,16 @@ def sift_match_mutual_u8_batch_dev(As, d_nAs, Bs, d_nBs, matches, capA=None, cap
     Returns (results, count[n]) and, with want_distance, the list of float32 (capA,) forward distances (+inf for a row
     without a claim). The outputs equal sift_match_mutual_batch_dev's on float copies of the same bytes bit for bit.
     results[k] plugs into ransac_batch_dev, ransac_refit_batch_dev and align_points as matches."""
-    torch = _torch()
-    n = _pair_count(As, d_nAs, Bs, d_nBs, matches, results)
-    capA, capB = _mutual_caps(As, Bs, matches, capA, capB)
-    device = _pair_device(list(As) + list(d_nAs) + list(Bs) + list(d_nBs) + list(matches) + list(results or ()) +
-                          [workspace.buf if workspace is not None else None], list(d_nAs) + list(d_nBs))
-    results, count, fwd = _pair_dev_match_out(n, capA, results, device, want_distance)
-    if {r.data_ptr() for r in results} & {m.data_ptr() for m in matches}:
-        raise NmError("a result tensor is also a match list")
-    if workspace is None:
-        workspace = MatchMutualU8Workspace(n, capA, capB, device)
-    need = lib().nm_sift_match_mutual_u8_workspace_bytes(n, capA, capB)
-    if need == 0 or workspace.buf.numel() < need:
-        raise NmError("mutual-u8 workspace too small")
-    arr, u8, f, i32 = _pair_dev_table, torch.uint8, torch.float32, torch.int32
-    _check(lib().nm_sift_match_mutual_u8_batch_dev(n, arr(As, u8), arr(d_nAs, i32), capA, arr(Bs, u8), arr(d_nBs, i32), capB,
-                                                   arr(matches, i32), arr(results, i32), _dev(count), arr(fwd, f),
-                                                   _dev(workspace.buf), _stream()), "nm_sift_match_mutual_u8_batch_dev")
-    return (results, count) + ((fwd,) if want_distance else ())
+    return _mutual_dev(_torch().uint8, "nm_sift_match_mutual_u8_batch_dev", MatchMutualU8Workspace,
+                       lambda n, capA, capB: (n, capA, capB), As, d_nAs, Bs, d_nBs, matches, capA, capB, results, workspace,
+                       want_distance)
 
 
 def sift_match_mutual_u8_host(As, nAs, Bs, nBs, matches, capA=None, capB=None, want_distance=False):
     """sift_match_mutual_u8_batch_dev on the host (nm_sift_match_mutual_u8_host): numpy in and out, identical results.
     nAs / nBs are host ints. Returns (results (n, capA) int32, count (n,)) and, with want_distance, forward distances
     (n, capA) float32."""
-    import numpy as np
-    n = _pair_count(As, nAs, Bs, nBs, matches)
-    As, Bs = (_pair_host_arrays(vs, np.uint8, flat=False) for vs in (As, Bs))
-    matches = _pair_host_arrays(matches, np.int32, flat=False)
-    capA, capB = _mutual_caps(As, Bs, matches, capA, capB)
-    nA, nB = _pair_host_sizes(nAs), _pair_host_sizes(nBs)
-    result, count, fwd = _pair_host_match_out(n, capA, want_distance)
-    arr = _pair_host_table
-    _check(lib().nm_sift_match_mutual_u8_host(n, arr(As), arr(nA), capA, arr(Bs), arr(nB), capB, arr(matches),
-                                              arr(list(result)), _pair_host_ptr(count), arr(list(fwd)) if want_distance else None),
-           "nm_sift_match_mutual_u8_host")
-    return (result, count) + ((fwd,) if want_distance else ())
+    return _mutual_host("uint8", "nm_sift_match_mutual_u8_host", As, nAs, Bs, nBs, matches, capA, capB, want_distance)
 
 
 MOSAIC_MAX_BATCH = 64

@@ -13,7 +13,6 @@ namespace {
 
 constexpr int TB = 256;                     // four waves = four rows per workgroup
 constexpr int ROWS = TB / 64;
-static_assert(NM_DESC_FINISH_MAX_BATCH == nmp::MAX_BATCH, "public header and pair-batch convention disagree");
 
 struct FinishArgs {                         // 4 x 64 pointers: 2 KB of kernel arguments
     const float *desc[NM_DESC_FINISH_MAX_BATCH];

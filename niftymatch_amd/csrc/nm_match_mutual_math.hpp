@@ -1,7 +1,7 @@
 // nm_match_mutual_math.hpp -- mutual-nearest-neighbour filtering of a match list (nm_sift_match_mutual_batch_dev_f32 and its
 // host twin), for gfx950. No reference counterpart: the reference's matcher (kernels/match.cu) tests one direction only; a
 // client that wants a cross-check calls it a second time with the sets swapped. Everything here is __host__ __device__ and
-// is the ONLY arithmetic of both entries, so host and device agree bit for bit: the claim test, the 128-D distance of
+// is the ONLY arithmetic of both entries, so host and device agree bit for bit: the claim test and the verdict (nm_pair_batch.hpp), the 128-D distance of
 // nm_bf_distance_f32 (acc = fma(t, t, acc), t = a_q - b_q, q ascending) cut into chunks of NMM_CHUNK dimensions with the
 // test that abandons a rival row, and the keep rule. The chain never decreases (t * t >= 0, rounding is monotone, a NaN stays
 // a NaN), so a rival whose partial sum is no longer <= tau cannot end below or at tau: abandoning it changes no result.
@@ -17,10 +17,9 @@ namespace nmm {
 constexpr int NMM_CHUNK = 16;                       // dimensions between two looks at the partial sum
 constexpr int NMM_CHUNKS = 128 / NMM_CHUNK;
 
+using nmp::beats;                                   // the verdict on a rival that ran to the end
 using nmp::clip;
-
-/* Row i claims column j = matches[i]: any value outside [0, nB) is no claim */
-__host__ __device__ __forceinline__ bool is_claim(int j, int nB) { return j >= 0 && j < nB; }
+using nmp::is_claim;
 
 /* The next NMM_CHUNK links of the chain: a and b point at dimension q0 of the rival row and of the claimed column */
 __host__ __device__ __forceinline__ float chunk(float acc, const float *a, const float *b)
@@ -35,9 +34,6 @@ __host__ __device__ __forceinline__ float chunk(float acc, const float *a, const
 
 /* A rival with this partial sum can still beat or tie tau. False for a NaN on either side: NaN rivals and NaN claims drop out. */
 __host__ __device__ __forceinline__ bool alive(float acc, float tau) { return acc <= tau; }
-
-/* Rival row ip with full distance d takes column j from row i: strictly nearer, or as near and earlier in the scan */
-__host__ __device__ __forceinline__ bool beats(float d, int ip, float tau, int i) { return d < tau || (d == tau && ip < i); }
 
 /* The keep rule: tau is a number and no rival beat it */
 __host__ __device__ __forceinline__ bool keep(float tau, bool beaten) { return tau == tau && !beaten; }

@@ -5,19 +5,17 @@
 // TWO launches per call whatever n is, on the caller's stream, no allocation, no synchronisation, no host read:
 //   1. norms (grid ceil(rows / 256) x 2 x n): one lane per row, |row - 128|^2 as an int into the workspace. Rows of B at and
 //      beyond nB (up to the next multiple of 32) get PAD_NORM, which puts their distances above every real one.
-//   2. match (grid ceil(capA / 256) x n): a wave owns 64 queries as two groups of 32 and keeps their four k-step fragments
-//      (bytes - 128 as signed i8, 16 bytes per lane and step) in 32 registers as the B operand of
-//      v_mfma_i32_32x32x32_i8; it streams the candidates in tiles of 32 as the A operand straight from global memory
-//      (a tile is 4 KB, one 16-byte read per lane and k step; the next tile is requested before this one is multiplied).
-//      The accumulator holds a query on its column (lane & 31) and the candidates (e & 3) + 8 (e >> 2) + 4 (lane >> 5) in
-//      its 16 registers e; d = |a|^2 + |b|^2 - 2 a.b. Per tile the two smallest keys (d << 4 | e) are found with min / max
+//   2. match (grid ceil(capA / 256) x n), on the tile stream of nm_match_u8_dev.hpp: a wave owns 64 queries and keeps their
+//      fragments as the B operand of v_mfma_i32_32x32x32_i8; it streams the candidates (a tile is 4 KB, one 16-byte read
+//      per lane and k step). d = |a|^2 + |b|^2 - 2 a.b. Per tile the two smallest keys (d << 4 | e) are found with min / max
 //      and merged into the lane's running (min1, index, min2) only when the wave votes that some lane needs it. Ascending
 //      e is ascending candidate index inside a lane, tiles ascend, and every comparison that replaces is strict, so the
 //      lowest index wins a tie; the two lane halves (same query, disjoint candidates) are merged at the end by
 //      (distance, index). The last step is the reference's: min2 starts at 2139095040.0f, a row with min2 == 0 is left
 //      unwritten, result = min1 / min2 < ambiguity ? index : -1 with an fp32 divide.
 // No LDS, no atomics. The lane -> (row, k) map of the i8 operands is checked by tools/micro/mfma_i8_model.hip. The operand
-// fragments, the row norm and PAD_NORM are nm_match_u8_dev.hpp, shared with the mutual filter (nm_match_mutual_u8.hip).
+// fragments, the row norm, PAD_NORM and the tile stream are nm_match_u8_dev.hpp, shared with the mutual filter
+// (nm_match_mutual_u8.hip).
 #include "nm_common.hpp"
 #include "nm_match_u8_dev.hpp"
 #include "nm_pair_batch.hpp"
@@ -29,13 +27,9 @@ namespace {
 
 using namespace nmu8;
 
-constexpr int TB = 256;                     // four waves
-constexpr int QG = 2;                       // query groups of 32 per wave
-constexpr int QW = 32 * QG;                 // queries per wave
 constexpr int QB = QW * TB / 64;            // queries per workgroup
 constexpr int NO_SECOND = 1 << 24;          // a min2 at or above this is "no second candidate"
 constexpr float MIN2_INIT = 2139095040.0f;  // match.cu:91, the int 0x7f800000 converted
-static_assert(NM_MATCH_U8_MAX_BATCH == nmp::MAX_BATCH, "public header and pair-batch convention disagree");
 
 struct NormArgs {
     const unsigned char *A[NM_MATCH_U8_MAX_BATCH];
@@ -97,33 +91,22 @@ __global__ __launch_bounds__(TB) void match_u8_kernel(const MatchArgs a, int cap
     const int q0 = blockIdx.x * QB + (threadIdx.x >> 6) * QW;
     if (q0 >= nA) return;                                            // uniform over the wave; no barrier follows
     const unsigned char *__restrict__ Ad = a.A[k];
-    const unsigned char *__restrict__ Bd = a.B[k];
     const int *__restrict__ na = norms_of(ws, k, capA, capB);
-    const int *__restrict__ nb = na + rows_a(capA);
 
     Frag qf[QG];
     int nq[QG], m1[QG], i1[QG], m2[QG];
 #pragma unroll
     for (int g = 0; g < QG; ++g) {
-        const int qi = q0 + 32 * g + r, qrow = qi < nA ? qi : nA - 1;   // a lane past nA repeats the last row and writes nothing
+        const int qrow = last_real(q0 + 32 * g + r, nA);             // a lane past nA repeats the last row and writes nothing
         qf[g] = load_frag(Ad + (size_t)qrow * DIM, h);
         nq[g] = na[qrow];
         m1[g] = KEY_INF; m2[g] = KEY_INF; i1[g] = 0;
     }
 
-    const int tiles = (nB + TILE - 1) / TILE;
-    auto cand_row = [&](int t) { const int c = t * TILE + r; return Bd + (size_t)(c < nB ? c : nB - 1) * DIM; };
-    Frag cf = load_frag(cand_row(0), h);
-    Norm16 cn = load_norms(nb, 0, h);
-    for (int t = 0; t < tiles; ++t) {
-        const int tn = t + 1 < tiles ? t + 1 : t;                    // the last tile asks for itself
-        const Frag nf = load_frag(cand_row(tn), h);
-        const Norm16 nn = load_norms(nb, tn * TILE, h);
+    for_tiles(a.B[k], na + rows_a(capA), nB, 0, (nB + TILE - 1) / TILE, r, h, [&](int t, const Frag cf, const Norm16 cn) {
 #pragma unroll
         for (int g = 0; g < QG; ++g) {
-            i32x16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-            for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(cf.s[s], qf[g].s[s], acc, 0, 0, 0);
+            const i32x16 acc = tile_product(cf, qf[g]);
             int g1 = KEY_INF, g2 = KEY_INF;
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
@@ -134,18 +117,17 @@ __global__ __launch_bounds__(TB) void match_u8_kernel(const MatchArgs a, int cap
             }
             const int d1 = g1 >> 4;
             if (__any(d1 < m2[g])) {
-                const int d2 = g2 >> 4, e1 = g1 & 15;
+                const int d2 = g2 >> 4;
                 if (d1 < m1[g]) {
                     m2[g] = min(m1[g], d2);
                     m1[g] = d1;
-                    i1[g] = t * TILE + (e1 & 3) + 8 * (e1 >> 2) + 4 * h;
+                    i1[g] = acc_row(t, g1 & 15, h);
                 } else {
                     m2[g] = min(m2[g], d1);
                 }
             }
         }
-        cf = nf; cn = nn;
-    }
+    });
 
 #pragma unroll
     for (int g = 0; g < QG; ++g) {
@@ -195,8 +177,7 @@ extern "C" int nm_sift_match_u8_batch_dev(int n, const unsigned char *const *A, 
                                           const unsigned char *const *B, const int *const *d_nB, int capB,
                                           int *const *result, float ambiguity, void *workspace, void *stream)
 {
-    if (!u8_args_ok(n, A, d_nA, capA, B, d_nB, capB, result) || !workspace || !aligned16(n, A) || !aligned16(n, B) ||
-        (reinterpret_cast<uintptr_t>(workspace) & 15u))
+    if (!u8_args_ok(n, A, d_nA, capA, B, d_nB, capB, result) || !workspace || !operands_aligned(n, A, B, workspace))
         return (int)hipErrorInvalidValue;
     NormArgs p;
     MatchArgs m;

@@ -1,9 +1,16 @@
 // nm_match_u8_dev.hpp -- what the two users of v_mfma_i32_32x32x32_i8 on unsigned-char descriptors share (nm_match_u8.hip, the
 // matcher, and nm_match_mutual_u8.hip, the mutual filter): the operand fragments of a 128-byte row (bytes - 128 as signed
-// i8), the integer row norm |row - 128|^2, the norm of a row that does not exist, and the alignment test of the entries.
+// i8), the integer row norm |row - 128|^2, the norm of a row that does not exist, the alignment test of the entries, and the
+// tile stream of their hot kernels.
 // A fragment is one lane's share of a row for the four k steps of a 32 x 32 x 128 product: lane (r = lane & 31, h = lane >>
 // 5) holds bytes 32 t + 16 h .. + 15 of row r in step t. The accumulator holds the B operand's row on its column (lane & 31)
 // and the A operand's rows (e & 3) + 8 (e >> 2) + 4 (lane >> 5) in its 16 registers e (tools/micro/mfma_i8_model.hip).
+// The tile stream: a wave owns QW = 64 items (queries, or compacted claims) as QG = 2 groups of 32, lane r of group g standing
+// for item first + 32 g + r (last_real keeps a lane past the end on the last item; such a lane stores nothing), and holds
+// their fragments Frag qf[QG] in 32 registers as the B operand. for_tiles streams the other side's rows in tiles of 32 as the
+// A operand straight from global memory, the next tile and its norms requested before this one is used; per tile the kernel's
+// body takes tile_product(cf, qf[g]) (a.b of 32 x 32 rows over the 4 k steps) and decodes a register with acc_row. What a
+// kernel makes of the 16 accumulators (a running top-2, a threshold test) is its own.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -16,6 +23,9 @@ typedef int i32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int DIM = 128;
 constexpr int TILE = 32;                    // rows of the A operand per MFMA tile
+constexpr int TB = 256;                     // four waves
+constexpr int QG = 2;                       // item groups of 32 per wave
+constexpr int QW = 32 * QG;                 // items per wave
 constexpr int PAD_NORM = 1 << 25;           // norm of a streamed row that does not exist: d >= 2^25 - 2^22 > 2^23
 constexpr int KEY_INF = 0x7fffffff;
 static_assert(DIM * 255 * 255 < (1 << 23) && ((PAD_NORM + (1 << 23)) >> 27) == 0, "keys (d << 4 | e) stay positive ints");
@@ -61,11 +71,49 @@ __device__ __forceinline__ Norm16 load_norms(const int *__restrict__ nb, int c0,
     return n;
 }
 
+/* Row c of n, or the last real one */
+__device__ __forceinline__ int last_real(int c, int n) { return c < n ? c : n - 1; }
+
+/* body(t, cf, cn) for the tiles t0 <= t < t1 of `rows` (n_rows real ones, rows past them repeat the last) and their `norms` */
+template <class Body>
+__device__ __forceinline__ void for_tiles(const unsigned char *__restrict__ rows, const int *__restrict__ norms, int n_rows,
+                                          int t0, int t1, int r, int h, Body body)
+{
+    auto cand_row = [&](int t) { return rows + (size_t)last_real(t * TILE + r, n_rows) * DIM; };
+    Frag cf = load_frag(cand_row(t0), h);
+    Norm16 cn = load_norms(norms, t0 * TILE, h);
+    for (int t = t0; t < t1; ++t) {
+        const int tn = t + 1 < t1 ? t + 1 : t;                       // the last tile asks for itself
+        const Frag nf = load_frag(cand_row(tn), h);
+        const Norm16 nn = load_norms(norms, tn * TILE, h);
+        body(t, cf, cn);
+        cf = nf; cn = nn;
+    }
+}
+
+/* a.b of the tile's 32 rows (cf, A operand) with the wave group's 32 items (qf, B operand): four k steps from zero */
+__device__ __forceinline__ i32x16 tile_product(const Frag &cf, const Frag &qf)
+{
+    i32x16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+    for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(cf.s[s], qf.s[s], acc, 0, 0, 0);
+    return acc;
+}
+
+/* The streamed row that register e of tile t's accumulator holds in lane half h */
+__device__ __forceinline__ int acc_row(int t, int e, int h) { return t * TILE + (e & 3) + 8 * (e >> 2) + 4 * h; }
+
 inline bool aligned16(int n, const unsigned char *const *t)
 {
     for (int k = 0; k < n; ++k)
         if (reinterpret_cast<uintptr_t>(t[k]) & 15u) return false;
     return true;
+}
+
+/* What both device entries ask of their pointers: 16-byte reads of every row, 16-byte parts of the workspace */
+inline bool operands_aligned(int n, const unsigned char *const *A, const unsigned char *const *B, const void *workspace)
+{
+    return aligned16(n, A) && aligned16(n, B) && !(reinterpret_cast<uintptr_t>(workspace) & 15u);
 }
 
 }  // namespace nmu8

@@ -17,10 +17,21 @@ namespace nmp {
 constexpr int MAX_BATCH = 64;               // pairs per call
 constexpr int CAP_LIMIT = 1 << 22;          // capacities (rows per pair) lie in [1, CAP_LIMIT)
 static_assert(NM_RANSAC_MAX_BATCH == MAX_BATCH && NM_MATCH_GUIDED_MAX_BATCH == MAX_BATCH &&
-              NM_MATCH_MUTUAL_MAX_BATCH == MAX_BATCH && NM_MATCH_MUTUAL_U8_MAX_BATCH == MAX_BATCH, "public header and pair-batch convention disagree");
+              NM_MATCH_MUTUAL_MAX_BATCH == MAX_BATCH && NM_MATCH_MUTUAL_U8_MAX_BATCH == MAX_BATCH &&
+              NM_MATCH_U8_MAX_BATCH == MAX_BATCH && NM_DESC_FINISH_MAX_BATCH == MAX_BATCH,
+              "public header and pair-batch convention disagree");
 
 /* A device size as the kernels (and the host twins) use it */
 __host__ __device__ __forceinline__ int clip(int v, int cap) { return v < 0 ? 0 : (v > cap ? cap : v); }
+
+/* The two predicates of the mutual filters (fp32 and u8, device and host twins). Row i claims column j = matches[i]: any
+ * value outside [0, nB) is no claim. Rival row ip at distance d takes the column from row i at distance tau: strictly
+ * nearer, or as near and earlier in the scan. A claim is kept exactly when no row of A beats it. */
+__host__ __device__ __forceinline__ bool is_claim(int j, int nB) { return j >= 0 && j < nB; }
+template <class D> __host__ __device__ __forceinline__ bool beats(D d, int ip, D tau, int i)
+{
+    return d < tau || (d == tau && ip < i);
+}
 
 __host__ __device__ __forceinline__ bool finite9(const float H[9])
 {

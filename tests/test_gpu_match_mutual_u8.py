@@ -2,7 +2,8 @@
 forward_distance against its host twin AND against sift_match_mutual_batch_dev (the fp32 filter) on float copies of the same
 bytes, over the cases of tests/mutual_u8_ref.py (sizes around the 32-row tile, the 64-claim wave, the 256-row workgroup and
 the 8-way range split, claim counts 0 / 1 / 64 / 65 / all, tied rows across every merge, shared columns, 0 against 255,
-clipped and empty sizes, ragged batches), slot independence, one 4096 x 4096 pair of finished real descriptors, and the
+clipped and empty sizes, ragged batches), slot independence, the two filters' shared claims stage on one two-workgroup batch
+with guarded workspaces and the pinned workspace sizes, one 4096 x 4096 pair of finished real descriptors, and the
 chain detect -> finish -> u8 match -> mutual u8 -> RANSAC captured into one HIP graph on a single stream and replayed on a
 second view pair. No tolerance and no excluded rows anywhere.
 """
@@ -100,6 +101,68 @@ def test_slot_independence(nm, cuda):
     for key in OUT:
         assert np.array_equal(_u32(alone[key][0]), _u32(again[key][0])), key
         assert np.array_equal(_u32(alone[key][0]), _u32(r[key][11])), key
+
+
+# *_workspace_bytes by hand from the layouts: the fp32 filter 512 + n 3 ceil(capA / 64) 64 4, the u8 filter
+# 256 + n (ceil(capA / 32) 32 + 4 ceil(capA / 64) 64) 4, the u8 matcher n (ceil(capA / 256) 256 + ceil(capB / 32) 32) 4
+WORKSPACE_BYTES = {(1, 1, 1): (1280, 1408, 1152), (2, 257, 33): (8192, 12800, 4608), (64, 4096, 4096): (3146240, 5243136, 2097152)}
+
+
+def test_shared_claims_stage_strides_and_claim_count(nm, cuda):
+    """Both filters on the same bytes, n = 2, capA = 257 (two claims workgroups, the second with one row), nA = (257, 0),
+    capB = 33, nB = (33, 1): pair 0 has claims on both sides of row 256, entries that are no claim, and rows 5 and 256 equal
+    to column 7 and claiming it (a tie across the workgroups: row 5 keeps it); pair 1 takes the nA == 0 path. Each call
+    equals its host twin and the other filter bit for bit, leaves m_k = (claims, 0) at the head of its workspace and a guard
+    behind *_workspace_bytes untouched; the three *_workspace_bytes functions return the values worked out by hand."""
+    import torch
+    L = nm.lib()
+    for (n, capA, capB), want in WORKSPACE_BYTES.items():
+        got = (L.nm_sift_match_mutual_workspace_bytes(n, capA), L.nm_sift_match_mutual_u8_workspace_bytes(n, capA, capB),
+               L.nm_sift_match_u8_workspace_bytes(n, capA, capB))
+        assert got == want, (n, capA, capB)
+    n, capA, capB, nA, nB = 2, 257, 33, (257, 0), (33, 1)
+    rng = np.random.default_rng(257)
+    A = [rng.integers(0, 256, (capA, 128), dtype=np.uint8) for _ in range(n)]
+    B = [rng.integers(0, 256, (capB, 128), dtype=np.uint8) for _ in range(n)]
+    A[0][5] = A[0][256] = B[0][7]
+    m0 = rng.integers(0, capB, capA).astype(np.int32)
+    m0[5] = m0[256] = 7
+    m0[[0, 100, 255]] = (-1, capB, 1 << 20)                          # no claims: below 0, == nB, far outside
+    m = [m0, np.zeros(capA, np.int32)]
+    claims = int(((m0 >= 0) & (m0 < capB)).sum())
+    assert 200 < claims == capA - 3
+
+    dev = lambda arrays: [torch.from_numpy(a).to(cuda) for a in arrays]
+    sizes = lambda ns: [torch.tensor([v], dtype=torch.int32, device=cuda) for v in ns]
+    out = {}
+    for name, cls, shape, call, host, conv in (
+            ("u8", nm.MatchMutualU8Workspace, (n, capA, capB), nm.sift_match_mutual_u8_batch_dev, nm.sift_match_mutual_u8_host,
+             lambda a: a),
+            ("f32", nm.MatchMutualWorkspace, (n, capA), nm.sift_match_mutual_batch_dev, nm.sift_match_mutual_host,
+             lambda a: a.astype(np.float32))):
+        ws = cls(*shape, cuda)
+        need = ws.buf.numel()
+        assert need == WORKSPACE_BYTES[(n, capA, capB)][0 if name == "f32" else 1]
+        guarded = torch.full((need + 64,), 0xA5, dtype=torch.uint8, device=cuda)
+        ws.buf = guarded[:need]
+        fA, fB = [conv(a) for a in A], [conv(b) for b in B]
+        res, cnt, fwd = call(dev(fA), sizes(nA), dev(fB), sizes(nB), dev(m), capA=capA, capB=capB, workspace=ws,
+                             want_distance=True)
+        torch.cuda.synchronize()
+        got = dict(result=np.stack([r.cpu().numpy() for r in res]), count=cnt.cpu().numpy(),
+                   forward=np.stack([f.cpu().numpy() for f in fwd]))
+        want = dict(zip(OUT, host(fA, nA, fB, nB, m, capA=capA, capB=capB, want_distance=True)))
+        for key in OUT:
+            assert np.array_equal(_u32(got[key]), _u32(want[key])), (name, key, "host twin")
+        assert (guarded[need:] == 0xA5).all(), name + ": bytes behind the workspace were written"
+        assert guarded[:8].view(torch.int32).tolist() == [claims, 0], name + ": m_k"
+        out[name] = got
+    for key in OUT:
+        assert np.array_equal(_u32(out["u8"][key]), _u32(out["f32"][key])), (key, "the two filters")
+    r = out["u8"]["result"]
+    assert r[0][5] == 7 and r[0][256] == -1 and out["u8"]["forward"][0][256] == 0.0
+    assert (r[1] == -1).all() and out["u8"]["count"][1] == 0 and np.isposinf(out["u8"]["forward"][1]).all()
+    assert 0 < out["u8"]["count"][0] < claims
 
 
 def test_finished_real_descriptors_4096(nm, cuda):
