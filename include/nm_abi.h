@@ -215,11 +215,13 @@ NM_API int nm_sift_set_detect_tall_min(int min_groups);
 /* Process-wide: issue order of detect/describe calls that take the per-octave launches (more frames than the octave tail
  * serves). 0: levels 1-5 of every octave on the caller's stream; 1: levels 4-5 go to the detection stream in front of the
  * octave's detection, so that the small octaves' launches run beside the large octaves'; 2 (cross): levels 4-5 go to a third
- * stream (the arena's description stream) instead, detection stays beside the next octave's levels 1-3 -- the call then uses
+ * stream (the call's description stream) instead, detection stays beside the next octave's levels 1-3 -- the call then uses
  * three streams, and a captured call is a graph with three parallel branches. Same launches and identical results in every
- * order (tests/test_gpu_frame_skew.py, tests/test_gpu_frame_cross.py). Any other value restores the default (NM_FRAME_SKEW in
- * the environment, read once; 0 when unset). Orders 1 and 2 apply to calls with one description pass that take the per-octave
- * launches; every other call is issued in order 0. Returns the previous value. */
+ * order (tests/test_gpu_frame_skew.py, tests/test_gpu_frame_cross.py). Any other value restores the default: NM_FRAME_SKEW in
+ * the environment (read once); when that is unset, order 2 for calls of at least NM_FRAME_CROSS_MIN_FRAMES frames (a build
+ * constant that the environment variable of the same name overrides, read once; 0 = never, the built-in value) and order 0 for
+ * all others. Orders 1 and 2 apply to calls with one description pass that take the per-octave launches; every other call is
+ * issued in order 0. Returns the previous value (for the default: NM_FRAME_SKEW's, 0 when unset). */
 NM_API int nm_sift_set_frame_skew(int mode);
 /* nm_compact_keypoints for three dense maps at once (three launches instead of nine); d_counts: 3 device ints. */
 NM_API size_t nm_compact3_workspace_bytes(int num_pixels);
@@ -873,7 +875,10 @@ NM_API int nm_frame_ingest_batch_f32(int n, const unsigned char *const *frames, 
 /* The per-octave client loop the reference leaves to its caller, run entirely on `stream` with no
  * host synchronisation and no allocation: Gaussian pyramid + DoG + gradients + extrema + ordered compaction +
  * orientations + descriptors of one grayscale fp32 frame. An arena owns every intermediate buffer
- * (replaces PyramidData, sift/pyramidata.cu:24-50) and is bound to one stream at a time.                        */
+ * (replaces PyramidData, sift/pyramidata.cu:24-50) and is bound to one stream at a time. The two helper streams and the
+ * events of a call belong to the caller's stream, not to an arena: the library keeps one set per caller stream and device
+ * (up to 16; calls on further streams use a set of their first arena's), made when a stream issues its first call -- or,
+ * for a call that is being captured, beforehand -- and kept until the process ends.                                */
 typedef struct nm_sift_arena nm_sift_arena;
 NM_API int nm_sift_arena_create(int width, int height, int capacity, nm_sift_arena **arena);
 NM_API void nm_sift_arena_destroy(nm_sift_arena *arena);
@@ -927,6 +932,15 @@ NM_API int nm_sift_tail_plan(int width, int height, int T, int *segments, int ma
  * (-1 none, 0 ev_pyr[octave], 1 ev_top[octave], 2 ev_det, 3 ev_desc, 4 ev_join). At most max_ops ops are written. Returns the
  * number of ops (<= 149), 0 for a configuration the driver never resolves to. Properties: tests/test_frame_plan.py. */
 NM_API int nm_sift_frame_plan(int num_octaves, int first_tail, int split, int write_dog, int order, int *ops, int max_ops);
+/* HOST function (no device access): the configuration the frame driver resolves a call of n frames to, on arenas of num_octaves
+ * octaves whose octave-tail plan starts at octave tail_first (0: no tail plan). selected_order: what nm_sift_set_frame_skew set,
+ * -1 for the default. split / cross_min_frames: NM_FRAME_SPLIT_DESCRIBE / NM_FRAME_CROSS_MIN_FRAMES as the call shall see them,
+ * < 0 for the process's own. cfg: num_octaves, first_tail, split, write_dog, order -- the arguments of nm_sift_frame_plan.
+ * Returns 0, hipErrorInvalidValue for arguments out of range. nm_sift_frame_cross_min_frames: the process's threshold (0: the
+ * cross order is never the default). Tests: tests/test_frame_plan_order_default.py. */
+NM_API int nm_sift_frame_resolve(int num_octaves, int tail_first, int n, int selected_order, int split, int cross_min_frames,
+                                 int cfg[5]);
+NM_API int nm_sift_frame_cross_min_frames(void);
 /* gray: width*height fp32 on the device. Outputs on the device: desc capacity x 128, x,y capacity (full-resolution
  * coordinates, descriptor.cu:75-77), d_num_items = number of descriptors written (<= capacity,
  * siftfunctions.cu:165-169). kpts (capacity float4) and orients (capacity float2) are optional (NULL).        */

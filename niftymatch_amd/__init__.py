@@ -138,6 +138,8 @@ _SIGNATURES = {
     "nm_sift_arena_launches_per_call": (_I, [_P, _I]),
     "nm_sift_tail_plan": (_I, [_I, _I, _I, _P, _I, _P]),
     "nm_sift_frame_plan": (_I, [_I, _I, _I, _I, _I, _P, _I]),
+    "nm_sift_frame_resolve": (_I, [_I, _I, _I, _I, _I, _I, _P]),
+    "nm_sift_frame_cross_min_frames": (_I, []),
     "nm_sift_arena_set_params": (_I, [_P, _F, _F]),
     "nm_sift_arena_get_params": (_I, [_P, _P, _P]),
     "nm_sift_arena_set_mask": (_I, [_P, _P, _I, _I]),

@@ -1,12 +1,111 @@
-// nm_arena.hip -- the frame driver's arena: creation (every buffer, stream, event and the octave-tail plan of one geometry),
-// destruction, the accessors and the thresholds / mask setters, and the octave tail's diagnostics. The driver that runs a call
-// on arenas is nm_frame.hip.
+// nm_arena.hip -- the frame driver's arena: creation (every buffer and the octave-tail plan of one geometry), destruction, the
+// accessors and the thresholds / mask setters, and the octave tail's diagnostics; and the per-device pool of helper sets (the
+// helper streams and events of a call). The driver that runs a call on arenas is nm_frame.hip.
 #include <algorithm>
+#include <mutex>
 #include <new>
 #include <vector>
 
 #include "nm_arena.hpp"
 #include "nm_frame_plan.hpp"
+
+// ---- helper sets ---------------------------------------------------------------------------------------------------------
+// A process used to hold two helper streams per arena (about 130 with the 64 arenas of a many-frame call) of which a call
+// only ever used the first arena's pair; which hardware queue those two shared with the caller's stream was then a matter of
+// where among all the others they had been created. Now a process holds two helper streams per caller stream in use, created
+// in the order in which the caller streams issue their first call.
+// (Round 5, measured: HIP stream priorities for the two helper streams -- the device offers 0 and -1 -- change nothing when one
+// of them is raised (headline 2 934-3 058 against 2 953-3 047) and cost 17 % when both are (2 479-2 498).)
+namespace {
+
+void helper_set_destroy(NmHelperSet *s)
+{
+    if (s->side) { (void)hipStreamSynchronize(s->side); (void)hipStreamDestroy(s->side); }
+    if (s->desc) { (void)hipStreamSynchronize(s->desc); (void)hipStreamDestroy(s->desc); }
+    for (int o = 0; o < 20; ++o) {
+        if (s->ev_pyr[o]) (void)hipEventDestroy(s->ev_pyr[o]);
+        if (s->ev_top[o]) (void)hipEventDestroy(s->ev_top[o]);
+    }
+    if (s->ev_join) (void)hipEventDestroy(s->ev_join);
+    if (s->ev_det) (void)hipEventDestroy(s->ev_det);
+    if (s->ev_desc) (void)hipEventDestroy(s->ev_desc);
+    *s = NmHelperSet{};
+}
+
+// On the current device. A set is geometry-free: it holds the events of all 20 octaves a plan can name.
+int helper_set_create(NmHelperSet *s)
+{
+    *s = NmHelperSet{};
+    int rc = 0;
+    for (int o = 0; !rc && o < 20; ++o) rc = (int)hipEventCreateWithFlags(&s->ev_pyr[o], hipEventDisableTiming);
+    for (int o = 0; !rc && o < 20; ++o) rc = (int)hipEventCreateWithFlags(&s->ev_top[o], hipEventDisableTiming);
+    if (!rc) rc = (int)hipEventCreateWithFlags(&s->ev_join, hipEventDisableTiming);
+    if (!rc) rc = (int)hipEventCreateWithFlags(&s->ev_det, hipEventDisableTiming);
+    if (!rc) rc = (int)hipEventCreateWithFlags(&s->ev_desc, hipEventDisableTiming);
+    if (!rc) rc = (int)hipStreamCreateWithFlags(&s->side, hipStreamNonBlocking);
+    if (!rc) rc = (int)hipStreamCreateWithFlags(&s->desc, hipStreamNonBlocking);
+    if (rc) helper_set_destroy(s);
+    return rc;
+}
+
+// sets[0, assigned) serve the caller streams key[.]; sets[assigned, created) are spares. A stream capture must not create
+// streams, so whenever the pool is touched outside a capture it makes sure that ONE spare stands ready: a capture on a caller
+// stream that has not issued a call yet then takes the spare. The sets live until the process ends: they are never destroyed
+// (a static destructor would run after the HIP runtime has begun to shut down), which leaks at most NM_HELPER_POOL_SETS sets
+// per device, once.
+struct HelperPool {
+    NmHelperSet sets[NM_HELPER_POOL_SETS];
+    hipStream_t key[NM_HELPER_POOL_SETS];
+    int assigned, created;
+};
+HelperPool g_pool[NM_HELPER_POOL_DEVICES] = {};
+std::mutex g_pool_mutex;
+
+void pool_reserve(HelperPool &p, int want)          // g_pool_mutex held, not capturing; failures leave the pool as it is
+{
+    want = std::min(want, NM_HELPER_POOL_SETS);
+    while (p.created < want && helper_set_create(&p.sets[p.created]) == 0) ++p.created;
+}
+
+bool capturing(hipStream_t st)
+{
+    hipStreamCaptureStatus status = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &status) != hipSuccess) {
+        (void)hipGetLastError();                    // e.g. the legacy stream while another stream captures: create nothing
+        return true;
+    }
+    return status != hipStreamCaptureStatusNone;
+}
+
+}  // namespace
+
+int nm_helper_set_acquire(nm_sift_arena *a0, hipStream_t caller, NmHelperSet **out)
+{
+    std::lock_guard<std::mutex> lock(g_pool_mutex);
+    if (a0->device >= 0 && a0->device < NM_HELPER_POOL_DEVICES) {
+        HelperPool &p = g_pool[a0->device];
+        for (int i = 0; i < p.assigned; ++i)
+            if (p.key[i] == caller) { *out = &p.sets[i]; return 0; }
+        const bool cap = capturing(caller);
+        if (!cap) pool_reserve(p, p.assigned + 1);
+        if (p.assigned < p.created) {
+            p.key[p.assigned] = caller;
+            *out = &p.sets[p.assigned++];
+            if (!cap) pool_reserve(p, p.assigned + 1);
+            return 0;
+        }
+    }
+    // the pool is full (or has nothing ready for a capture): the first arena's own set, made when first needed
+    if (!a0->own) {
+        NmHelperSet *s = new (std::nothrow) NmHelperSet();
+        if (!s) return (int)hipErrorOutOfMemory;
+        const int rc = helper_set_create(s);
+        if (rc) { delete s; return rc; }
+        a0->own = s;
+    }
+    *out = a0->own;
+    return 0;
+}
 
 extern "C" {
 
@@ -16,12 +115,10 @@ int nm_sift_arena_create(int width, int height, int capacity, nm_sift_arena **ou
     nm_sift_arena *a = new (std::nothrow) nm_sift_arena();
     if (!a) return (int)hipErrorOutOfMemory;
     a->width = width; a->height = height; a->capacity = capacity;
-    a->side = nullptr; a->ev_join = nullptr;
-    a->desc = nullptr; a->ev_det = nullptr; a->ev_desc = nullptr;
+    a->own = nullptr;
     a->mask = nullptr;
     a->device = -1;
     (void)hipGetDevice(&a->device);
-    for (int o = 0; o < 20; ++o) a->ev_pyr[o] = a->ev_top[o] = nullptr;
     a->params = SiftParams(width, height);
     a->npix = (size_t)width * height;
     a->bytes = 0;
@@ -60,15 +157,13 @@ int nm_sift_arena_create(int width, int height, int capacity, nm_sift_arena **ou
         if (!rc) rc = a->alloc(&blk, total);
         for (int o = 0; o < P._num_octaves; ++o) a->grad[o] = blk + a->grad_off[o];
     }
-    for (int o = 0; !rc && o < P._num_octaves; ++o) rc = (int)hipEventCreateWithFlags(&a->ev_pyr[o], hipEventDisableTiming);
-    for (int o = 0; !rc && o < P._num_octaves; ++o) rc = (int)hipEventCreateWithFlags(&a->ev_top[o], hipEventDisableTiming);
-    if (!rc) rc = (int)hipEventCreateWithFlags(&a->ev_join, hipEventDisableTiming);
-    if (!rc) rc = (int)hipEventCreateWithFlags(&a->ev_det, hipEventDisableTiming);
-    if (!rc) rc = (int)hipEventCreateWithFlags(&a->ev_desc, hipEventDisableTiming);
-    // (Round 5, measured: HIP stream priorities for these two streams -- the device offers 0 and -1 -- change nothing when one of
-    // them is raised (headline 2 934-3 058 against 2 953-3 047) and cost 17 % when both are (2 479-2 498).)
-    if (!rc) rc = (int)hipStreamCreateWithFlags(&a->side, hipStreamNonBlocking);
-    if (!rc) rc = (int)hipStreamCreateWithFlags(&a->desc, hipStreamNonBlocking);
+    // No streams and no events here: a call takes its helper set from the device's pool (nm_helper_set_acquire). An arena is
+    // never created inside a stream capture, so this is where the pool's spare set is made for a process whose FIRST call is
+    // captured.
+    if (a->device >= 0 && a->device < NM_HELPER_POOL_DEVICES) {
+        std::lock_guard<std::mutex> lock(g_pool_mutex);
+        pool_reserve(g_pool[a->device], g_pool[a->device].assigned + 1);
+    }
     a->max_blocks = height * nm_divup(width, NM_DET_SEG_W);
     a->stage_stride = (size_t)a->max_blocks * 256;
     if (!rc) rc = a->alloc(&a->staging, 3 * a->stage_stride * 4);
@@ -122,15 +217,10 @@ int nm_sift_arena_create(int width, int height, int capacity, nm_sift_arena **ou
 void nm_sift_arena_destroy(nm_sift_arena *a)
 {
     if (!a) return;
-    if (a->side) { (void)hipStreamSynchronize(a->side); (void)hipStreamDestroy(a->side); }
-    if (a->desc) { (void)hipStreamSynchronize(a->desc); (void)hipStreamDestroy(a->desc); }
-    if (a->ev_det) (void)hipEventDestroy(a->ev_det);
-    if (a->ev_desc) (void)hipEventDestroy(a->ev_desc);
-    for (int o = 0; o < 20; ++o)
-        if (a->ev_pyr[o]) (void)hipEventDestroy(a->ev_pyr[o]);
-    for (int o = 0; o < 20; ++o)
-        if (a->ev_top[o]) (void)hipEventDestroy(a->ev_top[o]);
-    if (a->ev_join) (void)hipEventDestroy(a->ev_join);
+    // The pool's sets stay: later calls on other arenas use them. Only a set of this arena's own (calls beyond the pool's cap
+    // that had this arena first) goes, behind the work still on its streams.
+    if (a->own) { helper_set_destroy(a->own); delete a->own; }
+    // (hipFree waits for the device's streams, the pooled helper streams among them, before it releases a buffer)
     for (void *p : a->allocs) (void)hipFree(p);
     delete a;
 }

@@ -28,12 +28,17 @@ static_assert(NM_FRAME_TAIL_MAX_FRAMES == NM_TAIL_MAX_FRAMES && NM_FRAME_MAX_OCT
 // caller's stream, detection beside the next octave's levels. 1 (skewed): only levels 1-3 -- all that the next octave's level 0
 // needs -- stay on the caller's stream; levels 4-5 go to the side stream in front of the octave's detection, so the chain
 // reaches the small octaves while the large launches of octaves 0-2 still run. Same launches, same results in either order.
-// NM_FRAME_SKEW (read once) is the default; nm_sift_set_frame_skew changes it per call. Off by default: measured, a 64-frame
-// call takes 7 904 us against 7 799 (profiles/r07_a_skew_alternation.txt) -- the side stream becomes one serial chain, and the
-// plain order's pairing of octave o's detection with octave o + 1's levels is lost.
-// 2 (cross): order 1 with levels 4-5 on a THIRD stream (the arena's desc stream, idle on this path), which keeps the plain
-// order's pairing: per octave o, levels 1-3 of octave o + 1 on the caller's stream, levels 4-5 of octave o on the third, detection
-// of octave o - 1 on the side stream.
+// Order 1 is off: measured, a 64-frame call takes 7 904 us against 7 799 (profiles/r07_a_skew_alternation.txt) -- the side stream
+// becomes one serial chain, and the plain order's pairing of octave o's detection with octave o + 1's levels is lost (DESIGN.md
+// section 9).
+// 2 (cross): order 1 with levels 4-5 on a THIRD stream (the helper set's description stream, idle on this path), which keeps the
+// plain order's pairing: per octave o, levels 1-3 of octave o + 1 on the caller's stream, levels 4-5 of octave o on the third,
+// detection of octave o - 1 on the side stream.
+// The order of a call is nm_frame_resolve's (nm_frame_plan.hpp): what nm_sift_set_frame_skew selected; else NM_FRAME_SKEW where
+// the environment names one (read once); else the cross order for calls of at least NM_FRAME_CROSS_MIN_FRAMES frames (a compile-
+// time value, NM_FRAME_CROSS_MIN_FRAMES in the environment overrides it, read once; 0 = never) and order 0 below that.
+// The three streams of a call are the caller's and the two of the helper set that nm_helper_set_acquire (nm_arena.hip) keeps for
+// that caller stream.
 // The schedule of every order is nm_frame_plan's (nm_frame_plan.hpp); what the orders rely on -- which stream touches which
 // planes and which event orders them -- is checked on that plan by tests/test_frame_plan.py.
 static std::atomic<int> g_frame_skew{-1};          // -1: the default
@@ -182,8 +187,7 @@ static NmFrameConfig resolve_call(const nm_sift_arena *const *as, int n_arenas, 
     NmArenaTail tails[NM_MAX_BATCH];
     for (int f = 0; f < n_arenas; ++f) tails[f] = NmArenaTail{as[f]->tail_ok, as[f]->tail.T, as[f]->tail.n_oct};
     const NmFrameSwitches &sw = nm_frame_switches();
-    const int order = g_frame_skew.load(std::memory_order_relaxed);
-    return nm_frame_resolve(as[0]->params._num_octaves, tails, n_arenas, n, sw, order < 0 ? sw.order : order);
+    return nm_frame_resolve(as[0]->params._num_octaves, tails, n_arenas, n, sw, g_frame_skew.load(std::memory_order_relaxed));
 }
 
 extern "C" {
@@ -211,6 +215,24 @@ int nm_sift_frame_plan(int num_octaves, int first_tail, int split, int write_dog
     return n;
 }
 
+// HOST function (no device access): nm_frame_resolve for a call of n frames on arenas of num_octaves octaves whose octave-tail
+// plan starts at tail_first (0: they have none). cfg: num_octaves, first_tail, split, write_dog, order -- nm_sift_frame_plan's
+// arguments.
+int nm_sift_frame_resolve(int num_octaves, int tail_first, int n, int selected_order, int split, int cross_min_frames, int cfg[5])
+{
+    if (!cfg || num_octaves < 1 || num_octaves > NM_FRAME_MAX_OCTAVES || n < 1 || tail_first < 0) return (int)hipErrorInvalidValue;
+    NmFrameSwitches sw = nm_frame_switches();
+    if (split >= 0) sw.split = split;
+    if (cross_min_frames >= 0) sw.cross_min_frames = cross_min_frames;
+    const bool tail = tail_first > 0 && tail_first < num_octaves;
+    const NmArenaTail t{tail, tail_first, tail ? num_octaves - tail_first : 0};
+    const NmFrameConfig c = nm_frame_resolve(num_octaves, &t, 1, n, sw, selected_order);
+    cfg[0] = c.num_octaves; cfg[1] = c.first_tail; cfg[2] = c.split; cfg[3] = c.dogs; cfg[4] = c.order;
+    return 0;
+}
+
+int nm_sift_frame_cross_min_frames(void) { return nm_frame_switches().cross_min_frames; }
+
 int nm_sift_octave_pyramid(nm_sift_arena *a, int ow, int oh, void *stream)
 {
     if (!a || ow <= 0 || oh <= 0 || (size_t)ow * oh > a->npix) return (int)hipErrorInvalidValue;
@@ -220,10 +242,11 @@ int nm_sift_octave_pyramid(nm_sift_arena *a, int ow, int oh, void *stream)
 // Frame driver for n <= NM_MAX_BATCH equally sized frames: EVERY launch covers all frames of the call (the frame index is
 // a grid dimension), so a call of 4 frames issues the same ~60 launches as a call of one, each 4x fatter. The
 // scale-space chain (base blur, decimations, 5 fused Gaussian launches per octave) runs on the caller's stream; extrema +
-// ordered compaction of octave o run on the first arena's side stream as soon as that octave's DoG planes exist, i.e.
+// ordered compaction of octave o run on the side stream as soon as that octave's DoG planes exist, i.e.
 // concurrently with the pyramid of octave o+1; orientation + descriptors follow on the side stream, which the caller's
-// stream joins at the end. Capture-safe (events only). The call resolves its path, plans it (nm_frame_plan.hpp), fills the
-// per-call arguments and walks the plan.
+// stream joins at the end. The helper streams and events are the set nm_helper_set_acquire keeps for the caller's stream, taken
+// before the first operation is enqueued. Capture-safe (events only; a capture takes a set made beforehand). The call resolves
+// its path, plans it (nm_frame_plan.hpp), fills the per-call arguments and walks the plan.
 //
 // Paths other than the plain one:
 // NM_FRAME_SPLIT_DESCRIBE=2 (experiment, off by default): octaves 0 and 1 hold ~98 % of a frame's keypoints; their
@@ -295,12 +318,16 @@ int nm_sift_detect_describe_batch(nm_sift_arena *const *as, int n, const float *
         tail_args.state = as[0]->tail_state;
     }
 
-    // every detection / description launch covers all frames of the call: the first arena's helper streams and events serve it
-    nm_sift_arena *const a0 = as[0];
-    const hipStream_t streams[3] = {nm_stream(stream), a0->side, a0->desc};
+    // every detection / description launch covers all frames of the call: ONE helper set serves it, the caller stream's
+    NmHelperSet *hs = nullptr;
+    {
+        const int e = nm_helper_set_acquire(as[0], nm_stream(stream), &hs);
+        if (e) return e;
+    }
+    const hipStream_t streams[3] = {nm_stream(stream), hs->side, hs->desc};
     auto event = [&](const NmFrameOp &p) {
-        return p.event == NM_FE_PYR ? a0->ev_pyr[p.octave] : p.event == NM_FE_TOP ? a0->ev_top[p.octave]
-               : p.event == NM_FE_DET ? a0->ev_det : p.event == NM_FE_DESC ? a0->ev_desc : a0->ev_join;
+        return p.event == NM_FE_PYR ? hs->ev_pyr[p.octave] : p.event == NM_FE_TOP ? hs->ev_top[p.octave]
+               : p.event == NM_FE_DET ? hs->ev_det : p.event == NM_FE_DESC ? hs->ev_desc : hs->ev_join;
     };
     auto issue = [&](const NmFrameOp &p) -> int {
         const hipStream_t st = streams[p.stream];
@@ -320,7 +347,7 @@ int nm_sift_detect_describe_batch(nm_sift_arena *const *as, int n, const float *
     };
     // A helper stream is forked once a wait has been issued on it. After an error nothing more is launched, but every forked
     // stream is still joined (the plan's last ops): a stream capture would otherwise be left with an unjoined fork, and the next
-    // call on these arenas could overtake helper-stream work still in flight.
+    // call on this stream could overtake helper-stream work still in flight.
     bool forked[3] = {false, false, false};
     int rc = 0;
     for (int k = 0; k < n_ops; ++k) {

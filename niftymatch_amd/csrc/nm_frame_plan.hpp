@@ -10,7 +10,7 @@ constexpr int NM_FRAME_MAX_OCTAVES = 20;
 constexpr int NM_FRAME_TAIL_MAX_FRAMES = 2;        // frames one octave-tail launch serves (= NM_TAIL_MAX_FRAMES, nm_tail.hpp)
 
 enum NmFrameStream { NM_FS_CALLER = 0,             // the caller's stream: base blur, the levels, the tail
-                     NM_FS_SIDE = 1,               // the first arena's side stream: detection, the description
+                     NM_FS_SIDE = 1,               // the helper set's side stream: detection, the description
                      NM_FS_DESC = 2 };             // its description stream: early description (split), levels 4-5 (cross order)
 enum NmFrameEvent { NM_FE_NONE = -1,
                     NM_FE_PYR = 0,                 // ev_pyr[octave]: behind the octave's last level on the caller's stream
@@ -43,9 +43,17 @@ struct NmFrameSwitches {
     int split;                 // NM_FRAME_SPLIT_DESCRIBE=k: describe the octaves < k early, on a stream of their own
     int tail_max_batch;        // NM_FRAME_TAIL_MAX_BATCH (2): calls of more frames take the per-octave launches
     int order;                 // NM_FRAME_SKEW (0): the issue order where nm_sift_set_frame_skew has not set one
+    bool order_env;            // NM_FRAME_SKEW is set: it then holds for calls of every size
+    int cross_min_frames;      // NM_FRAME_CROSS_MIN_FRAMES: calls of at least so many frames default to the cross order; 0: never
 };
 #ifndef NM_FRAME_SKEW_DEFAULT
 #define NM_FRAME_SKEW_DEFAULT 0
+#endif
+// Frames per call from which the cross order (2) is the default. 0 = never: measured on MI355X with the three streams on three
+// hardware queues, the cross order is 1-47 us per call SLOWER than order 0 for calls of 64, 32, 16 and 4 frames
+// (profiles/r12_a_cross_order_alternation.txt, r12_a_call_timeline_cross.txt).
+#ifndef NM_FRAME_CROSS_MIN_FRAMES
+#define NM_FRAME_CROSS_MIN_FRAMES 0
 #endif
 inline const NmFrameSwitches &nm_frame_switches()
 {
@@ -60,6 +68,10 @@ inline const NmFrameSwitches &nm_frame_switches()
         e = getenv("NM_FRAME_SKEW");
         const int m = e ? atoi(e) : NM_FRAME_SKEW_DEFAULT;
         v.order = (m >= 0 && m <= 2) ? m : NM_FRAME_SKEW_DEFAULT;
+        v.order_env = e != nullptr && m >= 0 && m <= 2;
+        e = getenv("NM_FRAME_CROSS_MIN_FRAMES");
+        v.cross_min_frames = e ? atoi(e) : NM_FRAME_CROSS_MIN_FRAMES;
+        if (v.cross_min_frames < 0) v.cross_min_frames = 0;
         return v;
     }();
     return s;
@@ -68,10 +80,14 @@ inline const NmFrameSwitches &nm_frame_switches()
 struct NmArenaTail { bool ok; int T, n_oct; };     // an arena's octave-tail plan (made when the arena was created)
 
 // THE path decision of a call of n frames on arenas with these tail plans (n_arenas of them: all of the call's for the
-// driver, one for nm_sift_arena_launches_per_call). order: what the caller selected (nm_sift_set_frame_skew or the default).
+// driver, one for nm_sift_arena_launches_per_call). selected: the order nm_sift_set_frame_skew set, -1 for the default -- which
+// is NM_FRAME_SKEW where the environment names one, else the cross order for calls of at least sw.cross_min_frames frames and
+// sw.order below that.
 inline NmFrameConfig nm_frame_resolve(int num_octaves, const NmArenaTail *tails, int n_arenas, int n, const NmFrameSwitches &sw,
-                                      int order)
+                                      int selected)
 {
+    const int order = (selected >= 0 && selected <= 2) ? selected
+                      : (!sw.order_env && sw.cross_min_frames > 0 && n >= sw.cross_min_frames) ? 2 : sw.order;
     NmFrameConfig c;
     c.num_octaves = num_octaves;
     c.dogs = sw.dogs ? 1 : 0;
