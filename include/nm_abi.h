@@ -711,6 +711,71 @@ NM_API int nm_sift_desc_finish_batch_dev(int n, const float *const *desc, const 
 NM_API int nm_sift_desc_finish_host(int n, const float *const *desc, const int *const *num_items, int capacity,
                                     float *const *out_f32, unsigned char *const *out_u8, int mode);
 
+/* ---- Keypoint selection: the strongest `keep` rows of a frame, spread over a gx x gy grid (no reference counterpart: the
+ * reference keeps the first `capacity` rows in octave / level / raster order, sift/siftdata.h:12-15, which at 1080p and 2048
+ * rows is a stripe along the top of the finest level). nm_sift_select_batch_dev selects in n in [1, NM_SELECT_MAX_BATCH]
+ * frames in FOUR launches on `stream` whatever n is (score, group, round, gather): no allocation, no synchronisation, no
+ * host read, so it can be captured into a HIP graph behind nm_sift_detect_describe_batch and in front of
+ * nm_sift_desc_finish_batch_dev. Every table is a HOST table of n device pointers; capacity is the room of every input and
+ * output of a frame, in rows:
+ *   d_num_items[k]  DEVICE int, the row count: m = clip(*d_num_items[k], 0, capacity); a negative count is 0;
+ *   x[k], y[k]      capacity floats, full-resolution coordinates in a width x height frame (an arena's x, y);
+ *   scores[k]       optional table: capacity floats. Without it desc is required and gives the default score;
+ *   desc[k], desc_u8[k], kpts[k], orients[k]   optional payload tables: capacity x 128 floats (8-byte aligned) / capacity x 128
+ *                   unsigned chars (2-byte aligned) / capacity float4 / capacity float2;
+ *   out_x[k] .. out_orients[k]   the same shapes; an out_* table is required exactly when its input table is given;
+ *   out_index[k]    optional: capacity ints, the source row of each output row;
+ *   d_out_items[k]  DEVICE int.
+ * Per frame, from that frame's inputs alone (never n, the slot or scheduling):
+ *   1. Score: s_i = scores[k][i], or without scores step 1 of the finish on desc[k]'s row i, v = its 128 elements:
+ *      s_i = sum(fmaf(v[2l+1], v[2l+1], v[2l] * v[2l])) with the finish's sum(p) (64 pairs, xor butterfly d = 32 .. 1): the
+ *      squared norm of the raw histogram, bit-identical on host and device (csrc/nm_select_math.hpp).
+ *      u_i = s_i when s_i > 0 and finite, else +0: NaN, negative, zero and infinite scores rank last.
+ *   2. Cell: cw = DivUp(width, gx), ch = DivUp(height, gy). xi = 0 unless x_i >= 0 (a NaN lands in pixel 0), width - 1 when
+ *      x_i >= width, else (int)x_i; yi the same in height. cell = (yi / ch) * gx + xi / cw.
+ *   3. Beats: row i beats row j when u_i > u_j, or u_i == u_j and i < j.
+ *   4. Round: r_i = the number of rows of i's cell that beat i.
+ *   5. Precedence: i precedes j when r_i < r_j, or r_i == r_j and i beats j: every cell's best, strongest first, then every
+ *      cell's second best, ...
+ *   6. Selected: the first min(keep, m) rows of that total order.
+ *   7. Output: the selected rows in ASCENDING SOURCE INDEX (the octave / level / raster order the matcher's first-minimum
+ *      rule and every later stage see), copied byte for byte to every given out_* table; out_index[k][t] = the source row
+ *      of output row t; *d_out_items[k] = min(keep, m). Rows at and beyond that count are not written. No output may
+ *      overlap an input or another output.
+ * It follows: gx = gy = 1 is the top keep rows by score; keep >= m copies the frame; a cell's selected rows are its best
+ * ones; the selected counts of two cells differ by more than one only when the smaller cell is exhausted; with keep no
+ * smaller than the number of non-empty cells every non-empty cell has a selected row.
+ * Cost: the round launch compares every row with the rows of its own cell, sum over cells of size^2 key compares -- all
+ * rows in one cell is capacity^2, which is why capacity stops at 65536.
+ * workspace: device, 8-byte aligned, nm_sift_select_workspace_bytes(n, capacity, gx, gy) bytes (0 for arguments out of
+ * range), no contents expected or preserved.
+ * Returns hipErrorInvalidValue, before anything is launched or dereferenced, for n not in [1, 64], capacity not in
+ * [1, 65536], gx or gy not in [1, 64], keep not in [1, capacity], width or height < 1, a NULL d_num_items, x, y, out_x,
+ * out_y, d_out_items or workspace (or a workspace that is not 8-byte aligned), neither scores nor desc, an out_* table without
+ * its input table or the reverse, a NULL among the first n entries of a given table, or an output pointer equal to its
+ * input pointer.
+ * nm_sift_select_host: the same with every pointer in host memory, no workspace and no stream, from the same score, cell
+ * and key functions and the same argument checks: host and device results are identical bit for bit.                   */
+#define NM_SELECT_MAX_BATCH 64
+#define NM_SELECT_MAX_CAPACITY 65536
+#define NM_SELECT_MAX_GRID 64
+NM_API size_t nm_sift_select_workspace_bytes(int n, int capacity, int gx, int gy);
+NM_API int nm_sift_select_batch_dev(int n, int capacity, int width, int height, int gx, int gy, int keep,
+                                    const int *const *d_num_items, const float *const *x, const float *const *y,
+                                    const float *const *scores, const float *const *desc,
+                                    const unsigned char *const *desc_u8, const float *const *kpts,
+                                    const float *const *orients, float *const *out_x, float *const *out_y,
+                                    float *const *out_desc, unsigned char *const *out_desc_u8, float *const *out_kpts,
+                                    float *const *out_orients, int *const *out_index, int *const *d_out_items,
+                                    void *workspace, void *stream);
+NM_API int nm_sift_select_host(int n, int capacity, int width, int height, int gx, int gy, int keep,
+                               const int *const *num_items, const float *const *x, const float *const *y,
+                               const float *const *scores, const float *const *desc, const unsigned char *const *desc_u8,
+                               const float *const *kpts, const float *const *orients, float *const *out_x,
+                               float *const *out_y, float *const *out_desc, unsigned char *const *out_desc_u8,
+                               float *const *out_kpts, float *const *out_orients, int *const *out_index,
+                               int *const *out_items);
+
 /* ---- Brute-force matching of unsigned-char descriptors on the i8 matrix cores (no reference counterpart: the reference
  * matches fp32 rows). n in [1, NM_MATCH_U8_MAX_BATCH] pairs in TWO launches on `stream` whatever n is (row norms, match);
  * no allocation, no synchronisation, no host read. Pair k (HOST tables of n device pointers):

@@ -118,6 +118,9 @@ _SIGNATURES = {
     "nm_sift_match_mutual_host_f32": (_I, [_I, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P]),
     "nm_sift_desc_finish_batch_dev": (_I, [_I, _P, _P, _I, _P, _P, _I, _P]),
     "nm_sift_desc_finish_host": (_I, [_I, _P, _P, _I, _P, _P, _I]),
+    "nm_sift_select_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
+    "nm_sift_select_batch_dev": (_I, [_I] * 7 + [_P] * 18),
+    "nm_sift_select_host": (_I, [_I] * 7 + [_P] * 16),
     "nm_sift_match_u8_workspace_bytes": (_SZ, [_I, _I, _I]),
     "nm_sift_match_u8_batch_dev": (_I, [_I, _P, _P, _I, _P, _P, _I, _P, _F, _P, _P]),
     "nm_sift_match_u8_host": (_I, [_I, _P, _P, _I, _P, _P, _I, _P, _F]),
@@ -1192,6 +1195,109 @@ def desc_finish_host(descs, counts, mode=DESC_L2, want_f32=True, want_u8=True, c
     _check(lib().nm_sift_desc_finish_host(n, arr(src), arr(cnt), capacity, arr(list(f32)) if want_f32 else None,
                                           arr(list(u8)) if want_u8 else None, mode), "nm_sift_desc_finish_host")
     return f32, u8
+
+
+SELECT_MAX_BATCH = _PAIR_MAX_BATCH
+SELECT_MAX_CAPACITY = 65536
+SELECT_MAX_GRID = 64
+# the payload of a selection: name -> (dtype name, trailing shape); x and y are required, the rest optional
+_SELECT_PAYLOAD = (("x", "float32", ()), ("y", "float32", ()), ("desc", "float32", (128,)), ("desc_u8", "uint8", (128,)),
+                   ("kpts", "float32", (4,)), ("orients", "float32", (2,)))
+
+
+class SelectWorkspace(_PairWorkspace):
+    """Device scratch of sift_select_batch_dev for up to n frames of `capacity` rows on a gx x gy grid (keys, cell
+    segments, flags and each frame's parked payload pointers)."""
+    _bytes_fn, _what, _shape_text = "nm_sift_select_workspace_bytes", "select workspace", "n %r / capacity %r / grid %r x %r"
+
+    def __init__(self, n, capacity, gx, gy, device=None):
+        self._alloc(device, n=n, capacity=capacity, gx=gx, gy=gy)
+
+
+def _select_shape(n, capacity, given, gx, gy, keep):
+    """The checks the C entries make on sizes, worded for Python; returns (capacity, keep)."""
+    for name, _, tail in _SELECT_PAYLOAD:
+        if any(tuple(t.shape[1:]) != tail for t in given.get(name) or ()):
+            raise NmError("select: %s must be (rows,%s)" % (name, " %d" % tail[0] if tail else ""))
+    capacity = _pair_cap(capacity, [t for ts in given.values() if ts is not None for t in ts])
+    if capacity > SELECT_MAX_CAPACITY or not (1 <= gx <= SELECT_MAX_GRID and 1 <= gy <= SELECT_MAX_GRID):
+        raise NmError("select: capacity %r above %d or grid %r x %r outside [1, %d]" % (capacity, SELECT_MAX_CAPACITY, gx, gy,
+                                                                                       SELECT_MAX_GRID))
+    if not 1 <= keep <= capacity:
+        raise NmError("select: keep %r outside [1, capacity %d]" % (keep, capacity))
+    return capacity
+
+
+def sift_select_batch_dev(d_counts, xs, ys, width, height, scores=None, descs=None, descs_u8=None, kpts=None, orients=None,
+                          gx=16, gy=9, keep=2048, capacity=None, out=None, want_index=True, workspace=None):
+    """The strongest `keep` keypoints of n = len(xs) <= SELECT_MAX_BATCH frames, spread over a gx x gy grid
+    (nm_sift_select_batch_dev): every cell's best row first, then every cell's second best, ..., written in ascending source
+    order; four launches on the current stream, no host read. d_counts: int32 DEVICE row counts (SiftArena.num_items), xs /
+    ys: float32 device coordinates in a width x height frame. scores: optional float32 device scores; without them descs
+    (raw (rows, 128) float32 descriptors) is required and a row's score is its squared norm. descs, descs_u8 (rows, 128),
+    kpts (rows, 4) and orients (rows, 2) are the optional payload: what is given is gathered. keep may not exceed the
+    capacity (default: the smallest first dimension). out: the dict a former call returned, to write into the same tensors
+    (what a graph capture needs, with a workspace); default: new tensors, zero-filled. Rows at and beyond a frame's output
+    count are not written. Returns a dict: "x", "y" and a key per given payload list (lists of n tensors of `capacity`
+    rows), "index" (the source row of every output row; None with want_index=False) and "count", an (n,) int32 DEVICE
+    tensor of min(keep, rows)."""
+    torch = _torch()
+    given = dict(x=xs, y=ys, desc=descs, desc_u8=descs_u8, kpts=kpts, orients=orients)
+    lists = [v for v in given.values() if v is not None]
+    n = _pair_count(xs, d_counts, ys, scores, descs, descs_u8, kpts, orients)
+    if scores is None and descs is None:
+        raise NmError("select: give scores or descs")
+    outs = [t for name in given if out is not None and out.get(name) is not None for t in out[name]]
+    everything = [t for ts in lists for t in ts] + list(scores or ()) + outs
+    capacity = _select_shape(n, capacity, dict(given, scores=scores, outs=outs or None), gx, gy, keep)
+    device = _pair_device(everything + list(d_counts) + [workspace.buf if workspace is not None else None], list(d_counts))
+    if out is None:
+        out = {name: None if given[name] is None else
+               [torch.zeros((capacity,) + tail, dtype=getattr(torch, dt), device=device) for _ in range(n)]
+               for name, dt, tail in _SELECT_PAYLOAD}
+        out["index"] = [torch.zeros(capacity, dtype=torch.int32, device=device) for _ in range(n)] if want_index else None
+        out["count"] = torch.zeros(n, dtype=torch.int32, device=device)
+    if any((out.get(name) is None) != (given[name] is None) for name in given) or out["count"].numel() != n or \
+            any(out[name] is not None and len(out[name]) != n for name in list(given) + ["index"]):
+        raise NmError("select: `out` does not fit this call's payload")
+    workspace = _pair_workspace(SelectWorkspace, workspace, device, n, capacity, gx, gy)
+    arr, i32 = _pair_dev_table, torch.int32
+    tab = lambda src: [arr(src[name], getattr(torch, dt)) for name, dt, _ in _SELECT_PAYLOAD]
+    ti, to = tab(given), tab(out)
+    counts = [out["count"][k:k + 1] for k in range(n)]
+    _check(lib().nm_sift_select_batch_dev(n, capacity, width, height, gx, gy, keep, arr(d_counts, i32), ti[0], ti[1],
+                                          arr(scores, torch.float32), *ti[2:], *to, arr(out["index"], i32), arr(counts, i32),
+                                          _dev(workspace.buf), _stream()), "nm_sift_select_batch_dev")
+    return out
+
+
+def sift_select_host(counts, xs, ys, width, height, scores=None, descs=None, descs_u8=None, kpts=None, orients=None,
+                     gx=16, gy=9, keep=2048, capacity=None, fill=0):
+    """sift_select_batch_dev on the host (nm_sift_select_host, the same score, cell and key functions): numpy in and out,
+    bit-identical results. counts are host ints. Returns the same dict with (n, capacity, ...) arrays, "index" always and
+    "count" an (n,) int32 array; rows at and beyond a count hold `fill`."""
+    import numpy as np
+    given = dict(x=xs, y=ys, desc=descs, desc_u8=descs_u8, kpts=kpts, orients=orients)
+    n = _pair_count(xs, counts, ys, scores, descs, descs_u8, kpts, orients)
+    if scores is None and descs is None:
+        raise NmError("select: give scores or descs")
+    for name, dt, _ in _SELECT_PAYLOAD:
+        if given[name] is not None:
+            given[name] = _pair_host_arrays(given[name], getattr(np, dt), flat=False)
+    scores = None if scores is None else _pair_host_arrays(scores, np.float32)
+    capacity = _select_shape(n, capacity, dict(given, scores=scores), gx, gy, keep)
+    out = {name: None if given[name] is None else np.full((n, capacity) + tail, fill, getattr(np, dt))
+           for name, dt, tail in _SELECT_PAYLOAD}
+    out["index"] = np.full((n, capacity), fill, np.int32)
+    out["count"] = np.full(n, fill, np.int32)
+    arr = _pair_host_table
+    ti = [arr(given[name]) for name, _, _ in _SELECT_PAYLOAD]
+    to = [None if out[name] is None else arr(list(out[name])) for name, _, _ in _SELECT_PAYLOAD]
+    cnt_in = _pair_host_sizes(counts)
+    cnt_out = [out["count"][k:k + 1] for k in range(n)]
+    _check(lib().nm_sift_select_host(n, capacity, width, height, gx, gy, keep, arr(cnt_in), ti[0], ti[1], arr(scores),
+                                     *ti[2:], *to, arr(list(out["index"])), arr(cnt_out)), "nm_sift_select_host")
+    return out
 
 
 def _u8_caps(As, Bs, results, capA, capB):
