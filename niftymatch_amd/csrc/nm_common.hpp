@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include "nm_wave_dev.hpp"
 
 #define NM_WAVE 64
 

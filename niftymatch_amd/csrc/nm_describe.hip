@@ -673,7 +673,7 @@ __global__ __launch_bounds__(256) void selftest_expw_kernel(unsigned long long *
         if (near) ++nears;
         else if (__float_as_uint(f) != __float_as_uint(e)) ++bad;
     }
-    for (int d = 32; d >= 1; d >>= 1) { bad += __shfl_xor(bad, d); nears += __shfl_xor(nears, d); n += __shfl_xor(n, d); }
+    bad = nmw::wave_sum(bad); nears = nmw::wave_sum(nears); n = nmw::wave_sum(n);
     if ((threadIdx.x & 63) == 0) { atomicAdd(&out[0], bad); atomicAdd(&out[1], nears); atomicAdd(&out[2], n); }
 }
 
@@ -709,9 +709,7 @@ __global__ __launch_bounds__(256) void selftest_orient_kernel(unsigned long long
         ++nd;
         if (__float_as_uint(nmfp::div_by(nmfp::div_by(den), num)) != __float_as_uint(num / den)) ++badd;
     }
-    for (int d = 32; d >= 1; d >>= 1) {
-        bad3 += __shfl_xor(bad3, d); rej += __shfl_xor(rej, d); badc += __shfl_xor(badc, d); badd += __shfl_xor(badd, d); nd += __shfl_xor(nd, d);
-    }
+    bad3 = nmw::wave_sum(bad3); rej = nmw::wave_sum(rej); badc = nmw::wave_sum(badc); badd = nmw::wave_sum(badd); nd = nmw::wave_sum(nd);
     if ((threadIdx.x & 63) == 0) {
         atomicAdd(&out[0], bad3); atomicAdd(&out[1], rej); atomicAdd(&out[2], badc); atomicAdd(&out[3], badd); atomicAdd(&out[4], nd);
     }

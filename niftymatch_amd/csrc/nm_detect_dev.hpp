@@ -278,7 +278,7 @@ __device__ __forceinline__ void detect_stage_body(const DetectView &a, int blk, 
             // scan by consecutive lanes. Refining in place made whole waves run the ~150-instruction refinement for the
             // one or two candidate lanes they hold, three times per row: most of the kernel's VALU work.
             const unsigned long long m = __ballot(cand);
-            if (cand) s_x[j][level][wave][__popcll(m & ((1ull << lane) - 1ull))] = (unsigned char)lane;
+            if (cand) s_x[j][level][wave][nmw::lane_rank(m)] = (unsigned char)lane;
             if (lane == 0) s_cnt[(j * 3 + level) * 4 + wave] = __popcll(m);
             if (DENSE && !cand && xin && y < oh)     // API path: every pixel of the dense maps is written exactly once
                 reinterpret_cast<float4 *>(a.dense[level])[(size_t)y * ow + x] = make_float4(-1.f, -1.f, -1.f, -1.f);
@@ -294,7 +294,7 @@ __device__ __forceinline__ void detect_stage_body(const DetectView &a, int blk, 
         for (int e = 0; e < EPL; ++e) { const int q = lane * EPL + e; c[e] = q < NSUB ? s_cnt[q] : 0; sum += c[e]; }
         int incl = sum;
 #pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
+        for (int d = 1; d < 64; d <<= 1) {                 // hand-written: nmw::wave_inclusive_scan changes the detection kernels' code
             const int o = __shfl_up(incl, d);
             if (lane >= d) incl += o;
         }
@@ -341,8 +341,9 @@ __device__ __forceinline__ void detect_stage_body(const DetectView &a, int blk, 
             continue;
         }
         // ordered compaction of the accepted candidates inside their (row, level) group
+        // hand-written: nmw::block_rank changes the detection kernels' code (and `wave` counts inside a quarter of the tail's workgroup)
         const unsigned long long m = __ballot(acc);
-        const int in_wave = __popcll(m & ((1ull << lane) - 1ull));
+        const int in_wave = nmw::lane_rank(m);
         if (lane == 0) s_wtot[wave] = __popcll(m);
         __syncthreads();
         int before = in_wave;

@@ -68,26 +68,6 @@ __global__ __launch_bounds__(256) void find_keypoints_dense_kernel(const float *
         result[(size_t)y * w + x] = kp;
 }
 
-// Ordered in-block compaction helper: returns this thread's rank among the block's flagged threads (block-wide,
-// in thread order) and the block total. 256 threads = 4 waves.
-__device__ __forceinline__ int block_rank(bool flag, int &total, int *s_wave /* [4] */)
-{
-    const unsigned long long m = __ballot(flag);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int rank = __popcll(m & ((1ull << lane) - 1ull));
-    if (lane == 0) s_wave[wave] = __popcll(m);
-    __syncthreads();
-    int off = 0;
-    total = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int c = s_wave[i];
-        if (i < wave) off += c;
-        total += c;
-    }
-    return off + rank;
-}
-
 __global__ __launch_bounds__(256) void count_valid_kernel(const float4 *__restrict__ dense, int n,
                                                          int *__restrict__ counts)
 {
@@ -95,7 +75,7 @@ __global__ __launch_bounds__(256) void count_valid_kernel(const float4 *__restri
     const int i = blockIdx.x * 256 + threadIdx.x;
     const bool f = (i < n) && (dense[i].w >= 0);
     int total;
-    block_rank(f, total, s_wave);
+    nmw::block_rank<4>(f, s_wave, total);
     if (threadIdx.x == 0) counts[blockIdx.x] = total;
 }
 
@@ -109,7 +89,7 @@ __global__ __launch_bounds__(256) void scatter_valid_kernel(const float4 *__rest
     if (i < n) v = dense[i];
     const bool f = (i < n) && (v.w >= 0);
     int total;
-    const int r = block_rank(f, total, s_wave);
+    const int r = nmw::block_rank<4>(f, s_wave, total);
     if (f) out[offsets[blockIdx.x] + r] = v;
 }
 
@@ -122,7 +102,7 @@ __global__ __launch_bounds__(256) void count_valid3_kernel(NmCompact3 c)
     const int i = blockIdx.x * 256 + threadIdx.x;
     const bool f = (i < c.n) && (c.dense[l][i].w >= 0);
     int total;
-    block_rank(f, total, s_wave);
+    nmw::block_rank<4>(f, s_wave, total);
     if (threadIdx.x == 0) c.counts[l * c.nb + blockIdx.x] = total;
 }
 
@@ -139,7 +119,7 @@ __global__ __launch_bounds__(256) void scatter_valid3_kernel(NmCompact3 c)
     if (i < c.n) v = c.dense[l][i];
     const bool f = (i < c.n) && (v.w >= 0);
     int total;
-    const int r = block_rank(f, total, s_wave);
+    const int r = nmw::block_rank<4>(f, s_wave, total);
     if (f) c.out[l][c.offsets[l * c.nb + blockIdx.x] + r] = v;
 }
 
@@ -175,7 +155,7 @@ __device__ __forceinline__ void block_exclusive_scan_1024(const int *__restrict_
     for (int l = 0; l < NL; ++l) {
         incl[l] = sum[l];
 #pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
+        for (int d = 1; d < 64; d <<= 1) {                 // hand-written: nmw::wave_inclusive_scan changes scan_book_kernel's code
             const int up = __shfl_up(incl[l], d);
             if (lane >= d) incl[l] += up;
         }

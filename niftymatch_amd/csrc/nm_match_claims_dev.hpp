@@ -61,7 +61,7 @@ template <class Metric>
 __device__ __forceinline__ void match_claims(const ClaimTables<typename Metric::Elem> &a, int capA, int capB,
                                              void *__restrict__ ws)
 {
-    __shared__ int s_cnt[2][TB / 64];
+    __shared__ int s_below[TB / 64], s_cnt[TB / 64];
     const int k = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int row0 = blockIdx.x * TB, i = row0 + tid;
     const int nA = clip(*a.d_nA[k], capA), nB = clip(*a.d_nB[k], capB);
@@ -81,23 +81,19 @@ __device__ __forceinline__ void match_claims(const ClaimTables<typename Metric::
     const int upto = blockIdx.x == 0 ? nA : row0;
     int below = 0;
     for (int r = tid; r < upto; r += TB) below += is_claim(mt[r], nB) ? 1 : 0;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) below += __shfl_xor(below, d);
+    below = nmw::wave_sum(below);
     int j = -1;
     bool claim = false;
     if (i < nA) {
         j = mt[i];
         claim = is_claim(j, nB);
     }
-    const unsigned long long bal = __ballot(claim);
-    if (lane == 0) { s_cnt[0][wave] = below; s_cnt[1][wave] = __popcll(bal); }
-    __syncthreads();
-    int all_below = 0, before = 0;
+    if (lane == 0) s_below[wave] = below;                            // read behind block_rank's barrier
+    int claims;
+    const int rank = nmw::block_rank<TB / 64>(claim, s_cnt, claims);
+    int all_below = 0;
 #pragma unroll
-    for (int w = 0; w < TB / 64; ++w) {
-        all_below += s_cnt[0][w];
-        before += w < wave ? s_cnt[1][w] : 0;
-    }
+    for (int w = 0; w < TB / 64; ++w) all_below += s_below[w];
     if (blockIdx.x == 0) {
         if (tid == 0) static_cast<int *>(ws)[k] = all_below;         // m_k
         all_below = 0;                                               // workgroup 0 has nothing below it
@@ -107,7 +103,7 @@ __device__ __forceinline__ void match_claims(const ClaimTables<typename Metric::
         tau = Metric::tau_of(a.A[k] + (size_t)i * Metric::DIM, a.B[k] + (size_t)j * Metric::DIM);
         const size_t cr = Metric::claim_rows(capA);
         int *__restrict__ ci = Metric::claims_of(ws, k, capA);
-        const int pos = all_below + before + __popcll(bal & ((1ull << lane) - 1ull));   // < nA <= capA
+        const int pos = all_below + rank;                            // < nA <= capA
         ci[pos] = i;
         ci[cr + pos] = j;
         Metric::store_claim(ci + 2 * cr, cr, pos, tau);

@@ -207,11 +207,7 @@ __global__ __launch_bounds__(256) void fine_rows_kernel(MatchBatch bt)
     const int nA = pair_nA(c), nB = pair_nB(c), lane = threadIdx.x & 63, k4 = lane & 31;
     const int count = (nA > 0 && nB > 0) ? min(max(*pair_f1_count(c), 0), nA) : 0;
     if (blockIdx.x == 0 && threadIdx.x < 64) {
-        const MatchPlan p = make_plan_on(count, nB, bt.n_cu2, bt.n_xcd, lane, 64, [](int v) {
-#pragma unroll
-            for (int d = 32; d >= 1; d >>= 1) v = max(v, __shfl_xor(v, d));
-            return v;
-        });
+        const MatchPlan p = make_plan_on(count, nB, bt.n_cu2, bt.n_xcd, lane, 64, [](int v) { return nmw::wave_max(v); });
         MatchPlan q = p;
         if (count == 0) q.G = 0;                          // nothing listed: every workgroup of the second pass leaves at once
         if (lane == 0) *pair_plan2(c) = q;

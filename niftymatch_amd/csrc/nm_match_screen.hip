@@ -50,7 +50,7 @@ __global__ __launch_bounds__(256) void prep_kernel(MatchBatch bt)
         const float4 x = v[q];
         double acc = ((double)x.x * (double)x.x + (double)x.y * (double)x.y) + ((double)x.z * (double)x.z + (double)x.w * (double)x.w);
 #pragma unroll
-        for (int d = 16; d >= 1; d >>= 1) acc += __shfl_xor(acc, d);
+        for (int d = 16; d >= 1; d >>= 1) acc += __shfl_xor(acc, d);   // hand-written: nmw::wave_sum<16> changes prep_kernel<0>'s code
         const float nrm = (float)acc;
         const float sc = isA[q] ? -2.0f : 1.0f;
         if (MODE == 1 || (MODE == 2 && !isA[q])) {
@@ -73,8 +73,7 @@ __global__ __launch_bounds__(256) void prep_kernel(MatchBatch bt)
             const float e0 = x.x - inv * f16_value(b0), e1 = x.y - inv * f16_value(b1);
             const float e2 = x.z - inv * f16_value(b2), e3 = x.w - inv * f16_value(b3);
             res = (e0 * e0 + e1 * e1) + (e2 * e2 + e3 * e3);
-#pragma unroll
-            for (int d = 16; d >= 1; d >>= 1) res += __shfl_xor(res, d);
+            res = nmw::wave_sum<16>(res);
             // upper bound of the residual's 2-norm: the 131 binary32 roundings above cost < 1e-5 relative, squares that
             // underflow < 1e-18 absolute
             res = __builtin_sqrtf(res) * 1.00002f + 1e-18f;
@@ -103,11 +102,7 @@ __global__ __launch_bounds__(1024) void nbmax_kernel(MatchBatch bt)
         // device-sized call: the last wave makes the work plan for the real sizes (make_plan_on: the same function the host
         // runs for the host-sized entries), its lanes sharing the slot count, while the others reduce the norms
         const int lane = threadIdx.x & 63;
-        const MatchPlan p = make_plan_on(pair_nA(c), nB, bt.n_cu, bt.n_xcd, lane, 64, [](int v) {
-#pragma unroll
-            for (int d = 32; d >= 1; d >>= 1) v = max(v, __shfl_xor(v, d));
-            return v;
-        });
+        const MatchPlan p = make_plan_on(pair_nA(c), nB, bt.n_cu, bt.n_xcd, lane, 64, [](int v) { return nmw::wave_max(v); });
         if (lane == 0) *c.d_plan = p;
     }
     // +inf as soon as one candidate norm is not a finite number below NORM_LIMIT (fmax would drop a NaN): the finalize
@@ -129,7 +124,7 @@ __global__ __launch_bounds__(1024) void nbmax_kernel(MatchBatch bt)
             mr = (e[k] < NORM_LIMIT) ? __builtin_fmaxf(mr, e[k]) : __builtin_inff();
         }
     }
-#pragma unroll
+#pragma unroll                                              // hand-written: two nmw::wave_max change nbmax_kernel's code
     for (int d = 32; d >= 1; d >>= 1) { m = __builtin_fmaxf(m, __shfl_xor(m, d)); mr = __builtin_fmaxf(mr, __shfl_xor(mr, d)); }
     if ((threadIdx.x & 63) == 0) { s[threadIdx.x >> 6] = m; s[16 + (threadIdx.x >> 6)] = mr; }
     __syncthreads();

@@ -157,13 +157,7 @@ __global__ __launch_bounds__(64) void mosaic_plan_kernel(int n, const float *__r
     // host twin's in-order loop
     float e[4] = {placed ? box[0] : INFINITY, placed ? box[1] : INFINITY, placed ? box[2] : -INFINITY,
                   placed ? box[3] : -INFINITY};
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        e[0] = fminf(e[0], __shfl_xor(e[0], d));
-        e[1] = fminf(e[1], __shfl_xor(e[1], d));
-        e[2] = fmaxf(e[2], __shfl_xor(e[2], d));
-        e[3] = fmaxf(e[3], __shfl_xor(e[3], d));
-    }
+    e[0] = nmw::wave_min(e[0]); e[1] = nmw::wave_min(e[1]); e[2] = nmw::wave_max(e[2]); e[3] = nmw::wave_max(e[3]);
     const bool any = __ballot(placed) != 0ull;
     if (k < 4) extent[k] = any ? e[k] : 0.f;
 }
@@ -204,13 +198,7 @@ __global__ __launch_bounds__(MB_THREADS) void transform_blend_batch_kernel(const
         s_rect[tid] = r;
         const bool empty = r.z == 0;                   // x1 > x0 >= 0 for every non-empty rectangle
         int ux0 = empty ? INT_MAX : r.x, uy0 = empty ? INT_MAX : r.y, ux1 = empty ? 0 : r.z, uy1 = empty ? 0 : r.w;
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) {
-            ux0 = min(ux0, __shfl_xor(ux0, d));
-            uy0 = min(uy0, __shfl_xor(uy0, d));
-            ux1 = max(ux1, __shfl_xor(ux1, d));
-            uy1 = max(uy1, __shfl_xor(uy1, d));
-        }
+        ux0 = nmw::wave_min(ux0); uy0 = nmw::wave_min(uy0); ux1 = nmw::wave_max(ux1); uy1 = nmw::wave_max(uy1);
         if (tid == 0) s_union = make_int4(ux0, uy0, ux1, uy1);
     }
     __syncthreads();

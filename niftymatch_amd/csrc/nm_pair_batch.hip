@@ -18,8 +18,7 @@ __global__ __launch_bounds__(TB) void pair_count_kernel(const CtArgs a, int capA
     const int *__restrict__ res = a.result[k];
     int c = 0;
     for (int i = tid; i < capA; i += TB) c += res[i] >= 0 ? 1 : 0;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) c += __shfl_xor(c, d);
+    c = nmw::wave_sum(c);
     if ((tid & 63) == 0) part[tid >> 6] = c;
     __syncthreads();
     if (tid == 0) {

@@ -16,28 +16,16 @@ __global__ __launch_bounds__(64) void ransac_model_kernel(const float *__restric
                                                          const int *__restrict__ rand_list, int iterations,
                                                          float *__restrict__ homographies, int *__restrict__ inliers)
 {
-    constexpr int NS = (MODEL == 0) ? 1 : (MODEL == 1) ? 2 : 4;
+    constexpr int NS = nmr_samples(MODEL);
     const int it = blockIdx.x * 64 + threadIdx.x;
     if (it >= iterations) return;
     float H[9];
 #pragma unroll
     for (int k = 0; k < 9; ++k) H[k] = 0.f;
     int ri[NS];
-    bool dup = false;
 #pragma unroll
     for (int a = 0; a < NS; ++a) ri[a] = rand_list[(size_t)it * NS + a];
-#pragma unroll
-    for (int a = 0; a < NS; ++a)
-#pragma unroll
-        for (int b = a + 1; b < NS; ++b) dup = dup || (ri[a] == ri[b]);
-    if (!dup) {
-        float px[NS], py[NS], qx[NS], qy[NS];
-#pragma unroll
-        for (int a = 0; a < NS; ++a) { px[a] = sx[ri[a]]; py[a] = sy[ri[a]]; qx[a] = dx[ri[a]]; qy[a] = dy[ri[a]]; }
-        if (MODEL == 0) nmr_fit_translation(px, py, qx, qy, H);
-        else if (MODEL == 1) nmr_fit_similarity(px, py, qx, qy, H);
-        else nmr_fit_homography(px, py, qx, qy, H);
-    }
+    const bool dup = nmr_fit_sampled<MODEL>(ri, [&](int i) { return make_float4(sx[i], sy[i], dx[i], dy[i]); }, H);
 #pragma unroll
     for (int k = 0; k < 9; ++k) homographies[(size_t)it * 9 + k] = H[k];
     inliers[it] = dup ? -1 : 0;                    // -1 marks a skipped hypothesis for the counting pass
@@ -63,8 +51,7 @@ __global__ __launch_bounds__(256) void ransac_inlier_kernel(const float *__restr
             const bool in = (x >= 0.f) && nmr_is_inlier(H, x, sy[i], dx[i], dy[i], thr);
             cnt += in ? 1 : 0;
         }
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) cnt += __shfl_xor(cnt, d);
+        cnt = nmw::wave_sum(cnt);
         if (lane == 0) inliers[it] = cnt;
     }
 }

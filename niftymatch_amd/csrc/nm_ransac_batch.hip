@@ -42,7 +42,6 @@ __host__ __device__ __forceinline__ unsigned int rb_sample(unsigned int seed, un
     return (unsigned int)(((z >> 32) * (unsigned long long)m) >> 32);
 }
 
-constexpr int rb_samples(int model) { return model == 0 ? 1 : model == 1 ? 2 : 4; }
 constexpr int rb_min_points(int model) { return model == 2 ? 4 : 2; }     // ransac_impl's minima
 
 struct RbLayout {
@@ -68,7 +67,7 @@ __global__ __launch_bounds__(RB_PREP_THREADS) void ransac_batch_prep_kernel(cons
                                                                             float4 *__restrict__ pts)
 {
     __shared__ int s_cnt[RB_PREP_THREADS / 64];
-    const int k = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int k = blockIdx.x, tid = threadIdx.x;
     const int nA = nmp::clip(*a.d_nA[k], capA);
     const float *__restrict__ sx = a.sx[k];
     const float *__restrict__ sy = a.sy[k];
@@ -89,17 +88,9 @@ __global__ __launch_bounds__(RB_PREP_THREADS) void ransac_batch_prep_kernel(cons
                 p = make_float4(x, sy[i], dx[j], dy[j]);
             }
         }
-        const unsigned long long bal = __ballot(valid);
-        if (lane == 0) s_cnt[wave] = __popcll(bal);
-        __syncthreads();
-        int before = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < RB_PREP_THREADS / 64; ++w) {
-            const int c = s_cnt[w];
-            before += (w < wave) ? c : 0;
-            total += c;
-        }
-        if (valid) out[base + before + __popcll(bal & ((1ull << lane) - 1ull))] = p;
+        int total;
+        const int rank = nmw::block_rank<RB_PREP_THREADS / 64>(valid, s_cnt, total);
+        if (valid) out[base + rank] = p;
         base += total;
         __syncthreads();                                   // s_cnt is rewritten by the next chunk
     }
@@ -122,7 +113,7 @@ __global__ __launch_bounds__(RB_FIT_THREADS) void ransac_batch_fit_count_kernel(
                                                                                 float *__restrict__ homographies,
                                                                                 int *__restrict__ inliers)
 {
-    constexpr int NS = rb_samples(MODEL);
+    constexpr int NS = nmr_samples(MODEL);
     __shared__ float4 s_pts[RB_TILE];
     __shared__ unsigned long long s_key[RB_FIT_THREADS / 64];
     const int k = blockIdx.y, tid = threadIdx.x;
@@ -148,21 +139,7 @@ __global__ __launch_bounds__(RB_FIT_THREADS) void ransac_batch_fit_count_kernel(
         int ri[NS];
 #pragma unroll
         for (int s = 0; s < NS; ++s) ri[s] = (int)rb_sample(seeds.seed[k], (unsigned int)(t * NS + s), (unsigned int)m);
-#pragma unroll
-        for (int s = 0; s < NS; ++s)
-#pragma unroll
-            for (int u = s + 1; u < NS; ++u) dup = dup || (ri[s] == ri[u]);
-        if (!dup) {
-            float px[NS], py[NS], qx[NS], qy[NS];
-#pragma unroll
-            for (int s = 0; s < NS; ++s) {
-                const float4 v = P[ri[s]];
-                px[s] = v.x; py[s] = v.y; qx[s] = v.z; qy[s] = v.w;
-            }
-            if (MODEL == 0) nmr_fit_translation(px, py, qx, qy, H);
-            else if (MODEL == 1) nmr_fit_similarity(px, py, qx, qy, H);
-            else nmr_fit_homography(px, py, qx, qy, H);
-        }
+        dup = nmr_fit_sampled<MODEL>(ri, [&](int i) { return P[i]; }, H);
 #pragma unroll
         for (int q = 0; q < 9; ++q) hyp[row * 9 + q] = H[q];
         if (homographies)
@@ -186,11 +163,7 @@ __global__ __launch_bounds__(RB_FIT_THREADS) void ransac_batch_fit_count_kernel(
     }
     if (active && inliers) inliers[row] = cnt;
     unsigned long long key = active ? (((unsigned long long)cnt << 32) | (0xFFFFFFFFu - (unsigned int)t)) : 0ull;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const unsigned long long o = __shfl_xor(key, d);
-        key = o > key ? o : key;
-    }
+    key = nmw::wave_max(key);
     if ((tid & 63) == 0) s_key[tid >> 6] = key;
     __syncthreads();
     if (tid == 0) {

@@ -135,6 +135,34 @@ __device__ __forceinline__ void nmr_fit_homography(const float sx[4], const floa
     nmr_denormalise(Hn, s1, s2, smx, smy, dmx, dmy, H);
 }
 
+/* Points a hypothesis of the model is fitted to: the one count of the samplers, the fit and the refit's minimum of inliers. */
+__host__ __device__ constexpr int nmr_samples(int model) { return model == 0 ? 1 : model == 1 ? 2 : 4; }
+
+/* A hypothesis from its sample indices ri; fetch(i) returns point i as (sx, sy, dx, dy). An index drawn twice: no fit, H is
+ * left as it is and the result is true (such a hypothesis counts no inliers, ransac.cu:430-521). */
+template <int MODEL, class Fetch>
+__device__ __forceinline__ bool nmr_fit_sampled(const int (&ri)[nmr_samples(MODEL)], Fetch fetch, float H[9])
+{
+    constexpr int NS = nmr_samples(MODEL);
+    bool dup = false;
+#pragma unroll
+    for (int s = 0; s < NS; ++s)
+#pragma unroll
+        for (int u = s + 1; u < NS; ++u) dup = dup || (ri[s] == ri[u]);
+    if (!dup) {
+        float px[NS], py[NS], qx[NS], qy[NS];
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            const float4 v = fetch(ri[s]);
+            px[s] = v.x; py[s] = v.y; qx[s] = v.z; qy[s] = v.w;
+        }
+        if (MODEL == 0) nmr_fit_translation(px, py, qx, qy, H);
+        else if (MODEL == 1) nmr_fit_similarity(px, py, qx, qy, H);
+        else nmr_fit_homography(px, py, qx, qy, H);
+    }
+    return dup;
+}
+
 /* eval_transformation's per-point test -- ransac.cu:68-78 */
 __device__ __forceinline__ bool nmr_is_inlier(const float H[9], float sx, float sy, float dx, float dy, float thr)
 {

@@ -46,7 +46,7 @@ __device__ __forceinline__ void reduce(double *acc, RfShared &sh, double *out)
 {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 #pragma unroll
-    for (int q = 0; q < N; ++q)
+    for (int q = 0; q < N; ++q)                          // hand-written: with nmw::wave_sum the refit with mask and rms timed outside the parent's spread
 #pragma unroll
         for (int d = 32; d >= 1; d >>= 1) acc[q] = acc[q] + __shfl_xor(acc[q], d);
     if (lane == 0)
@@ -171,7 +171,7 @@ __global__ __launch_bounds__(LANES) void ransac_refit_kernel(const nmp::PointTab
     pass<PASS_SUMS>(P, H, thr, nullptr, sh, sums);
     int done = 0;
     for (int r = 0; r < rounds; ++r) {                               // every branch below is uniform over the workgroup
-        if (sums[0] < (double)min_inliers(MODEL)) break;
+        if (sums[0] < (double)nmr_samples(MODEL)) break;
         float Hn[9];
         if (MODEL == 0) {
             fit_translation(sums, Hn);
@@ -295,7 +295,7 @@ void host_refit_pair(int model, const Pair &P, int capA, float thr, int rounds, 
     host_pass<PASS_SUMS>(P, H, thr, nullptr, sums);
     int done = 0;
     for (int r = 0; r < rounds; ++r) {
-        if (sums[0] < (double)min_inliers(model)) break;
+        if (sums[0] < (double)nmr_samples(model)) break;
         float Hn[9];
         if (model == 0) {
             fit_translation(sums, Hn);

@@ -27,7 +27,6 @@ __host__ __device__ constexpr int pass_width(int kind)
 {
     return kind == PASS_SUMS ? 5 : kind == PASS_DIST ? 2 : kind == PASS_SIM ? 3 : kind == PASS_DLT ? 24 : 1;
 }
-__host__ __device__ constexpr int min_inliers(int model) { return model == 0 ? 1 : model == 1 ? 2 : 4; }
 
 struct Pair {
     const float *sx, *sy, *dx, *dy;

@@ -44,6 +44,9 @@ struct FramePtrs {                          // a frame's payload, parked by laun
     int *out_index, *d_out;
 };
 
+constexpr int PTRS_BYTES = 128;             // the record of the parked pointers
+static_assert(sizeof(FramePtrs) <= PTRS_BYTES, "the parked pointers outgrow their record");
+
 // A frame's part of the workspace (8-byte aligned, widest members first)
 struct Frame {
     uint64_t *key, *skey, *list;            // source order; grouped by cell; the rows of round R*
@@ -51,25 +54,35 @@ struct Frame {
     FramePtrs *ptrs;
     unsigned short *cell;
     unsigned char *flag;                    // 0 out, 1 in, 2 round R*: in when the key reaches the threshold
-    static __host__ __device__ size_t bytes(int cap)
+    // The one layout: every member in order, each starting where the one before it ends (the element sizes only shrink, so
+    // each is aligned). Sets the members when there is a base; returns the frame's stride, a multiple of 16 bytes.
+    __host__ __device__ size_t layout(char *base, int cap)
     {
-        const size_t raw = (size_t)cap * 16 + (size_t)nmsel::MAX_CELLS * 8 + (size_t)(nmsel::MAX_CELLS + 8) * 4 + M_INTS * 4 +
-                           128 + (size_t)cap * 3;
-        return (raw + 15) / 16 * 16;
+        size_t off = 0;
+        auto take = [&](auto *&p, size_t bytes) {
+            if (base) p = reinterpret_cast<decltype(+p)>(base + off);
+            off += bytes;
+        };
+        take(key, (size_t)cap * 8);
+        take(skey, (size_t)cap * 8);
+        take(list, (size_t)nmsel::MAX_CELLS * 8);
+        take(cstart, (size_t)(nmsel::MAX_CELLS + 8) * 4);
+        take(meta, (size_t)M_INTS * 4);
+        take(ptrs, PTRS_BYTES);
+        take(cell, (size_t)cap * 2);
+        take(flag, (size_t)cap);
+        return (off + 15) / 16 * 16;
     }
     __host__ __device__ Frame(char *base, int cap)
     {
-        key = reinterpret_cast<uint64_t *>(base);
-        skey = key + cap;
-        list = skey + cap;
-        cstart = reinterpret_cast<int *>(list + nmsel::MAX_CELLS);
-        meta = cstart + nmsel::MAX_CELLS + 8;
-        ptrs = reinterpret_cast<FramePtrs *>(meta + M_INTS);
-        cell = reinterpret_cast<unsigned short *>(reinterpret_cast<char *>(ptrs) + 128);
-        flag = reinterpret_cast<unsigned char *>(cell + cap);
+        __builtin_assume(base != nullptr);  // the entry refuses a null workspace: no test of base is left in a kernel
+        layout(base, cap);
     }
+    static __host__ __device__ size_t bytes(int cap) { Frame f; return f.layout(nullptr, cap); }
+
+private:
+    Frame() = default;
 };
-static_assert(sizeof(FramePtrs) <= 128, "the parked pointers outgrow their record");
 
 struct Geometry { int capacity, width, height, gx, gy, keep; };
 
@@ -118,17 +131,10 @@ __global__ __launch_bounds__(SCORE_TB) void select_score_kernel(const ScoreArgs 
     f.cell[row] = (unsigned short)nmsel::cell_of(a.x[k][row], a.y[k][row], g.width, g.height, g.gx, g.gy);
 }
 
-__device__ __forceinline__ int wave_sum(int v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
-
 // Sum of v over the 1024 threads of the group kernel, the same value in every thread. Two barriers: red is free on return.
 __device__ __forceinline__ int group_sum(int v, int *red)
 {
-    v = wave_sum(v);
+    v = nmw::wave_sum(v);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
     __syncthreads();
     int s = 0;
@@ -158,12 +164,7 @@ __global__ __launch_bounds__(GROUP_TB) void select_group_kernel(const GroupArgs 
     int own[PER], local = 0;
 #pragma unroll
     for (int j = 0; j < PER; ++j) { own[j] = size[PER * tid + j]; local += own[j]; }
-    int incl = local;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int up = __shfl_up(incl, d);
-        if (lane >= d) incl += up;
-    }
+    const int incl = nmw::wave_inclusive_scan(local);
     if (lane == 63) red[wave] = incl;
     __syncthreads();
     int start = incl - local;
@@ -284,19 +285,11 @@ __global__ __launch_bounds__(GATHER_TB) void select_gather_kernel(int capacity, 
             const int flag = f.flag[i];
             in = flag == 1 || (flag == 2 && f.key[i] >= thr);
         }
-        const unsigned long long mask = __ballot(in);
-        if (lane == 0) wave_count[wave] = __popcll(mask);
-        __syncthreads();
-        int pos = base + __popcll(mask & (((unsigned long long)1 << lane) - 1));
-        int total = 0;
-#pragma unroll
-        for (int w = 0; w < GATHER_TB / 64; ++w) {
-            if (w < wave) pos += wave_count[w];
-            total += wave_count[w];
-        }
+        int total;
+        const int pos = base + nmw::block_rank<GATHER_TB / 64>(in, wave_count, total);
         if (in && pos >= t0 && pos < t1) sel[pos - t0] = i;
         base += total;
-        __syncthreads();
+        __syncthreads();                                             // wave_count is rewritten by the next chunk
     }
 
     for (int t = t0 + wave; t < t1; t += GATHER_TB / 64) {           // one wave per output row

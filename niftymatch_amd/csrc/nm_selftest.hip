@@ -186,11 +186,7 @@ __global__ __launch_bounds__(64) void selftest_instr_kernel(float *__restrict__ 
         }
         __syncthreads();
     }
-#pragma unroll
-    for (int dd = 32; dd >= 1; dd >>= 1) {
-        worst_rel = fmaxf(worst_rel, __shfl_xor(worst_rel, dd));
-        worst_model = fmaxf(worst_model, __shfl_xor(worst_model, dd));
-    }
+    worst_rel = nmw::wave_max(worst_rel); worst_model = nmw::wave_max(worst_model);
     if (lane == 0) {
         atomic_max_pos(&out[5], worst_rel);
         atomic_max_pos(&out[6], worst_model);
@@ -319,11 +315,7 @@ __global__ __launch_bounds__(64) void selftest_chain_kernel(float *__restrict__ 
         }
         __syncthreads();
     }
-#pragma unroll
-    for (int dd = 32; dd >= 1; dd >>= 1) {
-        worst = fmaxf(worst, __shfl_xor(worst, dd));
-        worst_sub = fmaxf(worst_sub, __shfl_xor(worst_sub, dd));
-    }
+    worst = nmw::wave_max(worst); worst_sub = nmw::wave_max(worst_sub);
     if (lane == 0) {
         atomic_max_pos(&out[8], worst);
         atomic_max_pos(&out[9], worst_sub);
@@ -377,10 +369,8 @@ __global__ __launch_bounds__(64) void selftest_f32_kernel(float *__restrict__ ou
         }
         __syncthreads();
     }
-    for (int dlt = 32; dlt >= 1; dlt >>= 1) {
-        worst = fmaxf(worst, __shfl_xor(worst, dlt));
-        n_chain += __shfl_xor(n_chain, dlt); n_rn += __shfl_xor(n_rn, dlt); n_all += __shfl_xor(n_all, dlt);
-    }
+    worst = nmw::wave_max(worst);
+    n_chain = nmw::wave_sum(n_chain); n_rn = nmw::wave_sum(n_rn); n_all = nmw::wave_sum(n_all);
     if (lane == 0) {
         atomic_max_pos(out + 0, worst);
         atomicAdd(out + 1, (float)n_chain); atomicAdd(out + 2, (float)n_rn); atomicAdd(out + 5, (float)n_all);
@@ -446,7 +436,7 @@ __global__ __launch_bounds__(64) void selftest_f32_chain_kernel(float *__restric
         }
         __syncthreads();
     }
-    for (int dlt = 32; dlt >= 1; dlt >>= 1) { worst2 = fmaxf(worst2, __shfl_xor(worst2, dlt)); worst1 = fmaxf(worst1, __shfl_xor(worst1, dlt)); }
+    worst2 = nmw::wave_max(worst2); worst1 = nmw::wave_max(worst1);
     if (lane == 0) { atomic_max_pos(out + 3, worst2); atomic_max_pos(out + 4, worst1); }
 }
 

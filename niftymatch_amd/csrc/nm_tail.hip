@@ -352,7 +352,7 @@ __device__ void scan_gather_all(const NmTailArgs &a, const NmTailFrame &fr, int 
             const int c = i < nb ? v[i] : 0;
             int incl = c;
 #pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
+            for (int d = 1; d < 64; d <<= 1) {             // hand-written: nmw::wave_inclusive_scan changes tail_scan_kernel's code
                 const int up = __shfl_up(incl, d);
                 if (lane >= d) incl += up;
             }

@@ -88,6 +88,14 @@ def test_ragged_batches(nm, cuda, n):
         assert (got["result"][i][min(max(c["nA"], 0), capA):] == -1).all(), "a row beyond nA is not -1"
 
 
+def test_claims_rank_in_a_second_workgroup_that_ends_inside_a_wave(nm, cuda):
+    """256 + 65 rows of A: the second workgroup of the claims stage ranks one full wave and one row of the next, behind the
+    claims of the first workgroup; every row claiming, and the default mix. Both filters share the stage."""
+    for c in (M.random_case(57, 256 + 65, 300, pad=0, claims=256 + 65), M.random_case(58, 256 + 65, 300, pad=0)):
+        got = _assert_all_equal(nm, cuda, [c], len(c["A"]), len(c["B"]))
+        assert 0 < got["count"][0] < M.claims_of(c)
+
+
 def test_slot_independence(nm, cuda):
     """The same pair alone, twice, and at slot 11 of a batch of 16 other pairs: identical outputs."""
     a = M.random_case(55, 150, 140, pad=0)

@@ -146,6 +146,19 @@ def test_batch_equals_oracle_on_synthetic_scenes(nm, oracle, cuda, model):
     assert (out[1][5:] > 0).all()
 
 
+def test_prep_compacts_through_a_second_chunk_that_ends_inside_a_wave(nm, oracle, cuda):
+    """capA = nA = 1024 + 65 with every third row unmatched: the prep kernel's ordered compaction takes a second chunk of 1024
+    rows whose second wave holds one row. Hypotheses and counts equal the oracle's on the valid rows in ascending order."""
+    model, capA, iterations, thr = 1, 1024 + 65, 300, 3.0
+    sx, sy, dx, dy, mt = _pair(np.random.default_rng(321), capA, capA, capA, model)
+    mt[:capA:3] = -1
+    sc = dict(nA=capA, sx=sx, sy=sy, dx=dx, dy=dy, matches=mt)
+    V = _valid_rows(sx, mt, capA, capA)
+    assert 700 < len(V) < 730 and V[-1] == capA - 1, "the last row, alone in its wave, is valid"
+    out = _run(nm, cuda, [sc], model, iterations, thr, [11], capA)
+    assert _check_pair(nm, oracle, cuda, sc, 0, out, model, iterations, thr, 11, capA) is not None
+
+
 def test_pair_result_independent_of_slot(nm, oracle, cuda):
     import torch
     model, capA, iterations, thr = 2, 2500, 700, 3.0

@@ -108,6 +108,28 @@ def test_sparse_grid_equal_scores_and_extreme_keeps(nm, cuda):
     run_both(nm, cuda, [odd], [300], cap, 320, 240, 16, 9, 100)
 
 
+@pytest.mark.parametrize("n", [1, 3])
+def test_gather_ranks_through_a_second_chunk_that_ends_inside_a_wave(nm, cuda, n):
+    """256 + 65 rows, half of them kept: the gather's ordered rank over the flags takes a second chunk of 256 rows whose second
+    wave holds one row, with the chunk base carried over from the first."""
+    cap = 256 + 65
+    frames = [make_frame(60 + k, cap, 301, 200) for k in range(n)]
+    host = run_both(nm, cuda, frames, [cap] * n, cap, 301, 200, 7, 5, cap // 2)
+    assert all(host["index"][k][:cap // 2].max() >= 256 + 64 - 40 for k in range(n)), "the selection ends in the first chunk"
+
+
+def test_group_scan_over_more_than_1024_occupied_cells(nm, cuda):
+    """One row in each of 1100 cells of a 64 x 64 grid (four cells per thread: 275 threads, five waves): every segment start
+    of the group kernel's scan depends on the totals of the waves before it."""
+    cap, side = 1100, 640
+    f = make_frame(61, cap, side, side)
+    cells = np.random.default_rng(62).permutation(cap)
+    f["x"] = ((cells % 64) * 10 + 5).astype(np.float32)
+    f["y"] = ((cells // 64) * 10 + 5).astype(np.float32)
+    for keep in (600, cap):
+        run_both(nm, cuda, [f], [cap], cap, side, side, 64, 64, keep, use=("x", "y", "kpts"))
+
+
 def test_every_subset_of_the_payload(nm, cuda):
     cap = 200
     frames = [make_frame(20 + k, cap, 160, 120) for k in range(2)]

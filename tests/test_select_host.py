@@ -187,3 +187,18 @@ def test_refusals_touch_nothing(nm):
         args.update(kw)
         with pytest.raises(nm.NmError):
             nm.sift_select_host([cap], [src["x"]], [src["y"]], 64, 48, **args)
+
+
+# nm_sift_select_workspace_bytes(n, capacity, gx, gy) as the release that introduced the selection returned it
+WORKSPACE_BYTES = {(1, 1): 49376, (1, 7): 49488, (1, 1024): 68800, (1, 65536): 1294528,
+                   (64, 1): 3160064, (64, 7): 3167232, (64, 1024): 4403200, (64, 65536): 82849792}
+
+
+def test_workspace_bytes_are_the_recorded_values(nm):
+    """The layout is stated once (key, skey, list, cstart, meta, pointer record, cell, flag; 16-byte stride); the byte count
+    it yields stays what callers have allocated so far, for every grid."""
+    ws = nm.lib().nm_sift_select_workspace_bytes
+    for (n, cap), want in WORKSPACE_BYTES.items():
+        for gx, gy in ((8, 8), (1, 1), (64, 64)):
+            assert ws(n, cap, gx, gy) == want, (n, cap, gx, gy)
+        assert want == n * ((cap * 19 + 4096 * 8 + (4096 + 8) * 4 + 8 * 4 + 128 + 15) // 16 * 16)
