@@ -805,6 +805,42 @@ NM_API int nm_sift_match_u8_host(int n, const unsigned char *const *A, const int
                                  const unsigned char *const *B, const int *const *nB, int capB, int *const *result,
                                  float ambiguity);
 
+/* ---- k-nearest-neighbour matching of unsigned-char descriptors on the i8 matrix cores (no reference counterpart): for
+ * every row of A the k nearest rows of B with their distances, where nm_sift_match_u8_batch_dev gives one index already cut
+ * by one ratio. n in [1, NM_MATCH_KNN_U8_MAX_BATCH] pairs in TWO launches on `stream` whatever n and k are (row norms, k-NN);
+ * no allocation, no synchronisation, no host read -- capturable into a HIP graph. Pair p (HOST tables of n device pointers):
+ *   A[p] / B[p]        capA x 128 / capB x 128 unsigned chars, row-major, 16-byte aligned (out_u8 of the finish);
+ *   d_nA[p], d_nB[p]   DEVICE ints: nA = clip(*d_nA[p], 0, capA), nB = clip(*d_nB[p], 0, capB). Rows beyond them are never
+ *                      read. A pair with nA <= 0 or nB <= 0 is a no-op;
+ *   index[p]           device, capA x k ints, row-major; rows at and beyond nA are not written;
+ *   distance[p]        device, capA x k ints, the same layout. The `distance` table may be NULL: indices only.
+ * k in [1, NM_MATCH_KNN_U8_MAX_K]. Per pair, all integers:
+ *   Distance: d(i, j) = sum over q of (A[i][q] - B[j][q])^2, exact (<= 128 * 255^2 = 8 323 200).
+ *   Order: for a row i < nA the candidates j < nB are ordered by (d(i, j), j) ascending -- a total order; the lowest index
+ *     wins every tie.
+ *   Filled slots: with m = min(k, nB), index[p][i * k + s] and distance[p][i * k + s] hold the s-th candidate of that order
+ *     and its distance, for s < m.
+ *   Empty slots: for m <= s < k the index is -1 and the distance 0x7fffffff.
+ * A pair's outputs depend on that pair's inputs alone, never on n, the slot or scheduling (no atomics). Column 0 of index
+ * and distance is the matcher's first minimum and min1; columns 0 and 1 of a k >= 2 call put through the matcher's last step
+ * (min2 = 2139095040.0f when nB == 1) give nm_sift_match_u8_batch_dev's result for any ambiguity.
+ * workspace: device, 16-byte aligned, nm_sift_match_knn_u8_workspace_bytes(n, capA, capB) bytes (0 for arguments out of
+ * range; the matcher's figure), no contents expected or preserved.
+ * Returns hipErrorInvalidValue, before anything is launched or dereferenced, for k not in [1, 8], n not in [1, 64], capA or
+ * capB not in [1, 2^22), a NULL A, d_nA, B, d_nB, index or workspace, a NULL among the first n entries of one of those
+ * tables or of a `distance` table that was given, or a descriptor pointer or workspace that is not 16-byte aligned.
+ * nm_sift_match_knn_u8_host: the same with every pointer in host memory (no alignment rule), no workspace and no stream: a
+ * plain loop with sorted insertion on (d, j), the same argument checks, results identical to the device entry's.        */
+#define NM_MATCH_KNN_U8_MAX_BATCH 64
+#define NM_MATCH_KNN_U8_MAX_K 8
+NM_API size_t nm_sift_match_knn_u8_workspace_bytes(int n, int capA, int capB);
+NM_API int nm_sift_match_knn_u8_batch_dev(int n, const unsigned char *const *A, const int *const *d_nA, int capA,
+                                          const unsigned char *const *B, const int *const *d_nB, int capB, int k,
+                                          int *const *index, int *const *distance, void *workspace, void *stream);
+NM_API int nm_sift_match_knn_u8_host(int n, const unsigned char *const *A, const int *const *nA, int capA,
+                                     const unsigned char *const *B, const int *const *nB, int capB, int k,
+                                     int *const *index, int *const *distance);
+
 /* ---- Mutual-nearest-neighbour filtering of a match list over unsigned-char descriptors on the i8 matrix cores: the
  * cross-check of the byte pipeline (finish -> nm_sift_match_u8_batch_dev -> this -> RANSAC), no reference counterpart. It is
  * nm_sift_match_mutual_batch_dev_f32 on bytes: given pair k's match list, a match i -> j is kept only when i is also the

@@ -124,6 +124,9 @@ _SIGNATURES = {
     "nm_sift_match_u8_workspace_bytes": (_SZ, [_I, _I, _I]),
     "nm_sift_match_u8_batch_dev": (_I, [_I, _P, _P, _I, _P, _P, _I, _P, _F, _P, _P]),
     "nm_sift_match_u8_host": (_I, [_I, _P, _P, _I, _P, _P, _I, _P, _F]),
+    "nm_sift_match_knn_u8_workspace_bytes": (_SZ, [_I, _I, _I]),
+    "nm_sift_match_knn_u8_batch_dev": (_I, [_I, _P, _P, _I, _P, _P, _I, _I, _P, _P, _P, _P]),
+    "nm_sift_match_knn_u8_host": (_I, [_I, _P, _P, _I, _P, _P, _I, _I, _P, _P]),
     "nm_sift_match_mutual_u8_workspace_bytes": (_SZ, [_I, _I, _I]),
     "nm_sift_match_mutual_u8_batch_dev": (_I, [_I, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P]),
     "nm_sift_match_mutual_u8_host": (_I, [_I, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P]),
@@ -1349,6 +1352,78 @@ def sift_match_u8_host(As, nAs, Bs, nBs, ambiguity=0.8, capA=None, capB=None, pr
     _check(lib().nm_sift_match_u8_host(n, arr(As), arr(nA), capA, arr(Bs), arr(nB), capB, arr(list(result)),
                                        float(ambiguity)), "nm_sift_match_u8_host")
     return result
+
+
+MATCH_KNN_U8_MAX_BATCH = _PAIR_MAX_BATCH
+MATCH_KNN_U8_MAX_K = 8
+KNN_U8_NONE = (-1, 0x7fffffff)                 # index and distance of a slot without a candidate
+
+
+class MatchKnnU8Workspace(_PairWorkspace):
+    """Device scratch of sift_match_knn_u8_batch_dev for up to n pairs of capA x capB rows (the integer row norms)."""
+    _bytes_fn, _what, _shape_text = "nm_sift_match_knn_u8_workspace_bytes", "u8 k-NN workspace", "n %r / capA %r / capB %r"
+
+    def __init__(self, n, capA, capB, device=None):
+        self._alloc(device, n=n, capA=capA, capB=capB)
+
+
+def _knn_k(k, *lists):
+    """k of a k-NN call, in range; the given output tensors are (rows, k)."""
+    if not isinstance(k, int) or not 1 <= k <= MATCH_KNN_U8_MAX_K:
+        raise NmError("k-NN: k %r outside [1, %d]" % (k, MATCH_KNN_U8_MAX_K))
+    if any(t.ndim != 2 or t.shape[1] != k for ts in lists for t in ts or ()):
+        raise NmError("k-NN: index and distance tensors must be (rows, %d)" % k)
+    return k
+
+
+def sift_match_knn_u8_batch_dev(As, d_nAs, Bs, d_nBs, k, indices=None, distances=None, want_distance=True, workspace=None,
+                                capA=None, capB=None):
+    """The k nearest rows of Bs[p] for every row of As[p], n = len(As) <= MATCH_KNN_U8_MAX_BATCH pairs of uint8 descriptors
+    on the i8 matrix cores (nm_sift_match_knn_u8_batch_dev): two launches on the current stream, no host read. As / Bs are
+    uint8 device tensors (rows, 128) (out_u8 of desc_finish_batch_dev), d_nAs / d_nBs int32 DEVICE sizes, k in
+    [1, MATCH_KNN_U8_MAX_K]. Row i of indices[p] lists the candidates by (distance, index) ascending, distances[p] their exact
+    integer squared distances; slots at and beyond min(k, nB) hold -1 / 0x7fffffff. indices / distances: n int32 device
+    tensors (>= capA, k) to write into (default: new, filled with -1 / 0x7fffffff); rows at and beyond nA keep their
+    contents. want_distance=False (and no distances given) asks for indices only. workspace: a MatchKnnU8Workspace
+    (default: new). Returns (indices, distances), distances None when not wanted."""
+    torch = _torch()
+    want_distance = want_distance or distances is not None
+    n = _pair_count(As, d_nAs, Bs, d_nBs, indices, distances)
+    k = _knn_k(k, indices, distances)
+    capA, capB = _u8_caps(As, Bs, list(indices or ()) + list(distances or ()), capA, capB)
+    device = _pair_device(list(As) + list(d_nAs) + list(Bs) + list(d_nBs) + list(indices or ()) + list(distances or ()) +
+                          [workspace.buf if workspace is not None else None], list(d_nAs) + list(d_nBs))
+    new = lambda fill: [torch.full((capA, k), fill, dtype=torch.int32, device=device) for _ in range(n)]
+    indices = new(KNN_U8_NONE[0]) if indices is None else indices
+    distances = (new(KNN_U8_NONE[1]) if distances is None else distances) if want_distance else None
+    workspace = _pair_workspace(MatchKnnU8Workspace, workspace, device, n, capA, capB)
+    arr, u8, i32 = _pair_dev_table, torch.uint8, torch.int32
+    _check(lib().nm_sift_match_knn_u8_batch_dev(n, arr(As, u8), arr(d_nAs, i32), capA, arr(Bs, u8), arr(d_nBs, i32), capB, k,
+                                                arr(indices, i32), arr(distances, i32), _dev(workspace.buf), _stream()),
+           "nm_sift_match_knn_u8_batch_dev")
+    return indices, distances
+
+
+def sift_match_knn_u8_host(As, nAs, Bs, nBs, k, capA=None, capB=None, want_distance=True, prior=KNN_U8_NONE):
+    """sift_match_knn_u8_batch_dev on the host (nm_sift_match_knn_u8_host): numpy in and out, identical results. nAs / nBs
+    are host ints. prior: what the index and the distance rows are pre-filled with (a pair of values or of (n, capA, k)
+    arrays). Returns (indices, distances), (n, capA, k) int32 each, distances None when not wanted."""
+    import numpy as np
+    n = _pair_count(As, nAs, Bs, nBs)
+    k = _knn_k(k)
+    As, Bs = (_pair_host_arrays(vs, np.uint8, flat=False) for vs in (As, Bs))
+    capA, capB = _u8_caps(As, Bs, None, capA, capB)
+    index = np.empty((n, capA, k), np.int32)
+    index[...] = prior[0]
+    dist = None
+    if want_distance:
+        dist = np.empty((n, capA, k), np.int32)
+        dist[...] = prior[1]
+    nA, nB = _pair_host_sizes(nAs), _pair_host_sizes(nBs)
+    arr = _pair_host_table
+    _check(lib().nm_sift_match_knn_u8_host(n, arr(As), arr(nA), capA, arr(Bs), arr(nB), capB, k, arr(list(index)),
+                                           arr(list(dist)) if want_distance else None), "nm_sift_match_knn_u8_host")
+    return index, dist
 
 
 class MatchMutualU8Workspace(_PairWorkspace):

@@ -16,6 +16,15 @@
 // No LDS, no atomics. The lane -> (row, k) map of the i8 operands is checked by tools/micro/mfma_i8_model.hip. The operand
 // fragments, the row norm, PAD_NORM and the tile stream are nm_match_u8_dev.hpp, shared with the mutual filter
 // (nm_match_mutual_u8.hip).
+// The k-nearest-neighbour entry (nm_sift_match_knn_u8_batch_dev) is the same two launches with match_knn_u8_kernel<L> as the
+// second: same grid, same query fragments, same tile stream. In place of (min1, index, min2) a lane keeps, per query group,
+// the L = 1, 2, 4 or 8 best (d, j) of its lane half in registers, ascending (the runtime k takes the next L up and stores
+// its first k). Per tile the lane's smallest key (d << 4 | e) is found as above; while the wave votes that some lane's
+// smallest beats that lane's list tail, every lane inserts its smallest (no change where it does not beat the tail) and
+// takes its next key above the one just taken: at most L rounds, because a lane's own L insertions of ascending keys make
+// up its whole list. Insertion is strict in d, visits ascend in j, so equal distances stay in index order; the two halves'
+// lists are merged at the end by (d, j) and half 0 stores. Slots at and beyond min(k, nB) are stored as -1 / 0x7fffffff
+// whatever the list holds there (padded rows, or its start value).
 #include "nm_common.hpp"
 #include "nm_match_u8_dev.hpp"
 #include "nm_pair_batch.hpp"
@@ -45,6 +54,20 @@ struct MatchArgs {                          // 5 x 64 pointers: 2.5 KB of the 4 
     int *result[NM_MATCH_U8_MAX_BATCH];
 };
 static_assert(sizeof(MatchArgs) + 64 < 4096, "match kernel arguments exceed 4 KB");
+struct KnnArgs {                            // 6 x 64 pointers: 3 KB of the 4 KB of kernel arguments
+    const unsigned char *A[NM_MATCH_KNN_U8_MAX_BATCH];
+    const int *d_nA[NM_MATCH_KNN_U8_MAX_BATCH];
+    const unsigned char *B[NM_MATCH_KNN_U8_MAX_BATCH];
+    const int *d_nB[NM_MATCH_KNN_U8_MAX_BATCH];
+    int *index[NM_MATCH_KNN_U8_MAX_BATCH];
+    int *distance[NM_MATCH_KNN_U8_MAX_BATCH];    // all null: indices only
+};
+static_assert(sizeof(KnnArgs) + 64 < 4096, "k-NN kernel arguments exceed 4 KB");
+static_assert(NM_MATCH_KNN_U8_MAX_BATCH == NM_MATCH_U8_MAX_BATCH, "the k-NN entry shares the matcher's norms launch");
+
+constexpr int KNN_NONE = KEY_INF;           // the distance of a slot without a candidate (its index is -1)
+constexpr int LIST_INF = KEY_INF >> 4;      // an unused list entry: above every padded row's distance, and what KEY_INF decodes to
+static_assert(LIST_INF > PAD_NORM + (1 << 23), "an unused list entry sorts behind the padded rows");
 
 __host__ __device__ inline size_t rows_a(int capA) { return ((size_t)capA + QB - 1) / QB * QB; }
 __host__ __device__ inline size_t rows_b(int capB) { return ((size_t)capB + TILE - 1) / TILE * TILE; }
@@ -140,6 +163,93 @@ __global__ __launch_bounds__(TB) void match_u8_kernel(const MatchArgs a, int cap
     }
 }
 
+// (d, j) goes into the ascending list (ld, lj) in front of the first entry it is `before`, the last entry dropping out; no
+// change when it is before none.
+template <int L, class Before>
+__device__ __forceinline__ void list_insert(int (&ld)[L], int (&lj)[L], int d, int j, Before before)
+{
+#pragma unroll
+    for (int s = L - 1; s > 0; --s) {
+        const bool up = before(d, j, ld[s - 1], lj[s - 1]), here = before(d, j, ld[s], lj[s]);
+        ld[s] = up ? ld[s - 1] : (here ? d : ld[s]);
+        lj[s] = up ? lj[s - 1] : (here ? j : lj[s]);
+    }
+    const bool here = before(d, j, ld[0], lj[0]);
+    ld[0] = here ? d : ld[0];
+    lj[0] = here ? j : lj[0];
+}
+
+template <int L>
+__global__ __launch_bounds__(TB) void match_knn_u8_kernel(const KnnArgs a, int capA, int capB, int kk, void *__restrict__ ws)
+{
+    static_assert(L >= 1 && L <= NM_MATCH_KNN_U8_MAX_K && L < 16, "a tile's 16 keys outlast L rounds");
+    const int k = blockIdx.y, lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
+    const int nA = nmp::clip(*a.d_nA[k], capA), nB = nmp::clip(*a.d_nB[k], capB);
+    if (nA <= 0 || nB <= 0) return;                                  // a pair without rows is a no-op
+    const int q0 = blockIdx.x * QB + (threadIdx.x >> 6) * QW;
+    if (q0 >= nA) return;                                            // uniform over the wave; no barrier follows
+    const unsigned char *__restrict__ Ad = a.A[k];
+    const int *__restrict__ na = norms_of(ws, k, capA, capB);
+
+    Frag qf[QG];
+    int nq[QG], ld[QG][L], lj[QG][L];
+#pragma unroll
+    for (int g = 0; g < QG; ++g) {
+        const int qrow = last_real(q0 + 32 * g + r, nA);             // a lane past nA repeats the last row and writes nothing
+        qf[g] = load_frag(Ad + (size_t)qrow * DIM, h);
+        nq[g] = na[qrow];
+#pragma unroll
+        for (int s = 0; s < L; ++s) { ld[g][s] = LIST_INF; lj[g][s] = -1; }
+    }
+
+    // Strict in d alone: this lane half meets its candidates in ascending index, so an equal distance belongs behind.
+    const auto nearer = [](int d, int, int ds, int) { return d < ds; };
+    for_tiles(a.B[k], na + rows_a(capA), nB, 0, (nB + TILE - 1) / TILE, r, h, [&](int t, const Frag cf, const Norm16 cn) {
+#pragma unroll
+        for (int g = 0; g < QG; ++g) {
+            const i32x16 acc = tile_product(cf, qf[g]);
+            int key[16], g1 = KEY_INF;
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                key[e] = ((nq[g] + cn.g[e >> 2][e & 3] - 2 * acc[e]) << 4) | e;
+                g1 = min(g1, key[e]);
+            }
+            for (int round = 0; round < L && __any((g1 >> 4) < ld[g][L - 1]); ++round) {
+                list_insert<L>(ld[g], lj[g], g1 >> 4, acc_row(t, g1 & 15, h), nearer);
+                if (L > 1) {                                         // the smallest key above g1: keys at or below it wrap high
+                    const unsigned above = (unsigned)g1 + 1u;
+                    unsigned off = 0xffffffffu;
+#pragma unroll
+                    for (int e = 0; e < 16; ++e) off = min(off, (unsigned)key[e] - above);
+                    g1 = (int)(above + off);
+                }
+            }
+        }
+    });
+
+    const auto before = [](int d, int j, int ds, int js) { return d < ds || (d == ds && j < js); };
+    const int m = min(kk, nB);
+#pragma unroll
+    for (int g = 0; g < QG; ++g) {
+        int od[L], oj[L];
+#pragma unroll
+        for (int s = 0; s < L; ++s) { od[s] = __shfl_xor(ld[g][s], 32); oj[s] = __shfl_xor(lj[g][s], 32); }
+#pragma unroll
+        for (int s = 0; s < L; ++s) list_insert<L>(ld[g], lj[g], od[s], oj[s], before);
+        const int qi = q0 + 32 * g + r;
+        if (h == 0 && qi < nA) {
+            int *__restrict__ oi = a.index[k] + (size_t)qi * kk;
+            int *__restrict__ dd = a.distance[k] ? a.distance[k] + (size_t)qi * kk : nullptr;
+#pragma unroll
+            for (int s = 0; s < L; ++s)
+                if (s < kk) {
+                    oi[s] = s < m ? lj[g][s] : -1;
+                    if (dd) dd[s] = s < m ? ld[g][s] : KNN_NONE;
+                }
+        }
+    }
+}
+
 // ---- the host twin: exact integer distances, the first minimum and the smallest of the others, the same last step ----
 void host_match_pair(const unsigned char *A, int nA, const unsigned char *B, int nB, float ambiguity, int *result)
 {
@@ -163,6 +273,44 @@ bool u8_args_ok(int n, const unsigned char *const *A, const int *const *nA, int 
                 const int *const *nB, int capB, int *const *result)
 {
     return nmp::range_ok(n, capA) && nmp::cap_ok(capB) && nmp::tables_ok(n, {A, nA, B, nB, result}, {}, {});
+}
+
+// The k-NN host twin: sorted insertion on (d, j) into a list of k, then the fill rule for the slots without a candidate.
+void host_knn_pair(const unsigned char *A, int nA, const unsigned char *B, int nB, int k, int *index, int *distance)
+{
+    if (nA <= 0 || nB <= 0) return;
+    for (int i = 0; i < nA; ++i) {
+        int ld[NM_MATCH_KNN_U8_MAX_K], lj[NM_MATCH_KNN_U8_MAX_K], held = 0;
+        for (int j = 0; j < nB; ++j) {
+            int d = 0;
+            for (int q = 0; q < DIM; ++q) {
+                const int t = (int)A[(size_t)i * DIM + q] - (int)B[(size_t)j * DIM + q];
+                d += t * t;
+            }
+            const auto before = [&](int s) { return d < ld[s] || (d == ld[s] && j < lj[s]); };
+            if (held == k && !before(k - 1)) continue;
+            int s = held < k ? held++ : k - 1;
+            for (; s > 0 && before(s - 1); --s) { ld[s] = ld[s - 1]; lj[s] = lj[s - 1]; }
+            ld[s] = d; lj[s] = j;
+        }
+        for (int s = 0; s < k; ++s) {
+            index[(size_t)i * k + s] = s < held ? lj[s] : -1;
+            if (distance) distance[(size_t)i * k + s] = s < held ? ld[s] : KNN_NONE;
+        }
+    }
+}
+
+bool knn_args_ok(int n, const unsigned char *const *A, const int *const *nA, int capA, const unsigned char *const *B,
+                 const int *const *nB, int capB, int k, int *const *index, int *const *distance)
+{
+    return k >= 1 && k <= NM_MATCH_KNN_U8_MAX_K && nmp::range_ok(n, capA) && nmp::cap_ok(capB) &&
+           nmp::tables_ok(n, {A, nA, B, nB, index}, {distance}, {});
+}
+
+template <int L>
+void launch_knn(const KnnArgs &m, int n, int capA, int capB, int k, void *workspace, hipStream_t stream)
+{
+    hipLaunchKernelGGL(match_knn_u8_kernel<L>, dim3(nm_divup(capA, QB), n), dim3(TB), 0, stream, m, capA, capB, k, workspace);
 }
 
 }  // namespace
@@ -202,5 +350,46 @@ extern "C" int nm_sift_match_u8_host(int n, const unsigned char *const *A, const
     if (!u8_args_ok(n, A, nA, capA, B, nB, capB, result)) return (int)hipErrorInvalidValue;
     for (int k = 0; k < n; ++k)
         host_match_pair(A[k], nmp::clip(*nA[k], capA), B[k], nmp::clip(*nB[k], capB), ambiguity, result[k]);
+    return 0;
+}
+
+extern "C" size_t nm_sift_match_knn_u8_workspace_bytes(int n, int capA, int capB)
+{
+    return nm_sift_match_u8_workspace_bytes(n, capA, capB);          // the matcher's norms, the matcher's layout
+}
+
+extern "C" int nm_sift_match_knn_u8_batch_dev(int n, const unsigned char *const *A, const int *const *d_nA, int capA,
+                                              const unsigned char *const *B, const int *const *d_nB, int capB, int k,
+                                              int *const *index, int *const *distance, void *workspace, void *stream)
+{
+    if (!knn_args_ok(n, A, d_nA, capA, B, d_nB, capB, k, index, distance) || !workspace ||
+        !operands_aligned(n, A, B, workspace))
+        return (int)hipErrorInvalidValue;
+    NormArgs p;
+    KnnArgs m;
+    nmp::fill_slots(p.A, A, 0, n); nmp::fill_slots(p.d_nA, d_nA, 0, n); nmp::fill_slots(p.B, B, 0, n);
+    nmp::fill_slots(p.d_nB, d_nB, 0, n);
+    nmp::fill_slots(m.A, A, 0, n); nmp::fill_slots(m.d_nA, d_nA, 0, n); nmp::fill_slots(m.B, B, 0, n);
+    nmp::fill_slots(m.d_nB, d_nB, 0, n); nmp::fill_slots(m.index, index, 0, n); nmp::fill_slots(m.distance, distance, 0, n);
+    const size_t rows = rows_a(capA) > rows_b(capB) ? rows_a(capA) : rows_b(capB);
+    hipLaunchKernelGGL(match_u8_norms_kernel, dim3((unsigned)((rows + TB - 1) / TB), 2, n), dim3(TB), 0, nm_stream(stream), p,
+                       capA, capB, workspace);
+    NM_LAUNCH_CHECK();
+    if (k == 1) launch_knn<1>(m, n, capA, capB, k, workspace, nm_stream(stream));
+    else if (k == 2) launch_knn<2>(m, n, capA, capB, k, workspace, nm_stream(stream));
+    else if (k <= 4) launch_knn<4>(m, n, capA, capB, k, workspace, nm_stream(stream));
+    else launch_knn<8>(m, n, capA, capB, k, workspace, nm_stream(stream));
+    NM_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int nm_sift_match_knn_u8_host(int n, const unsigned char *const *A, const int *const *nA, int capA,
+                                         const unsigned char *const *B, const int *const *nB, int capB, int k,
+                                         int *const *index, int *const *distance)
+{
+    if (!knn_args_ok(n, A, nA, capA, B, nB, capB, k, index, distance)) return (int)hipErrorInvalidValue;
+    for (int p = 0; p < n; ++p)
+        host_knn_pair(A[p], nmp::clip(*nA[p], capA), B[p], nmp::clip(*nB[p], capB), k, index[p],
+                      distance ? distance[p] : nullptr);
     return 0;
 }

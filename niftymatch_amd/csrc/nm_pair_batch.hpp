@@ -19,7 +19,7 @@ constexpr int CAP_LIMIT = 1 << 22;          // capacities (rows per pair) lie in
 static_assert(NM_RANSAC_MAX_BATCH == MAX_BATCH && NM_MATCH_GUIDED_MAX_BATCH == MAX_BATCH &&
               NM_MATCH_MUTUAL_MAX_BATCH == MAX_BATCH && NM_MATCH_MUTUAL_U8_MAX_BATCH == MAX_BATCH &&
               NM_MATCH_U8_MAX_BATCH == MAX_BATCH && NM_DESC_FINISH_MAX_BATCH == MAX_BATCH &&
-              NM_SELECT_MAX_BATCH == MAX_BATCH,
+              NM_SELECT_MAX_BATCH == MAX_BATCH && NM_MATCH_KNN_U8_MAX_BATCH == MAX_BATCH,
               "public header and pair-batch convention disagree");
 
 /* A device size as the kernels (and the host twins) use it */
