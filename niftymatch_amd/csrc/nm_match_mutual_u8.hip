@@ -149,11 +149,7 @@ void host_mutual_u8_pair(const unsigned char *A, int nA, int capA, const unsigne
         const int j = i < nA ? matches[i] : -1;
         if (i < nA && is_claim(j, nB)) {
             const unsigned char *bj = B + (size_t)j * DIM;
-            int tau = 0;
-            for (int q = 0; q < DIM; ++q) {
-                const int t = (int)A[(size_t)i * DIM + q] - (int)bj[q];
-                tau += t * t;
-            }
+            const int tau = row_distance(A + (size_t)i * DIM, bj);
             bool beaten = false;
             for (int ip = 0; ip < nA && !beaten; ++ip) {
                 int d = 0;

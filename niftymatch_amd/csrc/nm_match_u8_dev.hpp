@@ -1,7 +1,8 @@
-// nm_match_u8_dev.hpp -- what the two users of v_mfma_i32_32x32x32_i8 on unsigned-char descriptors share (nm_match_u8.hip, the
-// matcher, and nm_match_mutual_u8.hip, the mutual filter): the operand fragments of a 128-byte row (bytes - 128 as signed
-// i8), the integer row norm |row - 128|^2, the norm of a row that does not exist, the alignment test of the entries, and the
-// tile stream of their hot kernels.
+// nm_match_u8_dev.hpp -- what the three users of v_mfma_i32_32x32x32_i8 on unsigned-char descriptors share (the matcher and
+// the k-NN entry, which are one scan kernel with two outputs in nm_match_u8.hip, and the mutual filter's scan in
+// nm_match_mutual_u8.hip): the operand fragments of a 128-byte row (bytes - 128 as signed i8), the integer row norm
+// |row - 128|^2, the norm of a row that does not exist, the alignment test of the entries, the tile stream of their hot
+// kernels, and the plain integer distance of two rows that their host twins use.
 // A fragment is one lane's share of a row for the four k steps of a 32 x 32 x 128 product: lane (r = lane & 31, h = lane >>
 // 5) holds bytes 32 t + 16 h .. + 15 of row r in step t. The accumulator holds the B operand's row on its column (lane & 31)
 // and the A operand's rows (e & 3) + 8 (e >> 2) + 4 (lane >> 5) in its 16 registers e (tools/micro/mfma_i8_model.hip).
@@ -10,7 +11,7 @@
 // their fragments Frag qf[QG] in 32 registers as the B operand. for_tiles streams the other side's rows in tiles of 32 as the
 // A operand straight from global memory, the next tile and its norms requested before this one is used; per tile the kernel's
 // body takes tile_product(cf, qf[g]) (a.b of 32 x 32 rows over the 4 k steps) and decodes a register with acc_row. What a
-// kernel makes of the 16 accumulators (a running top-2, a threshold test) is its own.
+// kernel makes of the 16 accumulators (an ordered list of the best few, a threshold test) is its own.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -102,6 +103,17 @@ __device__ __forceinline__ i32x16 tile_product(const Frag &cf, const Frag &qf)
 
 /* The streamed row that register e of tile t's accumulator holds in lane half h */
 __device__ __forceinline__ int acc_row(int t, int e, int h) { return t * TILE + (e & 3) + 8 * (e >> 2) + 4 * h; }
+
+/* Host twins: the exact squared distance of two rows, a plain sum of DIM integer squares */
+inline int row_distance(const unsigned char *a, const unsigned char *b)
+{
+    int d = 0;
+    for (int q = 0; q < DIM; ++q) {
+        const int t = (int)a[q] - (int)b[q];
+        d += t * t;
+    }
+    return d;
+}
 
 inline bool aligned16(int n, const unsigned char *const *t)
 {

@@ -51,6 +51,15 @@ def matcher_last_step(idx, dist, nB, ambiguity, prior):
     return res
 
 
+def matcher_from_lists(case, idx, dist, ambiguity, capA, capB):
+    """matcher_last_step on the rows below nA of a pair's (capA, k >= 2) lists; a result pre-filled with case['prior']."""
+    nA, nB = min(max(case["nA"], 0), capA), min(max(case["nB"], 0), capB)
+    res = np.full(capA, case["prior"], np.int32)
+    if nA > 0 and nB > 0:
+        res[:nA] = matcher_last_step(idx[:nA], dist[:nA], nB, ambiguity, res[:nA])
+    return res
+
+
 def extreme_cases():
     """match_u8_ref.extremes_case() as it is (70 candidates: the eight nearest of a row never include its farthest), then
     the same rows with nB = 8, where a k = 8 list holds every candidate and ends on 128 * 255^2 for the rows of all 0 and

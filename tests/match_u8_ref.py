@@ -141,6 +141,39 @@ def ragged_batch(n, seed=0):
     return cases, capA, capB
 
 
+def shared_scan_cases():
+    """The smallest shapes at which one list kernel behind both entries can differ from a top-2 kernel, in buffers of 300 x
+    40 rows (random bytes beyond the sizes). Returns ([one candidate, two identical candidates, empty, ties], capA, capB):
+      one candidate   65 x 1: no second candidate; row 7 equals the candidate (min1 = 0, index 0);
+      identical       65 x 2, B[0] == B[1]: min2 == min1 everywhere (never below ambiguity <= 1); rows 0..31 equal them,
+                      min2 == 0, the entry keeps its prior;
+      empty           0 x 33;
+      ties            257 x 33, one row into the second tile: B[5] == B[1] (the two lane halves of one tile), B[32] == B[0]
+                      (across the tile boundary); query 10 is equally near rows 1 and 5, query 11 rows 0 and 32, nearer
+                      than to any other row.
+    nA = 65 is one row past a wave, 257 one past a workgroup."""
+    rng = np.random.default_rng(13)
+    capA, capB = 300, 40
+    fresh = lambda: (rng.integers(0, 256, (capA, 128)), rng.integers(0, 256, (capB, 128)))
+    A1, B1 = fresh()
+    A1[7] = B1[0]
+    A2, B2 = fresh()
+    B2[1] = B2[0]
+    A2[:32] = B2[0]
+    A3, B3 = fresh()
+    A4, B4 = fresh()
+    B4[5], B4[32] = B4[1], B4[0]
+    for q, j in ((10, 1), (11, 0)):
+        A4[q] = B4[j]
+        A4[q, q] += 3 if A4[q, q] < 200 else -3
+    cases = [_case(A1, B1, nA=65, nB=1, what="65 x 1"), _case(A2, B2, nA=65, nB=2, what="65 x 2 identical candidates"),
+             _case(A3, B3, nA=0, nB=33, what="empty, 0 x 33"), _case(A4, B4, nA=257, nB=33, what="257 x 33 with ties")]
+    D = distances(A4[:257], B4[:33])
+    assert D[10, 1] == D[10, 5] == 9 == D[11, 0] == D[11, 32] and (np.sort(D[10:12], axis=1)[:, 2] > 9).all()
+    assert (distances(A2[:32], B2[:2]) == 0).all() and distances(A2[32:65], B2[:2]).min() > 0
+    return cases, capA, capB
+
+
 def expected_clipped(case, capA, capB):
     c = dict(case, nB=min(max(case["nB"], 0), capB))
     return expected(c, capA)

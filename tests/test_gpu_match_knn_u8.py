@@ -100,6 +100,22 @@ def test_ragged_batches(nm, cuda, n):
     assert np.array_equal(ai[0], idx[last]) and np.array_equal(ad[0], dist[last]), "a pair's lists depend on the batch"
 
 
+@pytest.mark.parametrize("k", [1, 2, 3, 8])
+def test_shared_scan_cases(nm, cuda, k):
+    """M.shared_scan_cases() at a k of every list length the kernel is built for, each alone and as a 3-pair batch with the
+    empty pair: host twin and restatement, untouched rows, and equal distances in index order."""
+    cases, capA, capB = M.shared_scan_cases()
+    one, same, empty, ties = cases
+    for batch in [[one], [same], [ties], [same, empty, ties]]:
+        idx, dist = _assert_all_equal(nm, cuda, batch, k, capA, capB)
+        for p, c in enumerate(batch):
+            assert (idx[p][c["nA"]:] == K.PRIOR[0]).all() and (dist[p][c["nA"]:] == K.PRIOR[1]).all(), c["what"]
+    m = min(k, 2)
+    assert (idx[0][:65, :m] == np.arange(m)).all() and (dist[0][:32, :m] == 0).all() and (idx[0][:65, m:] == K.NO_INDEX).all()
+    if k >= 2:
+        assert tuple(idx[2][10, :2]) == (1, 5) and tuple(idx[2][11, :2]) == (0, 32) and (dist[2][10:12, :2] == 9).all()
+
+
 @pytest.mark.parametrize("amb", [0.8, 1.0])
 def test_k2_lists_reproduce_the_matcher(nm, cuda, amb):
     import torch

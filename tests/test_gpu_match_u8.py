@@ -64,6 +64,34 @@ def test_ragged_batches(nm, cuda, n):
         assert (got[i][min(max(c["nA"], 0), capA):] == -7).all(), "a row beyond nA was written"
 
 
+@pytest.mark.parametrize("amb", [0.8, 1.0])
+def test_shared_scan_cases_and_ratio_rule_on_device_k2_lists(nm, cuda, amb):
+    """M.shared_scan_cases() (one candidate, two identical candidates, one row into the second tile, one row past a wave and
+    past a workgroup, ties across the lane halves and the tile boundary), each alone and as a 3-pair batch with the empty
+    pair: host twin, fp32 matcher, restatement, and the ratio rule applied to the device's own k = 2 lists."""
+    import torch
+    import knn_u8_ref as K
+    cases, capA, capB = M.shared_scan_cases()
+    one, same, empty, ties = cases
+    for batch in [[one], [same], [ties], [same, empty, ties]]:
+        got = _assert_all_equal(nm, cuda, batch, capA, capB, amb)
+        up = lambda a: torch.from_numpy(a).to(cuda)
+        size = lambda v: torch.tensor([v], dtype=torch.int32, device=cuda)
+        idx, dist = nm.sift_match_knn_u8_batch_dev([up(c["A"]) for c in batch], [size(c["nA"]) for c in batch],
+                                                   [up(c["B"]) for c in batch], [size(c["nB"]) for c in batch], 2,
+                                                   capA=capA, capB=capB)
+        torch.cuda.synchronize()
+        for p, c in enumerate(batch):
+            assert np.array_equal(got[p], M.expected_clipped(dict(c, amb=amb), capA, capB)), c["what"]
+            lists = K.matcher_from_lists(c, idx[p].cpu().numpy(), dist[p].cpu().numpy(), amb, capA, capB)
+            assert np.array_equal(got[p], lists), (c["what"], "ratio rule on the device k = 2 lists")
+            assert (got[p][max(c["nA"], 0):] == -7).all(), "a row beyond nA was written"
+    assert (got[0][:32] == -7).all() and (got[0][32:65] == -1).all()          # min2 == 0 kept, min2 == min1 rejected
+    assert (got[1] == -7).all()                                               # the empty pair
+    above = _assert_all_equal(nm, cuda, [ties], capA, capB, 1.5)[0]           # only an ambiguity above 1 shows a tie's index
+    assert above[10] == 1 and above[11] == 0, "the lower index wins a tie"
+
+
 def _finished_1080p(nm, dev, seeds, want_rows=4096):
     """uint8 descriptors of synthetic 1080p frames: detect, describe and finish on the device."""
     import torch

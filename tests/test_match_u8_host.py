@@ -64,6 +64,25 @@ def test_ragged_batches(nm, oracle, n):
     assert np.array_equal(alone[0], got[0])                     # a pair's result does not depend on the batch
 
 
+@pytest.mark.parametrize("amb", [0.8, 1.0])
+def test_host_matcher_is_the_ratio_rule_on_the_host_k2_lists(nm, amb):
+    """The host matcher is the host k-NN twin at k = 2 followed by the last step: its result equals that step restated in
+    numpy on the host k = 2 lists, alone and as a 3-pair batch with the empty pair, and the restatement of the matcher."""
+    import knn_u8_ref as K
+    cases, capA, capB = M.shared_scan_cases()
+    for batch in [[c] for c in cases] + [cases[1:]]:
+        col = lambda key: [c[key] for c in batch]
+        got = nm.sift_match_u8_host(col("A"), col("nA"), col("B"), col("nB"), ambiguity=amb, capA=capA, capB=capB, prior=-7)
+        idx, dist = nm.sift_match_knn_u8_host(col("A"), col("nA"), col("B"), col("nB"), 2, capA=capA, capB=capB, prior=K.PRIOR)
+        for p, c in enumerate(batch):
+            assert np.array_equal(got[p], K.matcher_from_lists(c, idx[p], dist[p], amb, capA, capB)), c["what"]
+            assert np.array_equal(got[p], M.expected_clipped(dict(c, amb=amb), capA, capB)), c["what"]
+            assert (got[p][max(c["nA"], 0):] == -7).all(), "a row beyond nA was written"
+    # the batch (identical, empty, ties): min2 == 0 kept, min2 == min1 rejected, nothing for the empty pair, ties by index
+    assert (got[0][:32] == -7).all() and (got[0][32:65] == -1).all()
+    assert (got[1] == -7).all() and tuple(idx[2][10]) == (1, 5) and tuple(idx[2][11]) == (0, 32)
+
+
 def finished_real_pair(oracle, nm, rows=4096):
     """Two views of one synthetic scene, detected and described by the CPU oracle, finished by the host twin: (A, B) uint8."""
     import helpers as H

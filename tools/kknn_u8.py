@@ -1,7 +1,7 @@
 """What the u8 k-nearest-neighbour entry (nm_sift_match_knn_u8_batch_dev) costs beside the u8 matcher on the same
 descriptors, on the GPU.
 
-    python tools/kknn_u8.py [--pairs 16] [--rounds 20] [--trace] [--out FILE]
+    python tools/kknn_u8.py [--pairs 16] [--rounds 20] [--rows N] [--trace] [--out FILE]
 
 Input: `pairs` frame pairs of the bench's synthetic 1080p frames (uniform noise, Gaussian pre-blur; about 12k keypoints
 each), detected once, finished once (NM_DESC_L2, u8). Arms, each bracketed by device events on one stream and alternated
@@ -10,7 +10,8 @@ round by round after warm-up:
     knn1, knn2, knn4, knn8   nm_sift_match_knn_u8_batch_dev at k = 1, 2, 4, 8, indices and distances.
 Pair 0 of every arm is checked against its host twin first, and the k = 2 lists of every pair, put through the matcher's
 last step, against the matcher's result. Prints one JSON line (and writes it to --out): medians with min-max, per pair, and
-each k's ratio to the matcher. --trace runs only a few calls of each arm (for a kernel trace in a run of its own).
+each k's ratio to the matcher. --rows N clips every frame's row count to N. --trace runs only a few calls of each arm (for
+a kernel trace in a run of its own; the arms are match_scan_u8_kernel<2, RatioOut> and <L, ListOut>, L = 1, 2, 4, 8).
 """
 import argparse
 import json
@@ -34,6 +35,7 @@ def main():
     ap.add_argument("--pairs", type=int, default=16)
     ap.add_argument("--rounds", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--rows", type=int, default=0, help="use at most this many rows of every frame (0: all)")
     ap.add_argument("--trace", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -50,6 +52,8 @@ def main():
     torch.cuda.synchronize()
     del frames
     counts = [x.num_items for x in arenas]
+    if a.rows:
+        counts = [torch.clamp(c, max=a.rows) for c in counts]
     u8 = [torch.zeros((CAP, 128), dtype=torch.uint8, device=dev) for _ in range(2 * n)]
     stream = torch.cuda.Stream()
     with torch.cuda.stream(stream):

@@ -1,7 +1,7 @@
 """What the u8 matcher (nm_sift_match_u8_batch_dev) costs beside the fp32 matcher on the same descriptors, and what the
 descriptor finish costs beside a copy of the same bytes, on the GPU.
 
-    python tools/kmatch_u8.py [--pairs 16] [--rounds 20] [--trace]
+    python tools/kmatch_u8.py [--pairs 16] [--rounds 20] [--rows N] [--trace]
 
 Input: `pairs` frame pairs of the bench's synthetic 1080p frames (uniform noise, Gaussian pre-blur; about 12k keypoints
 each), detected once, finished once (NM_DESC_L2; fp32 and u8 outputs). Arms, each bracketed by device events on one stream
@@ -12,7 +12,9 @@ and alternated round by round after warm-up:
     copy    device-to-device copies of every frame's fp32 and u8 rows (1280 B moved per row; the finish moves 1152 B).
 Pair 0's device result is checked against the host twin first, and arm (b)'s results against arm (a)'s for every pair.
 Prints one JSON line: medians with min-max, b / a, arm (b)'s share of the i8 matrix peak, the finish's bytes per second.
---trace runs only a few calls of each arm (for a kernel trace in a run of its own).
+--rows N clips every frame's row count to N (--pairs 1 --rows 4096: one small pair, where a scan is a few tiles).
+--trace runs only a few calls of each arm (for a kernel trace in a run of its own; arm (b) is match_u8_norms_kernel and
+match_scan_u8_kernel<2, RatioOut>).
 """
 import argparse
 import json
@@ -36,6 +38,7 @@ def main():
     ap.add_argument("--pairs", type=int, default=16)
     ap.add_argument("--rounds", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--rows", type=int, default=0, help="use at most this many rows of every frame (0: all)")
     ap.add_argument("--trace", action="store_true")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "kmatch_u8.py measures on a GPU"
@@ -51,6 +54,8 @@ def main():
     torch.cuda.synchronize()
     del frames
     descs, counts = [x.desc for x in arenas], [x.num_items for x in arenas]
+    if a.rows:
+        counts = [torch.clamp(c, max=a.rows) for c in counts]
     f32 = [torch.zeros((CAP, 128), dtype=torch.float32, device=dev) for _ in range(2 * n)]
     u8 = [torch.zeros((CAP, 128), dtype=torch.uint8, device=dev) for _ in range(2 * n)]
     stream = torch.cuda.Stream()
