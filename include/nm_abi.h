@@ -886,6 +886,55 @@ NM_API int nm_sift_match_mutual_u8_host(int n, const unsigned char *const *A, co
                                         const int *const *matches, int *const *result, int *count,
                                         float *const *forward_distance);
 
+/* ---- Homography-guided matching of unsigned-char descriptors: the guided stage of the byte pipeline (finish ->
+ * nm_sift_match_u8_batch_dev -> nm_sift_match_mutual_u8_batch_dev -> RANSAC -> refit -> this -> refit), no reference
+ * counterpart. It is nm_sift_match_guided_batch_dev_f32 on bytes: the argument list is that entry's, except that A[k] / B[k]
+ * are capA x 128 / capB x 128 unsigned chars, row-major, 16-byte aligned (out_u8 of the finish). n in
+ * [1, NM_MATCH_GUIDED_U8_MAX_BATCH] pairs in THREE launches on `stream` whatever n is (pair slots 0-31, slots 32-63, the
+ * counts); no workspace, no allocation, no synchronisation, no host read, no atomics -- capturable into a HIP graph behind
+ * the refit. Rows of A beyond nA and rows of B beyond nB are never read.
+ * Semantics: result[k], count[k] and best_distance[k] are what nm_sift_match_guided_batch_dev_f32 writes for the same pair
+ * when A and B are float copies of the bytes, bit for bit. In full:
+ *   Unusable pair, valid rows and gate: those of the fp32 entry, unchanged, on the fp32 coordinates and H (status_in[k] != 1
+ *     or a non-finite H_k: result -1, count 0, best_distance +inf; valid rows i < nA with ax[i] >= 0; the gate is
+ *     nmr_is_inlier's fp32 sequence with the projection computed once per row; a NaN passes no gate).
+ *   Distance: d(i, j) = sum over q of (A[i][q] - B[j][q])^2, an exact integer <= 128 * 255^2 = 8 323 200 < 2^23, hence an
+ *     exact float too. (The kernel forms it as |a|^2 + |b|^2 - 2 a.b in unsigned 32-bit arithmetic, every term < 2^23; the
+ *     order of summation is free. The fp32 entry's fmaf chain is exact on such values: differences <= 255, partial sums
+ *     < 2^24.)
+ *   Decision: get_sift_matches' scan as the fp32 entry states it, on (float)d over the gated candidates in ascending j: the
+ *     first one sets min1 and the index, min2 starts at 2139095040.0f, a later d < min1 moves min1 to min2 and takes its
+ *     place, else d < min2 replaces min2 (strict <). result = index when min2 > 0 and min1 / min2 < ambiguity (fp32
+ *     divide) and min1 < max_distance, else -1; -1 also without a gated candidate. With a gate that passes everything and
+ *     max_distance = +inf the result equals nm_sift_match_u8_batch_dev's on a result pre-filled with -1 (nB >= 1).
+ * Outputs: result[k] (device, capA ints; ALL capA entries are written, -1 beyond nA), count (device, n ints: entries >= 0 of
+ * result[k]), best_distance (optional table, may be NULL: best_distance[k] device, capA floats = (float)min1, +inf for a row
+ * without a gated candidate). A pair's outputs depend on that pair's inputs alone, never on n, the slot or scheduling.
+ * Returns hipErrorInvalidValue, before anything is launched or dereferenced, for what the fp32 entry refuses (n not in
+ * [1, 64], capA or capB not in [1, 2^22), a non-finite radius2 or ambiguity, a NaN max_distance, a NULL required pointer --
+ * every argument but status_in, best_distance and stream -- or a NULL among the first n entries of a table) and for a
+ * descriptor pointer that is not 16-byte aligned.
+ * nm_sift_match_guided_u8_host: the same with every pointer in host memory (nA[k] / nB[k] point to host ints, no alignment
+ * rule), compiled from the same functions (csrc/nm_match_guided_math.hpp, csrc/nm_match_guided_u8_math.hpp): host and
+ * device results are identical bit for bit.                                                                            */
+#define NM_MATCH_GUIDED_U8_MAX_BATCH 64
+NM_API int nm_sift_match_guided_u8_batch_dev(int n,
+                                             const unsigned char *const *A, const float *const *ax, const float *const *ay,
+                                             const int *const *d_nA, int capA,
+                                             const unsigned char *const *B, const float *const *bx, const float *const *by,
+                                             const int *const *d_nB, int capB,
+                                             const float *H, const int *status_in, float radius2, float ambiguity,
+                                             float max_distance, int *const *result, int *count,
+                                             float *const *best_distance, void *stream);
+NM_API int nm_sift_match_guided_u8_host(int n,
+                                        const unsigned char *const *A, const float *const *ax, const float *const *ay,
+                                        const int *const *nA, int capA,
+                                        const unsigned char *const *B, const float *const *bx, const float *const *by,
+                                        const int *const *nB, int capB,
+                                        const float *H, const int *status_in, float radius2, float ambiguity,
+                                        float max_distance, int *const *result, int *count,
+                                        float *const *best_distance);
+
 /* ---- Mosaic plan and batched blend (no reference counterpart: the reference's client places frames on the host and
  * calls transform_blend once per frame). Together with nm_ransac_batch_dev_f32 the chain detect -> match -> RANSAC ->
  * plan -> blend runs on one stream with no host read and can be captured into one HIP graph.

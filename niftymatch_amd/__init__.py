@@ -130,6 +130,8 @@ _SIGNATURES = {
     "nm_sift_match_mutual_u8_workspace_bytes": (_SZ, [_I, _I, _I]),
     "nm_sift_match_mutual_u8_batch_dev": (_I, [_I, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P]),
     "nm_sift_match_mutual_u8_host": (_I, [_I, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P]),
+    "nm_sift_match_guided_u8_batch_dev": (_I, [_I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _P, _F, _F, _F, _P, _P, _P, _P]),
+    "nm_sift_match_guided_u8_host": (_I, [_I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _P, _F, _F, _F, _P, _P, _P]),
     "nm_mosaic_plan_f32": (_I, [_I, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "nm_mosaic_plan_host_f32": (_I, [_I, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "nm_transform_blend_batch": (_I, [_P, _I, _I, _P, _I, _P, _I, _I, _P, _I, _P, _I, _P, _P]),
@@ -1019,6 +1021,22 @@ def sift_match_guided_batch_dev(As, axs, ays, d_nAs, Bs, bxs, bys, d_nBs, H, sta
     descriptor distance (inf = no bound). results: n int32 device tensors of >= capA rows to write into (default: new).
     Returns (results, count[n]) and, with want_distance, the list of float32 (capA,) best distances. results[k] plugs into
     ransac_refit_batch_dev(matches=...)."""
+    return _guided_dev(_torch().float32, "nm_sift_match_guided_batch_dev_f32", As, axs, ays, d_nAs, Bs, bxs, bys, d_nBs, H,
+                       status, radius2, ambiguity, max_distance, capA, capB, results, want_distance)
+
+
+def sift_match_guided_host(As, axs, ays, nAs, Bs, bxs, bys, nBs, H, status=None, radius2=9.0, ambiguity=0.8,
+                           max_distance=float("inf"), capA=None, capB=None, want_distance=False):
+    """sift_match_guided_batch_dev on the host (nm_sift_match_guided_host_f32, the same functions): numpy in and out,
+    bit-identical results. nAs / nBs are host ints. Returns (results (n, capA) int32, count (n,)) and, with want_distance,
+    best distances (n, capA) float32."""
+    return _guided_host("float32", "nm_sift_match_guided_host_f32", As, axs, ays, nAs, Bs, bxs, bys, nBs, H, status, radius2,
+                        ambiguity, max_distance, capA, capB, want_distance)
+
+
+def _guided_dev(dtype, entry, As, axs, ays, d_nAs, Bs, bxs, bys, d_nBs, H, status, radius2, ambiguity, max_distance, capA,
+                capB, results, want_distance):
+    """The device call of both guided matchers: descriptors of `dtype`, the C entry `entry`."""
     torch = _torch()
     n = _pair_count(As, axs, ays, d_nAs, Bs, bxs, bys, d_nBs, results)
     capA = _pair_cap(capA, list(As) + list(axs) + list(ays))
@@ -1030,22 +1048,19 @@ def sift_match_guided_batch_dev(As, axs, ays, d_nAs, Bs, bxs, bys, d_nBs, H, sta
                           list(results or ()) + [H, status], list(d_nAs) + list(d_nBs))
     results, count, best = _pair_dev_match_out(n, capA, results, device, want_distance)
     arr, f, i32 = _pair_dev_table, torch.float32, torch.int32
-    _check(lib().nm_sift_match_guided_batch_dev_f32(n, arr(As, f), arr(axs, f), arr(ays, f), arr(d_nAs, i32), capA,
-                                                    arr(Bs, f), arr(bxs, f), arr(bys, f), arr(d_nBs, i32), capB,
-                                                    _dev(H, f), _dev(status, i32) if status is not None else None,
-                                                    radius2, ambiguity, max_distance, arr(results, i32), _dev(count),
-                                                    arr(best, f), _stream()), "nm_sift_match_guided_batch_dev_f32")
+    _check(getattr(lib(), entry)(n, arr(As, dtype), arr(axs, f), arr(ays, f), arr(d_nAs, i32), capA, arr(Bs, dtype),
+                                 arr(bxs, f), arr(bys, f), arr(d_nBs, i32), capB, _dev(H, f),
+                                 _dev(status, i32) if status is not None else None, radius2, ambiguity, max_distance,
+                                 arr(results, i32), _dev(count), arr(best, f), _stream()), entry)
     return (results, count) + ((best,) if want_distance else ())
 
 
-def sift_match_guided_host(As, axs, ays, nAs, Bs, bxs, bys, nBs, H, status=None, radius2=9.0, ambiguity=0.8,
-                           max_distance=float("inf"), capA=None, capB=None, want_distance=False):
-    """sift_match_guided_batch_dev on the host (nm_sift_match_guided_host_f32, the same functions): numpy in and out,
-    bit-identical results. nAs / nBs are host ints. Returns (results (n, capA) int32, count (n,)) and, with want_distance,
-    best distances (n, capA) float32."""
+def _guided_host(np_dtype, entry, As, axs, ays, nAs, Bs, bxs, bys, nBs, H, status, radius2, ambiguity, max_distance, capA,
+                 capB, want_distance):
+    """The host twin of both guided matchers: descriptors of `np_dtype`, the C entry `entry`."""
     import numpy as np
     n = _pair_count(As, axs, ays, nAs, Bs, bxs, bys, nBs)
-    As, Bs = (_pair_host_arrays(vs, np.float32, flat=False) for vs in (As, Bs))
+    As, Bs = (_pair_host_arrays(vs, np_dtype, flat=False) for vs in (As, Bs))
     axs, ays, bxs, bys = (_pair_host_arrays(vs, np.float32) for vs in (axs, ays, bxs, bys))
     capA = _pair_cap(capA, As + axs + ays)
     capB = _pair_cap(capB, Bs + bxs + bys)
@@ -1055,10 +1070,9 @@ def sift_match_guided_host(As, axs, ays, nAs, Bs, bxs, bys, nBs, H, status=None,
     nA, nB = _pair_host_sizes(nAs), _pair_host_sizes(nBs)
     result, count, best = _pair_host_match_out(n, capA, want_distance)
     arr, ptr = _pair_host_table, _pair_host_ptr
-    _check(lib().nm_sift_match_guided_host_f32(n, arr(As), arr(axs), arr(ays), arr(nA), capA, arr(Bs), arr(bxs), arr(bys),
-                                               arr(nB), capB, ptr(H), ptr(status), radius2, ambiguity, max_distance,
-                                               arr(list(result)), ptr(count), arr(list(best)) if want_distance else None),
-           "nm_sift_match_guided_host_f32")
+    _check(getattr(lib(), entry)(n, arr(As), arr(axs), arr(ays), arr(nA), capA, arr(Bs), arr(bxs), arr(bys), arr(nB), capB,
+                                 ptr(H), ptr(status), radius2, ambiguity, max_distance, arr(list(result)), ptr(count),
+                                 arr(list(best)) if want_distance else None), entry)
     return (result, count) + ((best,) if want_distance else ())
 
 
@@ -1456,6 +1470,32 @@ def sift_match_mutual_u8_host(As, nAs, Bs, nBs, matches, capA=None, capB=None, w
     nAs / nBs are host ints. Returns (results (n, capA) int32, count (n,)) and, with want_distance, forward distances
     (n, capA) float32."""
     return _mutual_host("uint8", "nm_sift_match_mutual_u8_host", As, nAs, Bs, nBs, matches, capA, capB, want_distance)
+
+
+MATCH_GUIDED_U8_MAX_BATCH = _PAIR_MAX_BATCH
+
+
+def sift_match_guided_u8_batch_dev(As, axs, ays, d_nAs, Bs, bxs, bys, d_nBs, H, status=None, radius2=9.0, ambiguity=0.8,
+                                   max_distance=float("inf"), capA=None, capB=None, results=None, want_distance=False):
+    """Homography-guided matching of n = len(As) <= MATCH_GUIDED_U8_MAX_BATCH pairs of uint8 descriptors
+    (nm_sift_match_guided_u8_batch_dev): three launches on the current stream, no host read, no workspace. As / Bs are uint8
+    device descriptors (rows, 128) (out_u8 of desc_finish_batch_dev, 16-byte aligned); every other argument and the return
+    value are those of sift_match_guided_batch_dev. Distances are exact integers: results, count and best distances equal
+    sift_match_guided_batch_dev's on float copies of the same bytes bit for bit."""
+    return _guided_dev(_torch().uint8, "nm_sift_match_guided_u8_batch_dev", As, axs, ays, d_nAs, Bs, bxs, bys, d_nBs, H,
+                       status, radius2, ambiguity, max_distance, capA, capB, results, want_distance)
+
+
+def sift_match_guided_u8_host(As, axs, ays, nAs, Bs, bxs, bys, nBs, H, status=None, radius2=9.0, ambiguity=0.8,
+                              max_distance=float("inf"), capA=None, capB=None, want_distance=False):
+    """sift_match_guided_u8_batch_dev on the host (nm_sift_match_guided_u8_host, the same functions): numpy uint8
+    descriptors in (no other dtype is converted), identical results out. nAs / nBs are host ints. Returns (results (n, capA)
+    int32, count (n,)) and, with want_distance, best distances (n, capA) float32."""
+    import numpy as np
+    if any(np.asarray(v).dtype != np.uint8 for vs in (As, Bs) for v in vs):
+        raise NmError("guided u8 matching: descriptors must be uint8")
+    return _guided_host("uint8", "nm_sift_match_guided_u8_host", As, axs, ays, nAs, Bs, bxs, bys, nBs, H, status, radius2,
+                        ambiguity, max_distance, capA, capB, want_distance)
 
 
 MOSAIC_MAX_BATCH = 64
