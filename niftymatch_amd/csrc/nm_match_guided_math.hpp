@@ -55,6 +55,18 @@ __host__ __device__ __forceinline__ float distance128(const float *a, const floa
     return acc;
 }
 
+/* fp32 rows as the guided kernel and its host twin see them (the u8 rows: nmg8::RowsU8). A lane keeps where its row lies,
+ * not the row: distance128 reads it again for every noted candidate */
+struct RowsF32 {
+    using Elem = float;
+    struct Own { const float *A; int i; };
+    __host__ __device__ __forceinline__ static void own(Own &o, const float *A, int i, bool) { o.A = A; o.i = i; }
+    __host__ __device__ __forceinline__ static float distance(const Own &o, const float *B, int j)
+    {
+        return distance128(o.A + (size_t)o.i * 128, B + (size_t)j * 128);
+    }
+};
+
 __host__ __device__ __forceinline__ void scan_init(Scan &s)
 {
     s.min1 = __builtin_inff(); s.min2 = 2139095040.0f; s.idx = -1; s.seen = 0;     /* (float)0x7f800000, not +inf (match.cu:91) */

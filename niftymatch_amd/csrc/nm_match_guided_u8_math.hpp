@@ -1,5 +1,5 @@
-// nm_match_guided_u8_math.hpp -- the distance of homography-guided matching over unsigned-char descriptors
-// (nm_sift_match_guided_u8_batch_dev and its host twin), for gfx950. No reference counterpart. Projection, gate and scan are
+// nm_match_guided_u8_math.hpp -- the distance and the row policy of homography-guided matching over unsigned-char descriptors
+// (nm_sift_match_guided_u8_batch_dev and its host twin, nm_match_guided.hip), for gfx950. No reference counterpart. Projection, gate and scan are
 // nm_match_guided_math.hpp as they are; what is new is d(i, j) = sum over q of (A[i][q] - B[j][q])^2 as an exact integer,
 // formed as |a|^2 + |b|^2 - 2 a.b from dot products of four bytes at a time: v_dot4_u32_u8 on the device, a plain loop on
 // the host. Every term is an integer <= 128 * 255^2 = 8 323 200 < 2^23, so the unsigned 32-bit sum is exact in any order,
@@ -64,5 +64,24 @@ __host__ __device__ __forceinline__ unsigned distance(const Row &a, unsigned aa,
     }
     return aa + (bb0 + bb1) - 2u * (ab0 + ab1);
 }
+
+/* u8 rows as the guided kernel and its host twin see them (the fp32 rows: nmg::RowsF32). A lane keeps its own row, read
+ * once (a row that is not valid: never, it stays zero), and |a|^2; (float)d is exact */
+struct RowsU8 {
+    using Elem = unsigned char;
+    struct Own { Row row; unsigned aa; };
+    __host__ __device__ __forceinline__ static void own(Own &o, const unsigned char *A, int i, bool valid)
+    {
+        o.row = {};
+        if (valid) load_row(o.row, A + (size_t)i * DIM);
+        o.aa = norm2(o.row);
+    }
+    __host__ __device__ __forceinline__ static float distance(const Own &o, const unsigned char *B, int j)
+    {
+        Row b;
+        load_row(b, B + (size_t)j * DIM);
+        return (float)nmg8::distance(o.row, o.aa, b);
+    }
+};
 
 }  // namespace nmg8

@@ -3,7 +3,9 @@ owns a whole chunk beside lanes with partly filled lists, every hit count around
 of a tile and the first of the next with a list pending, the nearest candidate in the rounded-up last chunk, every order the
 scan can meet, ragged row counts with invalid rows beside the burst, a wave in lockstep beside a wave of single hits).
 Everything is array_equal against the host twin: result, count and the bits of best, one pair per call in 300 x 1100 buffers,
-result, best_distance and count sentinel-filled before the call (the C entry, through ctypes). No tolerance, no excluded row. Which of these patterns can see which slip of the
+result, best_distance and count sentinel-filled before the call (the C entry, through ctypes). No tolerance, no excluded row.
+The two batch tests also run on the families' integer descriptors cast to bytes, through nm_sift_match_guided_u8_batch_dev
+against the u8 host twin: both entries are one kernel template and share the gate loop. Which of these patterns can see which slip of the
 schedule is measured on the CPU, in test_match_guided_hits_host.py, where the host twin is held to guided_ref.guided.
 """
 import ctypes as C
@@ -34,8 +36,21 @@ def _upload(cases, dev):
 SENTINEL = -7
 
 
-def _device(nm, cases, dev, run, up=None):
-    """One call of the C entry on the pairs `cases`. result, best_distance and count are all made here and start filled
+def _bytes(c):
+    """The case on byte descriptors: its rows are small integers in [0, 255] held in float32."""
+    q = dict(c)
+    for key in ("A", "B"):
+        assert c[key].min() >= 0 and c[key].max() <= 255 and np.array_equal(c[key], np.rint(c[key]))
+        q[key] = c[key].astype(np.uint8)
+    return q
+
+
+ELEMS = pytest.mark.parametrize("u8", [False, True], ids=["fp32", "u8"])
+
+
+def _device(nm, cases, dev, run, up=None, u8=False):
+    """One call of the C entry (u8: of the u8 entry, `cases` / `up` then hold byte descriptors) on the pairs `cases`.
+    result, best_distance and count are all made here and start filled
     with SENTINEL (no result is below -1, no distance below 0, no count below 0), and none may be left: a row or a count that
     the call does not write shows, whatever an earlier call left in the memory."""
     import torch
@@ -49,10 +64,12 @@ def _device(nm, cases, dev, run, up=None):
     count = torch.full((n,), SENTINEL, dtype=torch.int32, device=dev)
     arr = lambda ptrs: (C.c_void_p * n)(*ptrs)
     tab = lambda key: arr([u[key].data_ptr() for u in up])
-    rc = nm.lib().nm_sift_match_guided_batch_dev_f32(n, tab("A"), tab("ax"), tab("ay"), tab("nA"), R.CAP_A, tab("B"), tab("bx"),
-                                                     tab("by"), tab("nB"), R.CAP_B, Hd.data_ptr(), st.data_ptr(), r2, amb, maxd,
-                                                     arr([r.data_ptr() for r in res]), count.data_ptr(),
-                                                     arr([b.data_ptr() for b in best]), torch.cuda.current_stream().cuda_stream)
+    assert all(u["A"].dtype == u["B"].dtype == (torch.uint8 if u8 else torch.float32) for u in up)
+    entry = nm.lib().nm_sift_match_guided_u8_batch_dev if u8 else nm.lib().nm_sift_match_guided_batch_dev_f32
+    rc = entry(n, tab("A"), tab("ax"), tab("ay"), tab("nA"), R.CAP_A, tab("B"), tab("bx"),
+               tab("by"), tab("nB"), R.CAP_B, Hd.data_ptr(), st.data_ptr(), r2, amb, maxd,
+               arr([r.data_ptr() for r in res]), count.data_ptr(),
+               arr([b.data_ptr() for b in best]), torch.cuda.current_stream().cuda_stream)
     torch.cuda.synchronize()
     assert rc == 0
     out = dict(result=np.stack([r.cpu().numpy() for r in res]), count=count.cpu().numpy(),
@@ -62,15 +79,17 @@ def _device(nm, cases, dev, run, up=None):
     return out
 
 
-def _host(nm, cases, run):
-    """The host twin's answer, computed once per (cases, run)."""
-    key = (tuple(c["what"] for c in cases), run)
+def _host(nm, cases, run, u8=False):
+    """The host twin's answer (u8: the u8 host twin's, on byte descriptors), computed once per (cases, run, u8)."""
+    key = (tuple(c["what"] for c in cases), run, u8)
     if key not in _HOST:
         r2, amb, maxd = run
         k = lambda name: [c[name] for c in cases]
-        out = nm.sift_match_guided_host(k("A"), k("ax"), k("ay"), k("nA"), k("B"), k("bx"), k("by"), k("nB"), np.stack(k("H")),
-                                        status=np.array(k("status"), np.int32), radius2=r2, ambiguity=amb, max_distance=maxd,
-                                        capA=R.CAP_A, capB=R.CAP_B, want_distance=True)
+        assert all(c["A"].dtype == c["B"].dtype == (np.uint8 if u8 else np.float32) for c in cases)
+        twin = nm.sift_match_guided_u8_host if u8 else nm.sift_match_guided_host
+        out = twin(k("A"), k("ax"), k("ay"), k("nA"), k("B"), k("bx"), k("by"), k("nB"), np.stack(k("H")),
+                   status=np.array(k("status"), np.int32), radius2=r2, ambiguity=amb, max_distance=maxd,
+                   capA=R.CAP_A, capB=R.CAP_B, want_distance=True)
         _HOST[key] = dict(zip(OUT, out))
     return _HOST[key]
 
@@ -98,29 +117,34 @@ def test_device_equals_host_twin(nm, cuda, family):
     assert matched > 0, "nothing matched: the comparison covered nothing"
 
 
-def test_ragged_batch_of_mixed_families(nm, cuda):
-    """16 pairs in one call: the families mixed across the slots, one pair empty, one with status 0, one with nB = 1033."""
-    batch = R.ragged_batch()
+@ELEMS
+def test_ragged_batch_of_mixed_families(nm, cuda, u8):
+    """16 pairs in one call: the families mixed across the slots, one pair empty, one with status 0, one with nB = 1033.
+    u8: the same pairs on byte descriptors through the u8 entry, against the u8 host twin."""
+    batch = [_bytes(c) for c in R.ragged_batch()] if u8 else R.ragged_batch()
     up = _upload(batch, cuda)
     for run in ((R.R2, 0.8, np.inf), (R.R2, 1.5, np.inf)):
-        got = _device(nm, batch, cuda, run, up=up)
-        _assert_same(got, _host(nm, batch, run), ("ragged batch", run))
+        got = _device(nm, batch, cuda, run, up=up, u8=u8)
+        _assert_same(got, _host(nm, batch, run, u8), ("ragged batch", run, u8))
         assert got["count"][5] == got["count"][9] == 0 and (got["result"][[5, 9]] == -1).all() and np.isinf(got["best"][[5, 9]]).all()
     # tile_edge's nearest two are 100 and 120: matches above a ratio of 0.83 only, so the 1033 pair is counted at 1.5
     assert any(c["nB"] == 1033 and got["count"][p] >= 3 for p, c in enumerate(batch))
 
 
-def test_second_launch_and_last_slot_of_the_first(nm, cuda):
+@ELEMS
+def test_second_launch_and_last_slot_of_the_first(nm, cuda, u8):
     """33 pairs: chunk_burst in slot 32, the first slot of the second launch, tile_edge in slot 31; each equals its result
-    alone in a one-pair call."""
+    alone in a one-pair call. u8: the same pairs on byte descriptors through the u8 entry, against the u8 host twin."""
     burst, edge, filler = R.family_cases("chunk_burst")[0], R.family_cases("tile_edge")[3], R.family_cases("shared_point")[0]
+    if u8:
+        burst, edge, filler = _bytes(burst), _bytes(edge), _bytes(filler)
     run = (R.R2, 1.5, np.inf)                                   # (tile_edge's nearest two, 100 and 120, match above 0.83 only)
     pairs = [filler] * 31 + [edge, burst]
     up = _upload([filler, edge, burst], cuda)
-    got = _device(nm, pairs, cuda, run, up=[up[0]] * 31 + [up[1], up[2]])
-    _assert_same(got, _host(nm, pairs, run), "33 pairs")
+    got = _device(nm, pairs, cuda, run, up=[up[0]] * 31 + [up[1], up[2]], u8=u8)
+    _assert_same(got, _host(nm, pairs, run, u8), ("33 pairs", u8))
     for slot, c in ((32, burst), (31, edge), (0, filler), (30, filler)):
-        alone = _device(nm, [c], cuda, run)
+        alone = _device(nm, [c], cuda, run, u8=u8)
         for k in OUT:
             assert np.array_equal(_u32(got[k][slot]), _u32(alone[k][0])), (slot, c["what"], k)
     assert got["count"][32] > 0 and got["count"][31] > 0

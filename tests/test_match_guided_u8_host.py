@@ -268,7 +268,7 @@ def test_refusals(nm):
 def test_wrapper_checks_and_the_batch_limit(nm):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     hdr = int(re.search(r"#define NM_MATCH_GUIDED_U8_MAX_BATCH (\d+)", open(os.path.join(root, "include", "nm_abi.h")).read()).group(1))
-    src = open(os.path.join(root, "niftymatch_amd", "csrc", "nm_match_guided_u8.hip")).read()
+    src = open(os.path.join(root, "niftymatch_amd", "csrc", "nm_match_guided.hip")).read()
     slots = int(re.search(r"constexpr int SLOTS = (\d+);", src).group(1))
     assert "static_assert(NM_MATCH_GUIDED_U8_MAX_BATCH == 2 * SLOTS" in src
     assert hdr == 2 * slots == nm.MATCH_GUIDED_U8_MAX_BATCH == 64
