@@ -996,6 +996,77 @@ NM_API int nm_transform_blend_batch(unsigned char *canvas, int cw, int ch, float
                                     int mask_format, const void *const *wts, int wts_format,
                                     const nm_mosaic_record *records, void *stream);
 
+/* ---- Batched link verification (no reference counterpart): may the map of a frame pair be chained? RANSAC and the refit
+ * report "enough rows and H finite"; a map fitted to coincidental matches, a reflected or collapsing map, or a map between
+ * frames that do not overlap carries status 1 all the same, and nm_mosaic_plan_f32 would chain through it. This stage
+ * looks at H and at the two gray planes. n in [1, NM_LINK_VERIFY_MAX_BATCH] pairs in TWO launches on `stream` whatever n
+ * is (accumulate, finalize); no allocation, no synchronisation, no host read -- capturable into a HIP graph behind the
+ * refit and in front of the plan.
+ * grayA, grayB: HOST tables of n device pointers to fw x fh fp32 gray planes (those nm_frame_ingest_batch_f32 writes and
+ * nm_sift_detect_describe_batch reads; values in [0, 255]); pointers may repeat. mask: optional device plane fw x fh shared
+ * by all frames; a pixel is seen where mask > 0.5. H: device, n x 9, H_k maps frame-A pixels to frame-B pixels. status_in,
+ * inliers: device, n ints each, optional (inliers is e.g. the refit's count).
+ * Per pair k four gates; each failed gate sets a bit of reason[k], status_out[k] = (reason[k] == 0):
+ *   1 NM_LINK_UNUSABLE      unless (status_in == NULL || status_in[k] == 1) and all nine H_k are finite. Such a pair gets
+ *                           reason exactly 1 and zeros in stats; no other gate is looked at.
+ *   2 NM_LINK_FEW_INLIERS   when inliers != NULL and inliers[k] < min_inliers.
+ *   4 NM_LINK_BAD_GEOMETRY  the corners c0 .. c3 = (0,0), (fw,0), (fw,fh), (0,fh) go through project_den / project
+ *                           (csrc/nm_warp_math.hpp; fp32, fmaf explicit, IEEE division). All four denominators must be
+ *                           finite and > 0. From the fp32 projections p_c, in fp64: e_c = p_{c+1} - p_c (indices mod 4),
+ *                           turn_c = fma(e_c.x, e_{c+1}.y, -(e_c.y e_{c+1}.x)) must be > 0 for all four (convex,
+ *                           orientation kept; a NaN fails), S = 0.5 (((t_0 + t_1) + t_2) + t_3) with
+ *                           t_c = fma(p_c.x, p_{c+1}.y, -(p_{c+1}.x p_c.y)), r = S / ((double)fw (double)fh), and
+ *                           1 / (double)max_area_ratio <= r <= max_area_ratio must hold.
+ *   8 NM_LINK_LOW_OVERLAP, 16 NM_LINK_LOW_NCC   photometric, from seven exact integer sums over a lattice of A:
+ *     Lattice: pixels (x, y) = (s u + s/2, s v + s/2), u < fw / s, v < fh / s (integer divisions), s = stride.
+ *     A value v has the level q = (int)rintf(v * 16.0f) when 0 <= v <= 255 (a NaN has none).
+ *     A lattice pixel counts into L when the mask sees it and A's value there has a level qa.
+ *     It also counts into N when: den = project_den(H_k, x, y) is finite and > 0; with (xp, yp) = project(H_k, x, y) the
+ *     sampler's tex_setup accepts (xp + 0.5f, yp + 0.5f) on B -- the convention of nm_resample_perspective_u8x4: pixel
+ *     centres lie at integer coordinates of H's frame, the sampler takes them at + 0.5, so inside it
+ *     xb = (xp + 0.5f) - 0.5f, accepted when -1 <= xb < fw and -1 <= yb < fh, i = floor(xb), j = floor(yb),
+ *     a = floor((xb - i) 256 + 0.5) / 256, b alike; the four taps (i, j), (i+1, j), (i, j+1), (i+1, j+1) all lie inside B
+ *     (0 <= i, i + 1 < fw, 0 <= j, j + 1 < fh; a tap of weight 0 included); the mask sees all four; all four hold a level
+ *     q_t. The integer weights are w_t = 65536 {(1-a)(1-b), a(1-b), (1-a)b, ab} (they sum to 65536) and
+ *     qb = (w_0 q_0 + w_1 q_1 + w_2 q_2 + w_3 q_3 + 32768) >> 16.
+ *     Sums (unsigned 64-bit): L, N, and over the pixels of N: sum qa, sum qb, sum qa^2, sum qb^2, sum qa qb. Integers: they
+ *     depend on the pair's inputs alone, never on summation order, n, the pair's slot or scheduling.
+ *     Finalize (fp64, fma explicit, IEEE divide and sqrt): overlap = N / L (0 when L = 0); cov = fma(N, Sab, -(Sa Sb)),
+ *     va = fma(N, Saa, -(Sa Sa)), vb alike; ncc = cov / sqrt(va vb) when N >= 2, va > 0 and vb > 0, else 0;
+ *     gain = cov / va when N >= 1 and va > 0, else 0; bias = fma(-gain, Sa, Sb) / (16 N), mean_a = Sa / (16 N),
+ *     mean_b = Sb / (16 N) (all 0 when N = 0): B ~ gain A + bias in gray values.
+ *     Bit 8 when overlap < min_overlap, bit 16 when ncc < min_ncc.
+ * Outputs (device): status_out n (can go to nm_mosaic_plan_f32, the refit and the guided entries as it is), reason n,
+ * stats n x 8 doubles = (N, L, overlap, ncc, gain, bias, mean_a, mean_b); every pair that passes gate 1 gets all eight
+ * whatever the other gates say. workspace: device, nm_link_verify_workspace_bytes(n) bytes (0 for n out of range), any
+ * contents.
+ * Returns hipErrorInvalidValue, touching no device memory, for n not in [1, 64], fw or fh not in [1, 32767], stride not
+ * in [1, 64], (fw / stride)(fh / stride) > 2^28 (every sum then stays below 2^53, which fp64 holds exactly), a non-finite
+ * max_area_ratio, min_overlap or min_ncc, max_area_ratio < 1, min_inliers < 0, a NULL required pointer or a NULL among the
+ * first n table entries.
+ * nm_link_verify_host_f32: the same with every pointer in host memory, compiled from the same functions
+ * (csrc/nm_link_verify_math.hpp): host and device results are identical bit for bit.
+ * nm_link_verify_sums_host_f32: the seven sums themselves (host memory, n x 7, in the order above; zeros for a pair whose
+ * H is not finite), for tests and for clients that want their own statistics.                                        */
+#define NM_LINK_VERIFY_MAX_BATCH 64
+#define NM_LINK_UNUSABLE 1
+#define NM_LINK_FEW_INLIERS 2
+#define NM_LINK_BAD_GEOMETRY 4
+#define NM_LINK_LOW_OVERLAP 8
+#define NM_LINK_LOW_NCC 16
+NM_API size_t nm_link_verify_workspace_bytes(int n);
+NM_API int nm_link_verify_batch_dev_f32(int n, const float *const *grayA, const float *const *grayB, int fw, int fh,
+                                        const float *mask, const float *H, const int *status_in, const int *inliers,
+                                        int stride, int min_inliers, float max_area_ratio, float min_overlap,
+                                        float min_ncc, int *status_out, int *reason, double *stats, void *workspace,
+                                        void *stream);
+NM_API int nm_link_verify_host_f32(int n, const float *const *grayA, const float *const *grayB, int fw, int fh,
+                                   const float *mask, const float *H, const int *status_in, const int *inliers,
+                                   int stride, int min_inliers, float max_area_ratio, float min_overlap, float min_ncc,
+                                   int *status_out, int *reason, double *stats);
+NM_API int nm_link_verify_sums_host_f32(int n, const float *const *grayA, const float *const *grayB, int fw, int fh,
+                                        const float *mask, const float *H, int stride, unsigned long long *sums);
+
 /* ---- Batched frame ingest (no reference counterpart: the reference's client undistorts and converts each frame with
  * its own launches). nm_frame_ingest_batch_f32 turns n camera frames into the fp32 gray planes SIFT reads and,
  * optionally, their undistorted BGRA frames, in ONE launch.

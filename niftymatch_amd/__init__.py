@@ -111,6 +111,10 @@ _SIGNATURES = {
     "nm_ransac_batch_sample": (_I, [C.c_uint, _I, _I, _I, _I]),
     "nm_ransac_refit_batch_dev_f32": (_I, [_I, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _F, _I, _P, _P, _P, _P, _P, _P, _P]),
     "nm_ransac_refit_host_f32": (_I, [_I, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _F, _I, _P, _P, _P, _P, _P, _P]),
+    "nm_link_verify_workspace_bytes": (_SZ, [_I]),
+    "nm_link_verify_batch_dev_f32": (_I, [_I, _P, _P, _I, _I, _P, _P, _P, _P, _I, _I, _F, _F, _F, _P, _P, _P, _P, _P]),
+    "nm_link_verify_host_f32": (_I, [_I, _P, _P, _I, _I, _P, _P, _P, _P, _I, _I, _F, _F, _F, _P, _P, _P]),
+    "nm_link_verify_sums_host_f32": (_I, [_I, _P, _P, _I, _I, _P, _P, _I, _P]),
     "nm_sift_match_guided_batch_dev_f32": (_I, [_I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _P, _F, _F, _F, _P, _P, _P, _P]),
     "nm_sift_match_guided_host_f32": (_I, [_I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _P, _F, _F, _F, _P, _P, _P]),
     "nm_sift_match_mutual_workspace_bytes": (_SZ, [_I, _I]),
@@ -1002,6 +1006,94 @@ def ransac_refit_host(model, src_xs, src_ys, nAs, dst_xs, dst_ys, matches, H, st
                                           arr(matches), ptr(H), ptr(status), threshold, int(rounds), ptr(H_out), ptr(count),
                                           ptr(st), ptr(done), ptr(mask), ptr(rms)), "nm_ransac_refit_host_f32")
     return (H_out, count, st, done) + ((mask,) if want_mask else ()) + ((rms,) if want_rms else ())
+
+
+LINK_UNUSABLE, LINK_FEW_INLIERS, LINK_BAD_GEOMETRY, LINK_LOW_OVERLAP, LINK_LOW_NCC = 1, 2, 4, 8, 16
+LINK_STATS = ("N", "L", "overlap", "ncc", "gain", "bias", "mean_a", "mean_b")
+# The photometric thresholds' defaults: midway between the true links and the wrong maps of the synthetic mosaic views
+# under the unquantised float64 model ("Link verification"; tests/test_link_verify_host.py).
+LINK_MIN_NCC = 0.52            # true links 0.9989 .. 0.9994, wrong maps -0.019 .. 0.038
+LINK_MIN_OVERLAP = 0.60        # true links 0.817 .. 0.860, the true map shifted by half a frame 0.352 .. 0.385
+
+
+class LinkVerifyWorkspace(_PairWorkspace):
+    """Device scratch for nm_link_verify_batch_dev_f32: n pairs."""
+    _bytes_fn, _what, _shape_text = "nm_link_verify_workspace_bytes", "link verification workspace", "n=%d"
+
+    def __init__(self, n, device):
+        self._alloc(device, n=n)
+
+
+def _link_check(n, fw, fh, stride, min_inliers, max_area_ratio, min_overlap, min_ncc):
+    if not (1 <= fw <= 32767 and 1 <= fh <= 32767):
+        raise NmError("link verification: frame %r x %r outside [1, 32767]" % (fw, fh))
+    if int(stride) != stride or not 1 <= stride <= 64 or (fw // stride) * (fh // stride) > 1 << 28:
+        raise NmError("link verification: stride %r outside [1, 64] or a lattice beyond 2^28 pixels" % (stride,))
+    if int(min_inliers) != min_inliers or min_inliers < 0:
+        raise NmError("link verification: min_inliers %r must be an integer >= 0" % (min_inliers,))
+    if not all(math.isfinite(v) for v in (max_area_ratio, min_overlap, min_ncc)) or max_area_ratio < 1:
+        raise NmError("link verification: thresholds must be finite and max_area_ratio >= 1")
+
+
+def link_verify_batch_dev(grayAs, grayBs, H, status=None, inliers=None, mask=None, stride=4, min_inliers=16,
+                          max_area_ratio=4.0, min_overlap=LINK_MIN_OVERLAP, min_ncc=LINK_MIN_NCC, workspace=None):
+    """May the maps of n = len(grayAs) <= 64 frame pairs be chained (nm_link_verify_batch_dev_f32)? Two launches on the
+    current stream, no host read. grayAs[k], grayBs[k]: float32 device planes (fh, fw), all of one shape, e.g. those of
+    ingest_batch (tensors may repeat); H float32 device (n, 9) or (n, 3, 3) maps A pixels to B pixels, e.g. the refit's
+    H_out; status and inliers int32 device (n,) or None, e.g. the refit's status and count; mask float32 device (fh, fw)
+    or None. Returns (status_out[n], reason[n], stats[n, 8]): reason is a sum of LINK_* bits, stats float64 in the order of
+    LINK_STATS. status_out goes to mosaic_plan, ransac_refit_batch_dev and the guided matchers as it is."""
+    torch = _torch()
+    n = _pair_count(grayAs, grayBs)
+    if any(t.ndim != 2 or t.shape != grayAs[0].shape for t in list(grayAs) + list(grayBs) + ([mask] if mask is not None else [])):
+        raise NmError("link verification: planes of one (height, width) shape expected")
+    fh, fw = grayAs[0].shape
+    _link_check(n, fw, fh, stride, min_inliers, max_area_ratio, min_overlap, min_ncc)
+    _pair_model_shape(n, H.numel(), None if status is None else status.numel())
+    if inliers is not None and inliers.numel() != n:
+        raise NmError("link verification: inliers must hold n values")
+    device = _pair_device(list(grayAs) + list(grayBs) + [H, status, inliers, mask,
+                                                         workspace.buf if workspace is not None else None], [])
+    workspace = _pair_workspace(LinkVerifyWorkspace, workspace, device, n)
+    st, why = (torch.empty(n, dtype=torch.int32, device=device) for _ in range(2))
+    stats = torch.empty((n, 8), dtype=torch.float64, device=device)
+    opt = lambda t, dt: _dev(t, dt) if t is not None else None
+    _check(lib().nm_link_verify_batch_dev_f32(n, _pair_dev_table(grayAs, torch.float32), _pair_dev_table(grayBs, torch.float32),
+                                              fw, fh, opt(mask, torch.float32), _dev(H, torch.float32),
+                                              opt(status, torch.int32), opt(inliers, torch.int32), int(stride),
+                                              int(min_inliers), max_area_ratio, min_overlap, min_ncc, _dev(st), _dev(why),
+                                              _dev(stats), _dev(workspace.buf), _stream()), "nm_link_verify_batch_dev_f32")
+    return st, why, stats
+
+
+def link_verify_host(grayAs, grayBs, H, status=None, inliers=None, mask=None, stride=4, min_inliers=16, max_area_ratio=4.0,
+                     min_overlap=LINK_MIN_OVERLAP, min_ncc=LINK_MIN_NCC, want_sums=False):
+    """link_verify_batch_dev on the host (nm_link_verify_host_f32, the same functions): numpy in and out, bit-identical
+    results. With want_sums also the seven integer sums, uint64 (n, 7) (nm_link_verify_sums_host_f32)."""
+    import numpy as np
+    n = _pair_count(grayAs, grayBs)
+    grayAs, grayBs = (_pair_host_arrays(vs, np.float32, flat=False) for vs in (grayAs, grayBs))
+    mask = None if mask is None else np.ascontiguousarray(mask, dtype=np.float32)
+    if any(a.ndim != 2 or a.shape != grayAs[0].shape for a in grayAs + grayBs + ([mask] if mask is not None else [])):
+        raise NmError("link verification: planes of one (height, width) shape expected")
+    fh, fw = grayAs[0].shape
+    _link_check(n, fw, fh, stride, min_inliers, max_area_ratio, min_overlap, min_ncc)
+    H, status = _pair_host_model(n, H, status)
+    inliers = None if inliers is None else np.ascontiguousarray(inliers, dtype=np.int32).reshape(-1)
+    if inliers is not None and inliers.size != n:
+        raise NmError("link verification: inliers must hold n values")
+    st, why = np.zeros(n, np.int32), np.zeros(n, np.int32)
+    stats = np.zeros((n, 8), np.float64)
+    arr, ptr = _pair_host_table, _pair_host_ptr
+    _check(lib().nm_link_verify_host_f32(n, arr(grayAs), arr(grayBs), fw, fh, ptr(mask), ptr(H), ptr(status), ptr(inliers),
+                                         int(stride), int(min_inliers), max_area_ratio, min_overlap, min_ncc, ptr(st),
+                                         ptr(why), ptr(stats)), "nm_link_verify_host_f32")
+    if not want_sums:
+        return st, why, stats
+    sums = np.zeros((n, 7), np.uint64)
+    _check(lib().nm_link_verify_sums_host_f32(n, arr(grayAs), arr(grayBs), fw, fh, ptr(mask), ptr(H), int(stride), ptr(sums)),
+           "nm_link_verify_sums_host_f32")
+    return st, why, stats, sums
 
 
 def _guided_check(radius2, ambiguity, max_distance):

@@ -3,7 +3,8 @@
 // inverse and the per-pixel blend step of transform_blend. One copy, so that the batched blend equals n per-frame
 // transform_blend calls, and the ingest equals per-frame resamples, by construction. The build uses -ffp-contract=off
 // and correctly rounded fp32 division; every multiply-add here is an explicit fmaf.
-// project / invert3x3 / blend_combine are __host__ __device__: the mosaic plan's host twin runs the same sequence.
+// project / invert3x3 / blend_combine are __host__ __device__: the mosaic plan's host twin runs the same sequence; so is
+// tex_setup, for the host twin of the link verification (nm_link_verify_math.hpp).
 #pragma once
 #include "nm_common.hpp"
 #include "../../include/nm_abi.h"
@@ -24,7 +25,7 @@ __device__ __forceinline__ float texel(const Tex &t, int i, int j, int ch)
     return (float)((const unsigned char *)t.data)[4 * p + ch] / 255.0f;
 }
 
-__device__ __forceinline__ bool tex_setup(const Tex &t, float x, float y, int &i, int &j, float w[4])
+__host__ __device__ __forceinline__ bool tex_setup(const Tex &t, float x, float y, int &i, int &j, float w[4])
 {
     const float xb = x - 0.5f, yb = y - 0.5f;
     if (!(xb >= -1.0f && xb < (float)t.w && yb >= -1.0f && yb < (float)t.h)) return false;
