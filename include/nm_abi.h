@@ -1067,6 +1067,97 @@ NM_API int nm_link_verify_host_f32(int n, const float *const *grayA, const float
 NM_API int nm_link_verify_sums_host_f32(int n, const float *const *grayA, const float *const *grayB, int fw, int fh,
                                         const float *mask, const float *H, int stride, unsigned long long *sums);
 
+/* ---- Batched direct (photometric) refinement of link maps (no reference counterpart). The refit fits a map to keypoint
+ * coordinates; this stage moves it by a few inverse compositional Gauss-Newton steps on the level difference of the two
+ * gray planes over the verification's lattice, with a gain and a bias between the frames. It belongs between the refit and
+ * nm_link_verify_batch_dev_f32, whose conventions it keeps: n in [1, NM_LINK_REFINE_MAX_BATCH] pairs, TWO launches per
+ * iteration on `stream` whatever n is (accumulate, solve; 2 x iterations per call), no allocation, no synchronisation, no
+ * host read, no kernel that waits for another workgroup -- capturable into a HIP graph.
+ * grayA, grayB, mask, status_in: as for the verification. H_in: device, n x 9, H_k maps frame-A pixels to frame-B pixels.
+ * model: NM_LINK_REFINE_TRANSLATION (2 parameters), _AFFINE (6) or _HOMOGRAPHY (8). iterations in
+ * [1, NM_LINK_REFINE_MAX_ITERATIONS].
+ * A pair is usable when (status_in == NULL || status_in[k] == 1) and all nine H_in are finite. The iterate H is kept in
+ * fp64 (start: H_in as it is); each iteration walks the lattice under Hf = H rounded to fp32 (the first under H_in):
+ *   Lattice, mask rule, levels q and the sample qb of B under Hf: exactly those of the verification (above). A lattice pixel
+ *   counts into L as there. It counts into N when it counts into the verification's N and, in addition, its four neighbours
+ *   (x-1, y), (x+1, y), (x, y-1), (x, y+1) lie inside A, are seen by the mask and hold a level.
+ *   Per pixel of N, all fp64, every product and every sum rounded on its own (no fused multiply-add in the accumulation):
+ *     gx = 0.5 (q(x+1, y) - q(x-1, y)), gy = 0.5 (q(x, y+1) - q(x, y-1));  h = 0.5 max(fw, fh), cx = 0.5 (fw - 1),
+ *     cy = 0.5 (fh - 1);  X = (x - cx) / h, Y = (y - cy) / h;  gX = h gx, gY = h gy;  d = gX X + gY Y;
+ *     J = (gX X, gX Y, gX, gY X, gY Y, gY, -(X d), -(Y d), NM_LINK_REFINE_GAIN_SCALE qa, NM_LINK_REFINE_BIAS_SCALE);
+ *     r = qb - qa. The two scales (4 and 8192, powers of two) bring the photometric columns to the magnitude of the
+ *     geometric ones on textured frames (gX is about h x 16 x the gray gradient, qa at most 4080).
+ *   67 sums, s <- s + term: s[e(i, j)] of J_i J_j for i <= j, e = 10 i - i (i - 1) / 2 + (j - i) (the upper triangle of
+ *   J^T J by rows, 55 entries); s[55 + i] of J_i r; s[65] of r r; s[66] = L, one added per pixel of L. N is no sum of its
+ *   own: s[54] = BIAS_SCALE^2 N exactly.
+ *   SUMMATION ORDER (part of the result; it depends on fw, fh and stride alone, never on n, the pair's slot, the grid or
+ *   scheduling). Lattice column u, row v: tile (u / 64, v / 32), tiles numbered by rows, tiles_x = ceil(lw / 64) to a row.
+ *   Virtual workgroup g of 256 owns the tiles g, g + 256, .. in ascending order; in a tile, virtual wave w of 4 owns the
+ *   rows w, w + 4, .. in ascending order and lane l of 64 the column l. A lane adds its pixels in that order, each sum from
+ *   +0. The 64 lanes of a wave are combined by the butterfly of nmw::wave_reduce: for d = 32, 16, .., 1: v_l <- v_l +
+ *   v_(l + d) for l < d; v_0 is the wave's sum. A workgroup's row is ((((+0 + w_0) + w_1) + w_2) + w_3), the total
+ *   (((+0 + row_0) + row_1) + ..) over the rows g < min(tiles, 256).
+ *   Solve (fp64, fma explicit, IEEE divide and sqrt): rms = sqrt(s[65] / N) / 16 (0 when N = 0). N < min_pixels ends the
+ *   pair (FEW_PIXELS). Columns c_0 < c_1 < ..: the model's (translation 2, 5; affine 0 .. 5; homography 0 .. 7), then 8
+ *   and 9; A_ij = s[e(c_i, c_j)], b_i = s[55 + c_i]. Cholesky by columns j = 0, 1, ..: d = A_jj, then d <- fma(-L_jk,
+ *   L_jk, d) for k = 0 .. j-1; a d that is not positive and finite ends the pair (SINGULAR); L_jj = sqrt(d); for i > j:
+ *   t = A_ji, t <- fma(-L_ik, L_jk, t) for k = 0 .. j-1, L_ij = t / L_jj. Forward: t = b_i, t <- fma(-L_ik, y_k, t) for
+ *   k = 0 .. i-1, y_i = t / L_ii. Backward, i descending: t = y_i, t <- fma(-L_ki, x_k, t) for k = i+1 .., x_i = t / L_ii.
+ *   A non-finite x ends the pair (SINGULAR). p_c = x of column c (0 outside the model), alpha, beta = x of columns 8, 9;
+ *   gain = fma(GAIN_SCALE, alpha, 1), bias = BIAS_SCALE beta / 16: B ~ gain A + bias in gray values.
+ *   Step: W = [[1 + p0, p1, p2], [p3, 1 + p4, p5], [p6, p7, 1]], T = [[1/h, 0, -(cx/h)], [0, 1/h, -(cy/h)], [0, 0, 1]],
+ *   Ti = [[h, 0, cx], [0, h, cy], [0, 0, 1]], M = Ti (W T) with (P Q)[r][c] = fma(P[r][2], Q[2][c], fma(P[r][1], Q[1][c],
+ *   P[r][0] Q[0][c])). Its size is the largest displacement of the corners (0,0), (fw,0), (fw,fh), (0,fh) under M:
+ *   den = fma(M6, x, fma(M7, y, M8)), dx = fma(M0, x, fma(M1, y, M2)) / den - x, dy alike, sqrt(fma(dx, dx, dy dy));
+ *   +inf unless every den > 0 and every displacement is finite. Update: H' = H adj(M) (the same product; adj(M) =
+ *   det(M) M^-1, elements fma(t4, t8, -(t7 t5)) .. as csrc/nm_warp_math.hpp's invert3x3 without the division), then every
+ *   element divided by H'[8], the way the plan divides. A size > max_step (or NaN), or an H' that is not finite in fp32,
+ *   is NOT applied and ends the pair (STEP). Else H <- H', and a size < NM_LINK_REFINE_CONVERGED_STEP (2^-7 pixel, half
+ *   the sampler's weight step in each direction) ends the pair (CONVERGED). A pair still running after the last
+ *   iteration ends there (ITERATIONS). The launches of later iterations skip a pair that has ended: its workgroups leave
+ *   on a flag read from the workspace.
+ * Outputs (device), written when the pair ends: H_out n x 9 = H rounded to fp32 after the last applied step; a pair with
+ * no applied step keeps H_out = H_in bit for bit. status_out[k] = 1 exactly when at least one step was applied (an
+ * unusable pair: 0). H_out and status_out go to the verification, the plan, the refit and the guided entries as they are.
+ * stats n x NM_LINK_REFINE_STATS doubles = (N, L of the last walk; rms at H_in; rms at the last walk; gain, bias and the
+ * step's size in pixels from the last walk's solve, 0 where it solved nothing, the size of a refused step included;
+ * steps applied; the end reason NM_LINK_REFINE_END_*). An unusable pair has zeros and END_UNUSABLE.
+ * workspace: device, nm_link_refine_workspace_bytes(n) bytes (0 for n out of range; n times the bytes of one pair), 8-byte
+ * aligned, any contents.
+ * Returns hipErrorInvalidValue, touching no device memory, for n, fw, fh, stride or a lattice outside the verification's
+ * bounds, a model outside [0, 2], iterations outside [1, 8], min_pixels < 1, max_step not finite or <= 0, a NULL required
+ * pointer or a NULL among the first n table entries.
+ * nm_link_refine_host_f32: the same with every pointer in host memory, compiled from the same functions
+ * (csrc/nm_link_refine_math.hpp), walking the same summation order: host and device results are identical bit for bit.
+ * nm_link_refine_sums_host_f32: the 67 sums of one walk under H (host memory, n x 67 doubles in the order above; zeros
+ * for a pair whose H is not finite), for tests.                                                                        */
+#define NM_LINK_REFINE_MAX_BATCH 64
+#define NM_LINK_REFINE_MAX_ITERATIONS 8
+#define NM_LINK_REFINE_TRANSLATION 0
+#define NM_LINK_REFINE_AFFINE 1
+#define NM_LINK_REFINE_HOMOGRAPHY 2
+#define NM_LINK_REFINE_GAIN_SCALE 4.0
+#define NM_LINK_REFINE_BIAS_SCALE 8192.0
+#define NM_LINK_REFINE_CONVERGED_STEP 0.0078125
+#define NM_LINK_REFINE_STATS 9
+#define NM_LINK_REFINE_END_ITERATIONS 0
+#define NM_LINK_REFINE_END_CONVERGED 1
+#define NM_LINK_REFINE_END_UNUSABLE 2
+#define NM_LINK_REFINE_END_FEW_PIXELS 3
+#define NM_LINK_REFINE_END_SINGULAR 4
+#define NM_LINK_REFINE_END_STEP 5
+NM_API size_t nm_link_refine_workspace_bytes(int n);
+NM_API int nm_link_refine_batch_dev_f32(int n, const float *const *grayA, const float *const *grayB, int fw, int fh,
+                                        const float *mask, const float *H_in, const int *status_in, int model, int stride,
+                                        int iterations, int min_pixels, float max_step, float *H_out, int *status_out,
+                                        double *stats, void *workspace, void *stream);
+NM_API int nm_link_refine_host_f32(int n, const float *const *grayA, const float *const *grayB, int fw, int fh,
+                                   const float *mask, const float *H_in, const int *status_in, int model, int stride,
+                                   int iterations, int min_pixels, float max_step, float *H_out, int *status_out,
+                                   double *stats);
+NM_API int nm_link_refine_sums_host_f32(int n, const float *const *grayA, const float *const *grayB, int fw, int fh,
+                                        const float *mask, const float *H, int stride, double *sums);
+
 /* ---- Batched frame ingest (no reference counterpart: the reference's client undistorts and converts each frame with
  * its own launches). nm_frame_ingest_batch_f32 turns n camera frames into the fp32 gray planes SIFT reads and,
  * optionally, their undistorted BGRA frames, in ONE launch.

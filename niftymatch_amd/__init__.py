@@ -115,6 +115,10 @@ _SIGNATURES = {
     "nm_link_verify_batch_dev_f32": (_I, [_I, _P, _P, _I, _I, _P, _P, _P, _P, _I, _I, _F, _F, _F, _P, _P, _P, _P, _P]),
     "nm_link_verify_host_f32": (_I, [_I, _P, _P, _I, _I, _P, _P, _P, _P, _I, _I, _F, _F, _F, _P, _P, _P]),
     "nm_link_verify_sums_host_f32": (_I, [_I, _P, _P, _I, _I, _P, _P, _I, _P]),
+    "nm_link_refine_workspace_bytes": (_SZ, [_I]),
+    "nm_link_refine_batch_dev_f32": (_I, [_I, _P, _P, _I, _I, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P]),
+    "nm_link_refine_host_f32": (_I, [_I, _P, _P, _I, _I, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P]),
+    "nm_link_refine_sums_host_f32": (_I, [_I, _P, _P, _I, _I, _P, _P, _I, _P]),
     "nm_sift_match_guided_batch_dev_f32": (_I, [_I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _P, _F, _F, _F, _P, _P, _P, _P]),
     "nm_sift_match_guided_host_f32": (_I, [_I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _P, _F, _F, _F, _P, _P, _P]),
     "nm_sift_match_mutual_workspace_bytes": (_SZ, [_I, _I]),
@@ -1094,6 +1098,96 @@ def link_verify_host(grayAs, grayBs, H, status=None, inliers=None, mask=None, st
     _check(lib().nm_link_verify_sums_host_f32(n, arr(grayAs), arr(grayBs), fw, fh, ptr(mask), ptr(H), int(stride), ptr(sums)),
            "nm_link_verify_sums_host_f32")
     return st, why, stats, sums
+
+
+LINK_REFINE_MAX_BATCH, LINK_REFINE_MAX_ITERATIONS = 64, 8
+LINK_REFINE_TRANSLATION, LINK_REFINE_AFFINE, LINK_REFINE_HOMOGRAPHY = 0, 1, 2
+LINK_REFINE_GAIN_SCALE, LINK_REFINE_BIAS_SCALE, LINK_REFINE_CONVERGED_STEP = 4.0, 8192.0, 2.0 ** -7
+(LINK_REFINE_END_ITERATIONS, LINK_REFINE_END_CONVERGED, LINK_REFINE_END_UNUSABLE, LINK_REFINE_END_FEW_PIXELS,
+ LINK_REFINE_END_SINGULAR, LINK_REFINE_END_STEP) = range(6)
+LINK_REFINE_STATS = ("N", "L", "rms_first", "rms_last", "gain", "bias", "iterations", "last_step", "end")
+LINK_REFINE_SUMS = 67
+
+
+class LinkRefineWorkspace(_PairWorkspace):
+    """Device scratch for nm_link_refine_batch_dev_f32: n pairs."""
+    _bytes_fn, _what, _shape_text = "nm_link_refine_workspace_bytes", "link refinement workspace", "n=%d"
+
+    def __init__(self, n, device):
+        self._alloc(device, n=n)
+
+
+def _link_refine_check(fw, fh, model, stride, iterations, min_pixels, max_step):
+    if not (1 <= fw <= 32767 and 1 <= fh <= 32767):
+        raise NmError("link refinement: frame %r x %r outside [1, 32767]" % (fw, fh))
+    if int(stride) != stride or not 1 <= stride <= 64 or (fw // stride) * (fh // stride) > 1 << 28:
+        raise NmError("link refinement: stride %r outside [1, 64] or a lattice beyond 2^28 pixels" % (stride,))
+    if model not in (LINK_REFINE_TRANSLATION, LINK_REFINE_AFFINE, LINK_REFINE_HOMOGRAPHY):
+        raise NmError("link refinement: model %r is none of LINK_REFINE_TRANSLATION, _AFFINE, _HOMOGRAPHY" % (model,))
+    if int(iterations) != iterations or not 1 <= iterations <= LINK_REFINE_MAX_ITERATIONS:
+        raise NmError("link refinement: iterations %r outside [1, %d]" % (iterations, LINK_REFINE_MAX_ITERATIONS))
+    if int(min_pixels) != min_pixels or min_pixels < 1:
+        raise NmError("link refinement: min_pixels %r must be an integer >= 1" % (min_pixels,))
+    if not math.isfinite(max_step) or not max_step > 0:
+        raise NmError("link refinement: max_step %r must be finite and > 0" % (max_step,))
+
+
+def link_refine_batch_dev(grayAs, grayBs, H, status=None, mask=None, model=LINK_REFINE_HOMOGRAPHY, stride=4, iterations=4,
+                          min_pixels=64, max_step=16.0, workspace=None):
+    """Direct (photometric) refinement of the maps of n = len(grayAs) <= 64 frame pairs (nm_link_refine_batch_dev_f32): up to
+    `iterations` Gauss-Newton steps on the gray planes with gain and bias, two launches per iteration on the current
+    stream, no host read. The tensors are those of link_verify_batch_dev; H is e.g. the refit's H_out. Returns
+    (H_out[n, 9], status_out[n], stats[n, 9]): stats float64 in the order of LINK_REFINE_STATS, its last entry one of
+    LINK_REFINE_END_*. A pair without an applied step keeps its H and gets status 0. H_out and status_out go to
+    link_verify_batch_dev, mosaic_plan and the guided matchers as they are."""
+    torch = _torch()
+    n = _pair_count(grayAs, grayBs)
+    if any(t.ndim != 2 or t.shape != grayAs[0].shape for t in list(grayAs) + list(grayBs) + ([mask] if mask is not None else [])):
+        raise NmError("link refinement: planes of one (height, width) shape expected")
+    fh, fw = grayAs[0].shape
+    _link_refine_check(fw, fh, model, stride, iterations, min_pixels, max_step)
+    _pair_model_shape(n, H.numel(), None if status is None else status.numel())
+    device = _pair_device(list(grayAs) + list(grayBs) + [H, status, mask, workspace.buf if workspace is not None else None], [])
+    workspace = _pair_workspace(LinkRefineWorkspace, workspace, device, n)
+    H_out = torch.empty((n, 9), dtype=torch.float32, device=device)
+    st = torch.empty(n, dtype=torch.int32, device=device)
+    stats = torch.empty((n, len(LINK_REFINE_STATS)), dtype=torch.float64, device=device)
+    opt = lambda t, dt: _dev(t, dt) if t is not None else None
+    _check(lib().nm_link_refine_batch_dev_f32(n, _pair_dev_table(grayAs, torch.float32), _pair_dev_table(grayBs, torch.float32),
+                                              fw, fh, opt(mask, torch.float32), _dev(H, torch.float32),
+                                              opt(status, torch.int32), int(model), int(stride), int(iterations),
+                                              int(min_pixels), max_step, _dev(H_out), _dev(st), _dev(stats),
+                                              _dev(workspace.buf), _stream()), "nm_link_refine_batch_dev_f32")
+    return H_out, st, stats
+
+
+def link_refine_host(grayAs, grayBs, H, status=None, mask=None, model=LINK_REFINE_HOMOGRAPHY, stride=4, iterations=4,
+                     min_pixels=64, max_step=16.0, want_sums=False):
+    """link_refine_batch_dev on the host (nm_link_refine_host_f32, the same functions in the same summation order): numpy
+    in and out, bit-identical results. With want_sums also the 67 sums of one walk under H, float64 (n, 67)
+    (nm_link_refine_sums_host_f32)."""
+    import numpy as np
+    n = _pair_count(grayAs, grayBs)
+    grayAs, grayBs = (_pair_host_arrays(vs, np.float32, flat=False) for vs in (grayAs, grayBs))
+    mask = None if mask is None else np.ascontiguousarray(mask, dtype=np.float32)
+    if any(a.ndim != 2 or a.shape != grayAs[0].shape for a in grayAs + grayBs + ([mask] if mask is not None else [])):
+        raise NmError("link refinement: planes of one (height, width) shape expected")
+    fh, fw = grayAs[0].shape
+    _link_refine_check(fw, fh, model, stride, iterations, min_pixels, max_step)
+    H, status = _pair_host_model(n, H, status)
+    H_out = np.zeros((n, 9), np.float32)
+    st = np.zeros(n, np.int32)
+    stats = np.zeros((n, len(LINK_REFINE_STATS)), np.float64)
+    arr, ptr = _pair_host_table, _pair_host_ptr
+    _check(lib().nm_link_refine_host_f32(n, arr(grayAs), arr(grayBs), fw, fh, ptr(mask), ptr(H), ptr(status), int(model),
+                                         int(stride), int(iterations), int(min_pixels), max_step, ptr(H_out), ptr(st),
+                                         ptr(stats)), "nm_link_refine_host_f32")
+    if not want_sums:
+        return H_out, st, stats
+    sums = np.zeros((n, LINK_REFINE_SUMS), np.float64)
+    _check(lib().nm_link_refine_sums_host_f32(n, arr(grayAs), arr(grayBs), fw, fh, ptr(mask), ptr(H), int(stride), ptr(sums)),
+           "nm_link_refine_sums_host_f32")
+    return H_out, st, stats, sums
 
 
 def _guided_check(radius2, ambiguity, max_distance):
