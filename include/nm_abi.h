@@ -996,6 +996,18 @@ NM_API int nm_transform_blend_batch(unsigned char *canvas, int cw, int ch, float
                                     int mask_format, const void *const *wts, int wts_format,
                                     const nm_mosaic_record *records, void *stream);
 
+/* nm_mosaic_place_f32: the placement half of the plan on a GIVEN chain, e.g. chain_out of nm_mosaic_adjust_dev_f32. chain
+ * (device, n x 9): M_k, mosaic coordinates -> frame-k pixels; frame_status (device, n ints) may be NULL: every frame given.
+ * Frame k is placed exactly as the plan places a chained frame (footprint, box, record, above) when frame_status[k] == 1
+ * and all nine M_k are finite and no corner fails; otherwise its record is zero. extent (optional) as for the plan. On
+ * the plan's own chain output (frame_status NULL) records and extent equal the plan's bit for bit: the zero rows of a
+ * broken chain have no inverse and stay unplaced. One launch of one workgroup; the plan's refusals, and chain NULL.
+ * nm_mosaic_place_host_f32: the same with every pointer in host memory, the same functions, identical bit for bit.     */
+NM_API int nm_mosaic_place_f32(int n, const float *chain, const int *frame_status, int fw, int fh, int cw, int ch, int ox,
+                               int oy, nm_mosaic_record *records, float *extent, void *stream);
+NM_API int nm_mosaic_place_host_f32(int n, const float *chain, const int *frame_status, int fw, int fh, int cw, int ch,
+                                    int ox, int oy, nm_mosaic_record *records, float *extent);
+
 /* ---- Batched link verification (no reference counterpart): may the map of a frame pair be chained? RANSAC and the refit
  * report "enough rows and H finite"; a map fitted to coincidental matches, a reflected or collapsing map, or a map between
  * frames that do not overlap carries status 1 all the same, and nm_mosaic_plan_f32 would chain through it. This stage
@@ -1157,6 +1169,116 @@ NM_API int nm_link_refine_host_f32(int n, const float *const *grayA, const float
                                    double *stats);
 NM_API int nm_link_refine_sums_host_f32(int n, const float *const *grayA, const float *const *grayB, int fw, int fh,
                                         const float *mask, const float *H, int stride, double *sums);
+
+/* ---- Global adjustment of a mosaic's frame maps over all links, loop closures included (no reference counterpart). The
+ * plan multiplies the sequential maps, so the links' errors add up along the chain and a link between non-consecutive
+ * frames cannot be used. This stage is a joint least-squares adjustment (Gauss-Newton with Levenberg damping) of the maps
+ * G_k (frame-k pixels -> mosaic coordinates, the inverse of the plan's chain row M_k) over the matched points of all
+ * usable links, one anchor frame held fixed. It minimises
+ *     sum over usable links l = (a, b), sum over contributing rows i:  || pi(G_a p_i) - pi(G_b q_i) ||^2.
+ * (iterations + 1) x (ceil(L / 64) + 1) launches on `stream` (per round one accumulate launch per group of up to 64 links
+ * and one assemble-and-solve launch of one workgroup), no allocation, no synchronisation, no host read, no kernel that
+ * waits for another workgroup -- capturable into a HIP graph. A round boundary is a launch boundary.
+ * n frames in [2, 64], L links in [1, NM_MOSAIC_ADJUST_MAX_LINKS]. link_a, link_b: HOST int arrays of L, indices in
+ * [0, n), a != b, any order, repeats allowed, either direction. Per link the six point tables of
+ * nm_ransac_refit_batch_dev_f32 (HOST arrays of L device pointers; src is frame a, dst frame b) with its valid rows:
+ * nA = clip(*d_nA[l], 0, capA), row i < nA is valid when j = matches[l][i] >= 0 and src_x[l][i] >= 0. mask (device,
+ * L x capA bytes, the refit's mask; optional): a valid row contributes when mask[l capA + i] != 0; NULL: every valid row.
+ * link_status (device, L ints; optional), e.g. the verification's status_out. chain_in (device, n x 9 fp32): the plan's
+ * chain. anchor: host int in [0, n). fw, fh in [1, 32767]; iterations in [1, NM_MOSAIC_ADJUST_MAX_ITERATIONS];
+ * min_rows >= 4; damping >= 0 and max_step > 0 (pixels), both finite.
+ * Normalisation: h = max(fw, fh) / 2, T = [[1/h, 0, -(cx/h)], [0, 1/h, -(cy/h)], [0, 0, 1]] with cx = fw / 2, cy = fh / 2,
+ * Ti = [[h, 0, cx], [0, h, cy], [0, 0, 1]], applied to pixels and mosaic coordinates alike. 3 x 3 products are
+ * (P Q)[r][c] = fma(P[r][2], Q[2][c], fma(P[r][1], Q[1][c], P[r][0] Q[0][c])); inv(m) = adj(m) / det(m) element by
+ * element, then every element over element [8], with adj as in the link refinement and det = fma(m0, adj0, fma(m1,
+ * adj3, m2 adj6)). All fp64 from the fp32 inputs.
+ * Participation: G_k = inv(M_k), Gh_k = T (G_k Ti) with every element over its [8]. Frame k participates when its nine
+ * chain values, G_k and Gh_k are all finite (the plan's zero rows after a broken link do not). Link l is usable when
+ * (link_status == NULL || link_status[l] == 1), both frames participate, and at least min_rows rows contribute at the
+ * first iterate; the set of usable links is fixed there. Unknowns: elements 0 .. 7 of Gh_k of every participating frame
+ * but the anchor, in ascending frame order. A non-participating anchor ends the call at once (UNUSABLE).
+ * Per contributing row, all fp64, every product and every sum rounded on its own (no fused multiply-add), IEEE division:
+ *   px = (src_x - cx) / h, py = (src_y - cy) / h, q alike from dst; da = (Ga6 px + Ga7 py) + Ga8, db alike with Gb, q; a
+ *   row whose da or db is not finite and > 0 does not contribute. ux = ((Ga0 px + Ga1 py) + Ga2) / da, uy alike from
+ *   Ga3..5, v alike from Gb and q; r = u - v. Columns 0 .. 7 are frame a's, 8 .. 15 frame b's:
+ *     Jx = (px/da, py/da, 1/da, 0, 0, 0, (-(ux px))/da, (-(ux py))/da,  then the negatives of the same with q, v, db)
+ *     Jy = (0, 0, 0, px/da, py/da, 1/da, (-(uy px))/da, (-(uy py))/da,  then the negatives of the same with q, v, db)
+ *   NM_MOSAIC_ADJUST_SUMS = 153 sums, s <- s + t: s[e(i, j)], e = 16 i - i (i - 1) / 2 + (j - i) for i <= j (136): t =
+ *   Jx_i Jx_j + Jy_i Jy_j, where a product with a structurally zero factor (Jx of columns 3..5 and 11..13, Jy of 0..2 and
+ *   8..10) is left out together with its addition, and an entry with no product left is not touched (+0); s[136 + i]:
+ *   t = Jx_i rx + Jy_i ry under the same rule; s[152]: t = rx rx + ry ry. The row count is an integer.
+ *   SUMMATION ORDER (part of the result; a link's sums depend on the link's inputs and the current maps of its two frames
+ *   alone, never on L, n, the link's slot in its launch, or scheduling; no atomics): the refit's. Virtual lane t of 512
+ *   adds the rows t, t + 512, .. ascending, each sum from +0. Each group of 64 lanes is combined by the butterfly of
+ *   nmw::wave_reduce (for d = 32, 16, .., 1: v_l <- v_l + v_(l + d) for l < d); the eight group totals are added
+ *   ascending, ((g0 + g1) + g2) + .. .
+ * A round at iterate t = 0 .. iterations accumulates every usable link and then:
+ *   cost_t = sum of s[152] over the usable links ascending from +0; rows_t the sum of their counts. Link rms = h
+ *   sqrt(s[152] / count). For t > 0, a cost_t that is not <= cost_(t-1), or rows_t != rows_(t-1), restores the iterate
+ *   t - 1 and ends the call (COST_ROSE; the step count is taken back by one). Else, if the last applied step was below
+ *   NM_MOSAIC_ADJUST_CONVERGED_STEP the call ends (CONVERGED), and at t = iterations it ends (ITERATIONS): the last
+ *   accumulation only measures the cost. Hence the final cost never exceeds the initial one.
+ *   Assembly: A (dimension N = 8 x unknown frames <= 504) and g; every entry is the sum of the usable links' contributions
+ *   (J^T J entries by symmetry, s[136 + i] into g) added in ascending link order from +0; rows and columns of the anchor
+ *   are left out. Then A_ii <- A_ii (1 + damping), and a diagonal entry that is exactly 0 becomes 1 (a frame without a
+ *   usable link stays where it is).
+ *   Cholesky with explicit fma: column j = 0, 1, ..: d = A_jj, d <- fma(-L_jk, L_jk, d) for k = 0 .. j-1 ascending; a d that
+ *   is not finite and > 0 ends the call (SINGULAR, no step); L_jj = sqrt(d); for i > j: v = A_ij, v <- fma(-L_ik, L_jk, v)
+ *   for k ascending, L_ij = v / L_jj. Forward: v = g_i, v <- fma(-L_ik, y_k, v) for k = 0 .. i-1, y_i = v / L_ii.
+ *   Backward, i descending: v = y_i, v <- fma(-L_ki, x_k, v) for k = i+1 .. N-1 ascending, x_i = v / L_ii. A non-finite x
+ *   ends the call (SINGULAR). A rank-deficient system (e.g. with damping = 0 a component of frames that no usable link
+ *   ties to the anchor) has a pivot that is zero in exact arithmetic; rounded, it comes out non-positive (SINGULAR) or
+ *   tiny and positive, which gives a huge finite step and, with it above max_step, STEP. Which of the two is decided by
+ *   rounding; in either case no step is applied and no output is NaN.
+ *   Step: Gh'_k[q] = Gh_k[q] - x[8 slot_k + q], q < 8. Its size is the largest over the unknown frames and the corners (0,0),
+ *   (fw,0), (fw,fh), (0,fh), normalised to (X, Y), of h sqrt(fma(dx, dx, dy dy)) with dx = fma(G'0, X, fma(G'1, Y, G'2)) /
+ *   d' - (the same with G) / d, d = fma(G6, X, fma(G7, Y, G8)); +inf unless every d and d' is > 0, every distance finite
+ *   and the frame's new chain row (below) finite in fp32. A size > max_step (or NaN) is NOT applied and ends the call
+ *   (STEP). Else the iterate t is kept as the previous one and Gh <- Gh'.
+ * Outputs (device), written when the call ends: chain_out n x 9 fp32: inv(Ti (Gh_k T)) rounded, for every participating
+ * frame but the anchor when at least one step stays applied; the anchor's row, the rows of non-participating frames, and
+ * all rows when no step stays applied, are chain_in bit for bit. frame_status n ints: 1 = the frame participates.
+ * link_rms L x 2 doubles: the link's rms in pixels at the first and at the final iterate, 0 for a link that is not usable.
+ * stats NM_MOSAIC_ADJUST_STATS doubles: first cost, final cost (normalised units squared), contributing rows, usable
+ * links, unknown frames, steps applied, the last step's size in pixels (a refused one included), the end reason
+ * NM_MOSAIC_ADJUST_END_* (numbered as NM_LINK_REFINE_END_* where they coincide).
+ * workspace: device, nm_mosaic_adjust_workspace_bytes(n, L) bytes (0 out of range), 8-byte aligned, any contents: the
+ * links' sum rows, A, the current and the previous iterate, the state.
+ * Returns hipErrorInvalidValue, touching no device memory, for any range above, a NULL required pointer or a NULL among
+ * the first L table entries.
+ * nm_mosaic_adjust_host_f32: the same with every pointer in host memory, compiled from the same functions
+ * (csrc/nm_mosaic_adjust_math.hpp) over the same virtual lanes and chains: identical bit for bit.
+ * nm_mosaic_adjust_sums_host_f32: one link's 153 sums and row count under the normalised maps Ga, Gb (9 doubles each,
+ * host memory; mask: the link's capA bytes or NULL), for tests.                                                        */
+#define NM_MOSAIC_ADJUST_MAX_LINKS 256
+#define NM_MOSAIC_ADJUST_MAX_ITERATIONS 16
+#define NM_MOSAIC_ADJUST_SUMS 153
+#define NM_MOSAIC_ADJUST_STATS 8
+#define NM_MOSAIC_ADJUST_CONVERGED_STEP 0.0078125
+#define NM_MOSAIC_ADJUST_END_ITERATIONS 0
+#define NM_MOSAIC_ADJUST_END_CONVERGED 1
+#define NM_MOSAIC_ADJUST_END_UNUSABLE 2
+#define NM_MOSAIC_ADJUST_END_NO_LINK 3
+#define NM_MOSAIC_ADJUST_END_SINGULAR 4
+#define NM_MOSAIC_ADJUST_END_STEP 5
+#define NM_MOSAIC_ADJUST_END_COST_ROSE 6
+NM_API size_t nm_mosaic_adjust_workspace_bytes(int n, int L);
+NM_API int nm_mosaic_adjust_dev_f32(int n, int L, const int *link_a, const int *link_b, const float *const *src_x,
+                                    const float *const *src_y, const int *const *d_nA, int capA,
+                                    const float *const *dst_x, const float *const *dst_y, const int *const *matches,
+                                    const unsigned char *mask, const int *link_status, const float *chain_in, int anchor,
+                                    int fw, int fh, int iterations, int min_rows, double damping, double max_step,
+                                    float *chain_out, int *frame_status, double *link_rms, double *stats, void *workspace,
+                                    void *stream);
+NM_API int nm_mosaic_adjust_host_f32(int n, int L, const int *link_a, const int *link_b, const float *const *src_x,
+                                     const float *const *src_y, const int *const *nA, int capA, const float *const *dst_x,
+                                     const float *const *dst_y, const int *const *matches, const unsigned char *mask,
+                                     const int *link_status, const float *chain_in, int anchor, int fw, int fh,
+                                     int iterations, int min_rows, double damping, double max_step, float *chain_out,
+                                     int *frame_status, double *link_rms, double *stats);
+NM_API int nm_mosaic_adjust_sums_host_f32(const float *src_x, const float *src_y, int nA, int capA, const float *dst_x,
+                                          const float *dst_y, const int *matches, const unsigned char *mask, int fw, int fh,
+                                          const double *Ga, const double *Gb, double *sums, int *count);
 
 /* ---- Batched frame ingest (no reference counterpart: the reference's client undistorts and converts each frame with
  * its own launches). nm_frame_ingest_batch_f32 turns n camera frames into the fp32 gray planes SIFT reads and,

@@ -143,6 +143,14 @@ _SIGNATURES = {
     "nm_mosaic_plan_f32": (_I, [_I, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "nm_mosaic_plan_host_f32": (_I, [_I, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "nm_transform_blend_batch": (_I, [_P, _I, _I, _P, _I, _P, _I, _I, _P, _I, _P, _I, _P, _P]),
+    "nm_mosaic_place_f32": (_I, [_I, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "nm_mosaic_place_host_f32": (_I, [_I, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "nm_mosaic_adjust_workspace_bytes": (_SZ, [_I, _I]),
+    "nm_mosaic_adjust_dev_f32": (_I, [_I, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, C.c_double,
+                                      C.c_double, _P, _P, _P, _P, _P, _P]),
+    "nm_mosaic_adjust_host_f32": (_I, [_I, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, C.c_double,
+                                       C.c_double, _P, _P, _P, _P]),
+    "nm_mosaic_adjust_sums_host_f32": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
     "nm_frame_ingest_batch_f32": (_I, [_I, _P, _I, _I, _P, _P, _I, _I, _P, _P, _P]),
     "nm_sift_arena_create": (_I, [_I, _I, _I, _P]),
     "nm_sift_arena_destroy": (None, [_P]),
@@ -1788,6 +1796,168 @@ def transform_blend_batch(canvas, canvas_wts, frames, masks, wts, records):
                                           arr([_dev(f, torch.uint8) for f in frames]), fw, fh,
                                           arr([_dev(t) for t in masks]), mfmt, arr([_dev(t) for t in wts]), wfmt,
                                           _dev(records, torch.int32), _stream()), "nm_transform_blend_batch")
+
+
+def mosaic_place(chain, fw, fh, cw, ch, ox, oy, frame_status=None):
+    """Placement records of the n = chain.shape[0] frames of a GIVEN chain (nm_mosaic_place_f32), e.g. mosaic_adjust's
+    chain_out: the placement half of mosaic_plan, one launch, no host read. chain float32 device (n, 9) or (n, 3, 3);
+    frame_status int32 device (n,) or None. Returns (records int32 (n, 16), extent float32 (4,)) as mosaic_plan does; on
+    mosaic_plan's own chain they equal its records and extent bit for bit."""
+    torch = _torch()
+    n = chain.shape[0]
+    _mosaic_check_geometry(n, fw, fh, cw, ch, ox, oy)
+    if chain.numel() != 9 * n or (frame_status is not None and frame_status.numel() != n):
+        raise NmError("mosaic_place: chain must hold n x 9 floats and frame_status n values")
+    device = _on_current_device([chain] + ([frame_status] if frame_status is not None else []), "mosaic_place")
+    records = torch.empty((n, 16), dtype=torch.int32, device=device)
+    extent = torch.empty(4, dtype=torch.float32, device=device)
+    _check(lib().nm_mosaic_place_f32(n, _dev(chain, torch.float32),
+                                     _dev(frame_status, torch.int32) if frame_status is not None else None, fw, fh, cw, ch,
+                                     ox, oy, _dev(records), _dev(extent), _stream()), "nm_mosaic_place_f32")
+    return records, extent
+
+
+def mosaic_place_host(chain, fw, fh, cw, ch, ox, oy, frame_status=None):
+    """mosaic_place on the host (nm_mosaic_place_host_f32, the same functions): numpy in and out, bit-identical results."""
+    import numpy as np
+    chain = np.ascontiguousarray(chain, dtype=np.float32).reshape(-1, 9)
+    n = chain.shape[0]
+    _mosaic_check_geometry(n, fw, fh, cw, ch, ox, oy)
+    if frame_status is not None:
+        frame_status = np.ascontiguousarray(frame_status, dtype=np.int32).reshape(-1)
+        if frame_status.size != n:
+            raise NmError("mosaic_place_host: frame_status must hold n values")
+    records = np.zeros((n, 16), np.int32)
+    extent = np.zeros(4, np.float32)
+    _check(lib().nm_mosaic_place_host_f32(n, chain.ctypes.data, _pair_host_ptr(frame_status), fw, fh, cw, ch, ox, oy,
+                                          records.ctypes.data, extent.ctypes.data), "nm_mosaic_place_host_f32")
+    return records, extent
+
+
+MOSAIC_ADJUST_MAX_LINKS, MOSAIC_ADJUST_MAX_ITERATIONS, MOSAIC_ADJUST_SUMS = 256, 16, 153
+MOSAIC_ADJUST_CONVERGED_STEP = 2.0 ** -7
+MOSAIC_ADJUST_STATS = ("cost_first", "cost_last", "rows", "links", "unknown_frames", "steps", "last_step", "end")
+(MOSAIC_ADJUST_END_ITERATIONS, MOSAIC_ADJUST_END_CONVERGED, MOSAIC_ADJUST_END_UNUSABLE, MOSAIC_ADJUST_END_NO_LINK,
+ MOSAIC_ADJUST_END_SINGULAR, MOSAIC_ADJUST_END_STEP, MOSAIC_ADJUST_END_COST_ROSE) = range(7)
+
+
+class MosaicAdjustWorkspace(_PairWorkspace):
+    """Device scratch for nm_mosaic_adjust_dev_f32: n frames, L links."""
+    _bytes_fn, _what, _shape_text = "nm_mosaic_adjust_workspace_bytes", "mosaic adjustment workspace", "n=%d L=%d"
+
+    def __init__(self, n, L, device):
+        self._alloc(device, n=n, L=L)
+
+
+def _mosaic_adjust_check(n, lists, link_a, link_b, anchor, fw, fh, iterations, min_rows, damping, max_step):
+    L = len(link_a)
+    if not 2 <= n <= MOSAIC_MAX_BATCH or not 1 <= L <= MOSAIC_ADJUST_MAX_LINKS or len(link_b) != L or \
+            any(len(v) != L for v in lists):
+        raise NmError("mosaic adjustment: n in [2, %d] frames and lists of one length in [1, %d] expected"
+                      % (MOSAIC_MAX_BATCH, MOSAIC_ADJUST_MAX_LINKS))
+    if any(not (0 <= int(a) < n and 0 <= int(b) < n and int(a) != int(b)) for a, b in zip(link_a, link_b)):
+        raise NmError("mosaic adjustment: a link joins two different frames in [0, n)")
+    if not 0 <= int(anchor) < n:
+        raise NmError("mosaic adjustment: anchor %r outside [0, n)" % (anchor,))
+    if not (1 <= fw <= _MOSAIC_SIZE_LIMIT and 1 <= fh <= _MOSAIC_SIZE_LIMIT):
+        raise NmError("mosaic adjustment: frame %r x %r outside [1, %d]" % (fw, fh, _MOSAIC_SIZE_LIMIT))
+    if int(iterations) != iterations or not 1 <= iterations <= MOSAIC_ADJUST_MAX_ITERATIONS:
+        raise NmError("mosaic adjustment: iterations %r outside [1, %d]" % (iterations, MOSAIC_ADJUST_MAX_ITERATIONS))
+    if int(min_rows) != min_rows or min_rows < 4:
+        raise NmError("mosaic adjustment: min_rows %r must be an integer >= 4" % (min_rows,))
+    if not (math.isfinite(damping) and damping >= 0 and math.isfinite(max_step) and max_step > 0):
+        raise NmError("mosaic adjustment: damping must be finite and >= 0, max_step finite and > 0")
+    return L, (C.c_int * L)(*[int(a) for a in link_a]), (C.c_int * L)(*[int(b) for b in link_b])
+
+
+def mosaic_adjust(link_a, link_b, src_xs, src_ys, d_nAs, dst_xs, dst_ys, matches, chain, fw, fh, anchor=0, mask=None,
+                  link_status=None, iterations=5, min_rows=8, damping=1e-6, max_step=64.0, capA=None, workspace=None):
+    """Joint least-squares adjustment of the n = chain.shape[0] <= 64 frame maps of a mosaic over L = len(link_a) <= 256
+    links, loop closures included (nm_mosaic_adjust_dev_f32): (iterations + 1) x (ceil(L / 64) + 1) launches on the current
+    stream, no host read. link_a, link_b: host ints, link l matches frame link_a[l] (src) to frame link_b[l] (dst); the
+    per-link tensors are those of ransac_refit_batch_dev; chain float32 device (n, 9), e.g. mosaic_plan's; mask uint8 device
+    (L, capA) or None, e.g. the refit's; link_status int32 device (L,) or None, e.g. link_verify_batch_dev's. Returns
+    (chain_out[n, 9], frame_status[n], link_rms[L, 2], stats[8]): stats float64 in the order of MOSAIC_ADJUST_STATS, its last
+    entry one of MOSAIC_ADJUST_END_*. chain_out and frame_status go to mosaic_place as they are."""
+    torch = _torch()
+    n = chain.shape[0]
+    lists = (src_xs, src_ys, d_nAs, dst_xs, dst_ys, matches)
+    L, la, lb = _mosaic_adjust_check(n, lists, link_a, link_b, anchor, fw, fh, iterations, min_rows, damping, max_step)
+    capA = _pair_cap(capA, list(src_xs) + list(src_ys) + list(matches))
+    if chain.numel() != 9 * n or (link_status is not None and link_status.numel() != L) or \
+            (mask is not None and tuple(mask.shape) != (L, capA)):
+        raise NmError("mosaic adjustment: chain n x 9, link_status L values and mask (L, capA) expected")
+    device = _pair_device([t for ts in lists for t in ts] + [chain, mask, link_status,
+                                                              workspace.buf if workspace is not None else None], d_nAs)
+    workspace = _pair_workspace(MosaicAdjustWorkspace, workspace, device, n, L)
+    chain_out = torch.empty((n, 9), dtype=torch.float32, device=device)
+    fstat = torch.empty(n, dtype=torch.int32, device=device)
+    rms = torch.empty((L, 2), dtype=torch.float64, device=device)
+    stats = torch.empty(len(MOSAIC_ADJUST_STATS), dtype=torch.float64, device=device)
+    tables = _point_tables_dev(*lists)
+    opt = lambda t, dt: _dev(t, dt) if t is not None else None
+    _check(lib().nm_mosaic_adjust_dev_f32(n, L, la, lb, *tables[:3], capA, *tables[3:], opt(mask, torch.uint8),
+                                          opt(link_status, torch.int32), _dev(chain, torch.float32), int(anchor), fw, fh,
+                                          int(iterations), int(min_rows), damping, max_step, _dev(chain_out), _dev(fstat),
+                                          _dev(rms), _dev(stats), _dev(workspace.buf), _stream()), "nm_mosaic_adjust_dev_f32")
+    return chain_out, fstat, rms, stats
+
+
+def _mosaic_adjust_host_rows(src_xs, src_ys, dst_xs, dst_ys, matches, capA):
+    import numpy as np
+    src_xs, src_ys, dst_xs, dst_ys = (_pair_host_arrays(vs, np.float32) for vs in (src_xs, src_ys, dst_xs, dst_ys))
+    matches = _pair_host_arrays(matches, np.int32)
+    capA = _pair_cap(capA, src_xs + src_ys + matches)
+    for m, x, y in zip(matches, dst_xs, dst_ys):
+        if m.size and int(m.max()) >= min(x.size, y.size):
+            raise NmError("a match points beyond the destination coordinates")
+    return src_xs, src_ys, dst_xs, dst_ys, matches, capA
+
+
+def mosaic_adjust_host(link_a, link_b, src_xs, src_ys, nAs, dst_xs, dst_ys, matches, chain, fw, fh, anchor=0, mask=None,
+                       link_status=None, iterations=5, min_rows=8, damping=1e-6, max_step=64.0, capA=None):
+    """mosaic_adjust on the host (nm_mosaic_adjust_host_f32, the same functions in the same summation order): numpy in and
+    out, bit-identical results. nAs are host ints."""
+    import numpy as np
+    chain = np.ascontiguousarray(chain, dtype=np.float32).reshape(-1, 9)
+    n = chain.shape[0]
+    lists = (src_xs, src_ys, nAs, dst_xs, dst_ys, matches)
+    L, la, lb = _mosaic_adjust_check(n, lists, link_a, link_b, anchor, fw, fh, iterations, min_rows, damping, max_step)
+    src_xs, src_ys, dst_xs, dst_ys, matches, capA = _mosaic_adjust_host_rows(src_xs, src_ys, dst_xs, dst_ys, matches, capA)
+    mask = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)
+    link_status = None if link_status is None else np.ascontiguousarray(link_status, dtype=np.int32).reshape(-1)
+    if (link_status is not None and link_status.size != L) or (mask is not None and mask.shape != (L, capA)):
+        raise NmError("mosaic adjustment: link_status L values and mask (L, capA) expected")
+    nA = _pair_host_sizes(nAs)
+    chain_out = np.zeros((n, 9), np.float32)
+    fstat = np.zeros(n, np.int32)
+    rms = np.zeros((L, 2), np.float64)
+    stats = np.zeros(len(MOSAIC_ADJUST_STATS), np.float64)
+    arr, ptr = _pair_host_table, _pair_host_ptr
+    _check(lib().nm_mosaic_adjust_host_f32(n, L, la, lb, arr(src_xs), arr(src_ys), arr(nA), capA, arr(dst_xs), arr(dst_ys),
+                                           arr(matches), ptr(mask), ptr(link_status), ptr(chain), int(anchor), fw, fh,
+                                           int(iterations), int(min_rows), damping, max_step, ptr(chain_out), ptr(fstat),
+                                           ptr(rms), ptr(stats)), "nm_mosaic_adjust_host_f32")
+    return chain_out, fstat, rms, stats
+
+
+def mosaic_adjust_sums_host(src_x, src_y, nA, dst_x, dst_y, matches, fw, fh, Ga, Gb, mask=None, capA=None):
+    """One link's 153 sums and its contributing rows under the normalised maps Ga, Gb (float64, 9 values each, element 8
+    = 1) in the adjustment's summation order (nm_mosaic_adjust_sums_host_f32), for tests: (sums float64 (153,), count)."""
+    import numpy as np
+    (sx,), (sy,), (dx,), (dy,), (mt,), capA = _mosaic_adjust_host_rows([src_x], [src_y], [dst_x], [dst_y], [matches], capA)
+    mask = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8).reshape(-1)
+    if mask is not None and mask.size < capA:
+        raise NmError("mosaic adjustment: the mask is smaller than the capacity")
+    Ga, Gb = (np.ascontiguousarray(G, dtype=np.float64).reshape(-1) for G in (Ga, Gb))
+    if Ga.size != 9 or Gb.size != 9:
+        raise NmError("mosaic adjustment: Ga and Gb hold 9 values each")
+    sums = np.zeros(MOSAIC_ADJUST_SUMS, np.float64)
+    count = C.c_int(0)
+    ptr = _pair_host_ptr
+    _check(lib().nm_mosaic_adjust_sums_host_f32(ptr(sx), ptr(sy), int(nA), capA, ptr(dx), ptr(dy), ptr(mt), ptr(mask), fw, fh,
+                                                ptr(Ga), ptr(Gb), ptr(sums), C.byref(count)), "nm_mosaic_adjust_sums_host_f32")
+    return sums, count.value
 
 
 INGEST_MAX_BATCH = 64

@@ -4,6 +4,8 @@
 //   plan  (1 launch, 1 workgroup): lane 0 chains the n-1 links serially (63 3x3 products at most), then one lane per
 //         frame computes its footprint, record and chain row; the extent is a wave min / max. The same __host__
 //         __device__ functions build the host twin, so the two agree bit for bit.
+//   place (1 launch, 1 workgroup): the plan's placement half on a given chain (e.g. the adjusted one of
+//         nm_mosaic_adjust.hip): one lane per frame through the same mp_frame, the same extent.
 //   blend (1 launch, fixed grid): every workgroup stages the n records and frame pointers in LDS and clips the
 //         rectangles; a grid-stride loop walks the 64 x 4 tiles of the rectangles' bounding box, one canvas row of 64
 //         pixels per wave. A wave ballots the frames whose rectangle meets its row (a wave-uniform 64-bit mask) and
@@ -116,6 +118,14 @@ __host__ __device__ inline bool mp_frame(const float *M, int chained, int fw, in
     return false;
 }
 
+// Whether a frame of a given chain (nm_mosaic_place_f32) is to be placed: status 1 and a finite row
+__host__ __device__ __forceinline__ int mp_given(const float *M, int status)
+{
+    bool ok = status == 1;
+    for (int q = 0; q < 9; ++q) ok = ok && mp_finite(M[q]);
+    return ok ? 1 : 0;
+}
+
 inline bool mp_args_ok(int n, const float *H, int fw, int fh, int cw, int ch, int ox, int oy, const void *records)
 {
     const auto size_ok = [](int v) { return v >= 1 && v <= MP_LIMIT; };
@@ -155,6 +165,30 @@ __global__ __launch_bounds__(64) void mosaic_plan_kernel(int n, const float *__r
     if (!extent) return;                                  // uniform
     // every box value is an integer-valued finite float (no -0), so min / max are order-independent: equal to the
     // host twin's in-order loop
+    float e[4] = {placed ? box[0] : INFINITY, placed ? box[1] : INFINITY, placed ? box[2] : -INFINITY,
+                  placed ? box[3] : -INFINITY};
+    e[0] = nmw::wave_min(e[0]); e[1] = nmw::wave_min(e[1]); e[2] = nmw::wave_max(e[2]); e[3] = nmw::wave_max(e[3]);
+    const bool any = __ballot(placed) != 0ull;
+    if (k < 4) extent[k] = any ? e[k] : 0.f;
+}
+
+// The placement half of the plan on a given chain: one lane per frame, the extent as in the plan
+__global__ __launch_bounds__(64) void mosaic_place_kernel(int n, const float *__restrict__ chain,
+                                                          const int *__restrict__ frame_status, int fw, int fh, int cw,
+                                                          int ch, int ox, int oy, nm_mosaic_record *__restrict__ records,
+                                                          float *__restrict__ extent)
+{
+    const int k = threadIdx.x;
+    bool placed = false;
+    float box[4] = {0.f, 0.f, 0.f, 0.f};
+    if (k < n) {
+        float M[9];
+        for (int q = 0; q < 9; ++q) M[q] = chain[9 * k + q];
+        nm_mosaic_record rec;
+        placed = mp_frame(M, mp_given(M, frame_status ? frame_status[k] : 1), fw, fh, cw, ch, ox, oy, rec, box);
+        records[k] = rec;
+    }
+    if (!extent) return;                                  // uniform
     float e[4] = {placed ? box[0] : INFINITY, placed ? box[1] : INFINITY, placed ? box[2] : -INFINITY,
                   placed ? box[3] : -INFINITY};
     e[0] = nmw::wave_min(e[0]); e[1] = nmw::wave_min(e[1]); e[2] = nmw::wave_max(e[2]); e[3] = nmw::wave_max(e[3]);
@@ -278,6 +312,37 @@ int nm_mosaic_plan_f32(int n, const float *H, const int *status, int fw, int fh,
     if (!mp_args_ok(n, H, fw, fh, cw, ch, ox, oy, records)) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(mosaic_plan_kernel, dim3(1), dim3(64), 0, nm_stream(stream), n, H, status, fw, fh, cw, ch, ox, oy,
                        M_first, records, chain, extent);
+    NM_LAUNCH_CHECK();
+    return 0;
+}
+
+int nm_mosaic_place_host_f32(int n, const float *chain, const int *frame_status, int fw, int fh, int cw, int ch, int ox,
+                             int oy, nm_mosaic_record *records, float *extent)
+{
+    // mp_args_ok lets its second pointer (the plan's H) be null for n == 1; a chain is needed for every n
+    if (!mp_args_ok(n, chain, fw, fh, cw, ch, ox, oy, records) || !chain) return (int)hipErrorInvalidValue;
+    bool any = false;
+    float e[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int k = 0; k < n; ++k) {
+        float box[4];
+        const float *M = chain + 9 * k;
+        if (!mp_frame(M, mp_given(M, frame_status ? frame_status[k] : 1), fw, fh, cw, ch, ox, oy, records[k], box)) continue;
+        for (int q = 0; q < 2; ++q) e[q] = (!any || box[q] < e[q]) ? box[q] : e[q];
+        for (int q = 2; q < 4; ++q) e[q] = (!any || box[q] > e[q]) ? box[q] : e[q];
+        any = true;
+    }
+    if (extent)
+        for (int q = 0; q < 4; ++q) extent[q] = e[q];
+    return 0;
+}
+
+int nm_mosaic_place_f32(int n, const float *chain, const int *frame_status, int fw, int fh, int cw, int ch, int ox, int oy,
+                        nm_mosaic_record *records, float *extent, void *stream)
+{
+    // mp_args_ok lets its second pointer (the plan's H) be null for n == 1; a chain is needed for every n
+    if (!mp_args_ok(n, chain, fw, fh, cw, ch, ox, oy, records) || !chain) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(mosaic_place_kernel, dim3(1), dim3(64), 0, nm_stream(stream), n, chain, frame_status, fw, fh, cw, ch,
+                       ox, oy, records, extent);
     NM_LAUNCH_CHECK();
     return 0;
 }
