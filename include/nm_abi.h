@@ -1280,6 +1280,66 @@ NM_API int nm_mosaic_adjust_sums_host_f32(const float *src_x, const float *src_y
                                           const float *dst_y, const int *matches, const unsigned char *mask, int fw, int fh,
                                           const double *Ga, const double *Gb, double *sums, int *count);
 
+/* ---- Link proposal: which frame pairs of a sequence to link at all (no reference counterpart). Two steps, both on
+ * `stream` with no allocation, no synchronisation and no host read -- capturable into a HIP graph.
+ * nm_link_votes_dev_u8: the u8 matcher's ratio test for ALL ordered pairs of n in [1, NM_LINK_PROPOSE_MAX_FRAMES] frames,
+ * each pair reduced to a count, in TWO launches whatever n is (row norms once per frame, vote scan on the i8 matrix cores).
+ *   desc[k]      HOST table of n device pointers: cap x 128 unsigned chars, row-major, 16-byte aligned (out_u8 of the
+ *                finish, out_desc_u8 of the selection). Two slots may name the same table;
+ *   d_count[k]   HOST table of n device pointers to DEVICE ints: n_k = clip(*d_count[k], 0, cap). Rows beyond n_k are never
+ *                read;
+ *   cap          in [1, 2^22);
+ *   votes        device, n x n ints, row-major; EVERY entry is written.
+ * Semantics: for a != b, votes[a n + b] is the number of rows i < n_a for which nm_sift_match_u8_host on (A = desc[a],
+ * nA = n_a, B = desc[b], nB = n_b, ambiguity), with result pre-filled with -1, leaves result[i] >= 0. As one rule: a row
+ * counts when it passes the matcher's last step (min1 / min2 < ambiguity with an fp32 divide of the exact integer
+ * distances), so a row whose second distance is 0 does not count, and a row against n_b == 1 is tested against
+ * min2 = 2139095040.0f and counts. votes[a n + a] = 0; a frame with no rows has zeros in its row and its column. The count
+ * does not depend on which of several equal minima comes first. The output depends on the inputs alone: not on the previous
+ * contents of votes or the workspace, on n, on the slot a frame sits in (permuting the frames permutes votes) or on
+ * scheduling (the only sums are integer sums).
+ * workspace: device, 16-byte aligned, nm_link_votes_workspace_bytes(n, cap) bytes (0 for arguments out of range), no
+ * contents expected or preserved.
+ * Returns hipErrorInvalidValue, before anything is launched or dereferenced, for n not in [1, 64], cap not in [1, 2^22), a
+ * NULL desc, d_count, votes or workspace, a NULL among the first n entries of a table, or a descriptor pointer or
+ * workspace that is not 16-byte aligned.
+ * nm_link_votes_host_u8: the same with every pointer in host memory (no alignment rule), no workspace and no stream: a
+ * loop over the ordered pairs through the matcher's host pair function and a count; identical results.
+ * nm_link_votes_set_split (tuning, process-wide): the vote scan's grid is (ceil(cap / 256), n, z), the candidate frames of
+ * a query wave divided into z parts. z in [1, 64] fixes the number of parts (clipped to n); any other value restores the
+ * default, which takes one part when ceil(cap / 256) n reaches 512 workgroups and else as many as reach it. Results are
+ * identical for every z. Returns the previous setting (0: the default).
+ *
+ * nm_link_rank_dev: the vote matrix -> a ranked link list sized for nm_mosaic_adjust_dev_f32, in ONE launch of one
+ * workgroup. All integers:
+ *   Score: for a < b, score(a, b) = min(votes[a n + b], votes[b n + a]): both directions must agree.
+ *   Candidates: the pairs a < b with b - a >= min_gap and score >= min_votes. min_gap >= 1 (2 leaves out the sequential
+ *     links), min_votes >= 1.
+ *   Order: by (score descending, a ascending, b ascending) -- a total order.
+ *   Walk: the candidates are taken in that order. One is accepted when fewer than max_links are accepted so far and, if
+ *     per_frame > 0, each of its two frames has fewer than per_frame accepted links; otherwise it is passed over and the
+ *     walk goes on. per_frame = 0: no limit per frame; per_frame >= 0.
+ *   Outputs (device): link_a, link_b, link_score, max_links ints each, max_links in [1, NM_LINK_PROPOSE_MAX_LINKS]: the
+ *     accepted links in acceptance order with their scores; every entry at and beyond the accepted count is -1 / -1 / 0.
+ *     *d_links: the accepted count. No output keeps a previous value.
+ * Returns hipErrorInvalidValue, before anything is launched or dereferenced, for n not in [1, 64], min_votes < 1,
+ * min_gap < 1, per_frame < 0, max_links not in [1, 256] or a NULL pointer.
+ * nm_link_rank_host: the same with every pointer in host memory and no stream: a sort and the same walk.
+ * The pair tables of the stages that follow are HOST tables of device pointers, so the client reads d_links and the three
+ * lists once to build them.                                                                                            */
+#define NM_LINK_PROPOSE_MAX_FRAMES 64
+#define NM_LINK_PROPOSE_MAX_LINKS 256
+NM_API size_t nm_link_votes_workspace_bytes(int n, int cap);
+NM_API int nm_link_votes_dev_u8(int n, const unsigned char *const *desc, const int *const *d_count, int cap,
+                                float ambiguity, int *votes, void *workspace, void *stream);
+NM_API int nm_link_votes_host_u8(int n, const unsigned char *const *desc, const int *const *count, int cap,
+                                 float ambiguity, int *votes);
+NM_API int nm_link_votes_set_split(int z);
+NM_API int nm_link_rank_dev(int n, const int *votes, int min_votes, int min_gap, int per_frame, int max_links,
+                            int *link_a, int *link_b, int *link_score, int *d_links, void *stream);
+NM_API int nm_link_rank_host(int n, const int *votes, int min_votes, int min_gap, int per_frame, int max_links,
+                             int *link_a, int *link_b, int *link_score, int *d_links);
+
 /* ---- Batched frame ingest (no reference counterpart: the reference's client undistorts and converts each frame with
  * its own launches). nm_frame_ingest_batch_f32 turns n camera frames into the fp32 gray planes SIFT reads and,
  * optionally, their undistorted BGRA frames, in ONE launch.

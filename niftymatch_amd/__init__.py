@@ -151,6 +151,12 @@ _SIGNATURES = {
     "nm_mosaic_adjust_host_f32": (_I, [_I, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, C.c_double,
                                        C.c_double, _P, _P, _P, _P]),
     "nm_mosaic_adjust_sums_host_f32": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
+    "nm_link_votes_workspace_bytes": (_SZ, [_I, _I]),
+    "nm_link_votes_dev_u8": (_I, [_I, _P, _P, _I, _F, _P, _P, _P]),
+    "nm_link_votes_host_u8": (_I, [_I, _P, _P, _I, _F, _P]),
+    "nm_link_votes_set_split": (_I, [_I]),
+    "nm_link_rank_dev": (_I, [_I, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "nm_link_rank_host": (_I, [_I, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "nm_frame_ingest_batch_f32": (_I, [_I, _P, _I, _I, _P, _P, _I, _I, _P, _P, _P]),
     "nm_sift_arena_create": (_I, [_I, _I, _I, _P]),
     "nm_sift_arena_destroy": (None, [_P]),
@@ -1958,6 +1964,120 @@ def mosaic_adjust_sums_host(src_x, src_y, nA, dst_x, dst_y, matches, fw, fh, Ga,
     _check(lib().nm_mosaic_adjust_sums_host_f32(ptr(sx), ptr(sy), int(nA), capA, ptr(dx), ptr(dy), ptr(mt), ptr(mask), fw, fh,
                                                 ptr(Ga), ptr(Gb), ptr(sums), C.byref(count)), "nm_mosaic_adjust_sums_host_f32")
     return sums, count.value
+
+
+LINK_PROPOSE_MAX_FRAMES = _PAIR_MAX_BATCH
+LINK_PROPOSE_MAX_LINKS = MOSAIC_ADJUST_MAX_LINKS
+
+
+class LinkVotesWorkspace(_PairWorkspace):
+    """Device scratch of link_votes_dev for up to n frames of cap rows (one integer norm per row and frame)."""
+    _bytes_fn, _what, _shape_text = "nm_link_votes_workspace_bytes", "link-votes workspace", "n %r / cap %r"
+
+    def __init__(self, n, cap, device=None):
+        self._alloc(device, n=n, cap=cap)
+
+
+def link_votes_set_split(z=0):
+    """Tuning: the number of parts the vote scan divides a wave's candidate frames into (nm_link_votes_set_split); 0 restores
+    the default. Results do not depend on it. Returns the previous setting."""
+    return lib().nm_link_votes_set_split(int(z))
+
+
+def link_votes_dev(descs_u8, d_counts, ambiguity=0.8, votes=None, workspace=None, cap=None):
+    """The u8 matcher's ratio test for all ordered pairs of n = len(descs_u8) <= LINK_PROPOSE_MAX_FRAMES frames, each pair
+    reduced to a count (nm_link_votes_dev_u8): two launches on the current stream whatever n is, no host read. descs_u8 are
+    uint8 device tensors (rows, 128) (out_u8 of desc_finish_batch_dev, out_desc_u8 of the selection), d_counts int32 DEVICE
+    sizes. votes: an int32 device tensor of n x n entries to write into (default: new); every entry is written:
+    votes[a, b] = rows of frame a that sift_match_u8_batch_dev would match into frame b, 0 on the diagonal. workspace: a
+    LinkVotesWorkspace (default: new). Returns votes as (n, n)."""
+    torch = _torch()
+    n = _pair_count(descs_u8, d_counts)
+    _pair_descriptors(descs_u8)
+    cap = _pair_cap(cap, list(descs_u8))
+    device = _pair_device(list(descs_u8) + list(d_counts) + [votes, workspace.buf if workspace is not None else None],
+                          list(d_counts))
+    if votes is None:
+        votes = torch.empty((n, n), dtype=torch.int32, device=device)
+    if votes.numel() != n * n:
+        raise NmError("link votes: votes must hold n x n values")
+    workspace = _pair_workspace(LinkVotesWorkspace, workspace, device, n, cap)
+    arr = _pair_dev_table
+    _check(lib().nm_link_votes_dev_u8(n, arr(descs_u8, torch.uint8), arr(d_counts, torch.int32), cap, float(ambiguity),
+                                      _dev(votes, torch.int32), _dev(workspace.buf), _stream()), "nm_link_votes_dev_u8")
+    return votes.view(n, n)
+
+
+def link_votes_host(descs_u8, counts, ambiguity=0.8, cap=None):
+    """link_votes_dev on the host (nm_link_votes_host_u8): numpy in and out, identical results. counts are host ints.
+    Returns (n, n) int32."""
+    import numpy as np
+    n = _pair_count(descs_u8, counts)
+    descs_u8 = _pair_host_arrays(descs_u8, np.uint8, flat=False)
+    _pair_descriptors(descs_u8)
+    cap = _pair_cap(cap, descs_u8)
+    votes = np.empty((n, n), np.int32)
+    arr = _pair_host_table
+    _check(lib().nm_link_votes_host_u8(n, arr(descs_u8), arr(_pair_host_sizes(counts)), cap, float(ambiguity),
+                                       _pair_host_ptr(votes)), "nm_link_votes_host_u8")
+    return votes
+
+
+def _link_rank_check(votes_shape, min_votes, min_gap, per_frame, max_links):
+    n = votes_shape[0]
+    if len(votes_shape) != 2 or votes_shape[1] != n or not 1 <= n <= LINK_PROPOSE_MAX_FRAMES:
+        raise NmError("link ranking: votes must be (n, n) with n in [1, %d]" % LINK_PROPOSE_MAX_FRAMES)
+    if any(int(v) != v for v in (min_votes, min_gap, per_frame, max_links)) or min_votes < 1 or min_gap < 1 or per_frame < 0 or \
+            not 1 <= max_links <= LINK_PROPOSE_MAX_LINKS:
+        raise NmError("link ranking: min_votes >= 1, min_gap >= 1, per_frame >= 0 and max_links in [1, %d] expected"
+                      % LINK_PROPOSE_MAX_LINKS)
+    return n
+
+
+def link_rank_dev(votes, min_votes=16, min_gap=2, per_frame=0, max_links=LINK_PROPOSE_MAX_LINKS, links=None):
+    """The vote matrix of link_votes_dev -> a ranked link list (nm_link_rank_dev): one launch on the current stream, no host
+    read. score(a, b) = min(votes[a, b], votes[b, a]) for a < b; candidates have b - a >= min_gap and score >= min_votes, go
+    by (score descending, a, b) and are accepted while fewer than max_links are and, for per_frame > 0, both frames have fewer
+    than per_frame links. links: (link_a, link_b, link_score, d_links) int32 device tensors to write into (default: new).
+    Returns them: the accepted links in acceptance order, -1 / -1 / 0 behind them, and the count in d_links[0]."""
+    torch = _torch()
+    n = _link_rank_check(tuple(votes.shape), min_votes, min_gap, per_frame, max_links)
+    if links is None:
+        links = tuple(torch.empty(max_links, dtype=torch.int32, device=votes.device) for _ in range(3)) + \
+            (torch.empty(1, dtype=torch.int32, device=votes.device),)
+    la, lb, ls, cnt = links
+    if any(t.numel() < max_links for t in (la, lb, ls)) or cnt.numel() < 1:
+        raise NmError("link ranking: the link lists hold max_links values and d_links one")
+    _pair_device([votes, la, lb, ls, cnt], [])
+    i32 = torch.int32
+    _check(lib().nm_link_rank_dev(n, _dev(votes, i32), int(min_votes), int(min_gap), int(per_frame), int(max_links), _dev(la, i32),
+                                  _dev(lb, i32), _dev(ls, i32), _dev(cnt, i32), _stream()), "nm_link_rank_dev")
+    return la, lb, ls, cnt
+
+
+def link_rank_host(votes, min_votes=16, min_gap=2, per_frame=0, max_links=LINK_PROPOSE_MAX_LINKS):
+    """link_rank_dev on the host (nm_link_rank_host): numpy in and out, identical results. Returns (link_a, link_b,
+    link_score, count) with count a Python int."""
+    import numpy as np
+    votes = np.ascontiguousarray(votes, dtype=np.int32)
+    n = _link_rank_check(votes.shape, min_votes, min_gap, per_frame, max_links)
+    la, lb, ls = (np.full(max_links, -9, np.int32) for _ in range(3))
+    cnt = np.full(1, -9, np.int32)
+    ptr = _pair_host_ptr
+    _check(lib().nm_link_rank_host(n, ptr(votes), int(min_votes), int(min_gap), int(per_frame), int(max_links), ptr(la), ptr(lb),
+                                   ptr(ls), ptr(cnt)), "nm_link_rank_host")
+    return la, lb, ls, int(cnt[0])
+
+
+def link_propose(descs_u8, d_counts, ambiguity=0.8, min_votes=16, min_gap=2, per_frame=0, max_links=LINK_PROPOSE_MAX_LINKS,
+                 cap=None, votes=None, links=None, workspace=None):
+    """Which frame pairs of a sequence to link: link_votes_dev, then link_rank_dev, three launches on the current stream and
+    no host read. Returns (link_a, link_b, link_score, d_links, votes), all device tensors. The pair tables of the stages
+    that follow are host tables, so the caller reads d_links and the lists once."""
+    votes = link_votes_dev(descs_u8, d_counts, ambiguity=ambiguity, votes=votes, workspace=workspace, cap=cap)
+    la, lb, ls, cnt = link_rank_dev(votes, min_votes=min_votes, min_gap=min_gap, per_frame=per_frame, max_links=max_links,
+                                    links=links)
+    return la, lb, ls, cnt, votes
 
 
 INGEST_MAX_BATCH = 64

@@ -25,7 +25,9 @@
 //                 prologue, tile stream, merge and store are the shared ones.
 // No LDS, no atomics. The lane -> (row, k) map of the i8 operands is checked by tools/micro/mfma_i8_model.hip. The operand
 // fragments, the row norm, PAD_NORM, the tile stream and the host's row distance are nm_match_u8_dev.hpp, shared with the
-// mutual filter (nm_match_mutual_u8.hip). The host twins are one sorted insertion on (d, j); the matcher's is its k = 2.
+// mutual filter (nm_match_mutual_u8.hip); fold_top2, emit_u8 and their constants are there too, shared with the link votes
+// (nm_link_propose.hip), whose host twin calls the matcher's through nmu8::match_pair_host. The host twins are one sorted
+// insertion on (d, j); the matcher's is its k = 2.
 #include "nm_common.hpp"
 #include "nm_match_u8_dev.hpp"
 #include "nm_pair_batch.hpp"
@@ -38,14 +40,8 @@ namespace {
 using namespace nmu8;
 
 constexpr int QB = QW * TB / 64;            // queries per workgroup
-constexpr int NO_SECOND = 1 << 24;          // a min2 at or above this is "no second candidate"
-constexpr float MIN2_INIT = 2139095040.0f;  // match.cu:91, the int 0x7f800000 converted
 constexpr int KNN_NONE = KEY_INF;           // the distance of a slot without a candidate (its index is -1)
-constexpr int LIST_INF = KEY_INF >> 4;      // an unused list entry: above every padded row's distance, and what KEY_INF decodes to
-constexpr int NO_ROW = KEY_INF;             // the index of an entry that names no row: behind every row at an equal distance
-static_assert(LIST_INF > PAD_NORM + (1 << 23), "an unused list entry sorts behind the padded rows");
-static_assert(PAD_NORM - (1 << 22) >= NO_SECOND && LIST_INF >= NO_SECOND && KNN_NONE >= NO_SECOND,
-              "a padded row, an unused entry and an empty slot all read as no second candidate");
+static_assert(KNN_NONE >= NO_SECOND, "an empty slot reads as no second candidate");
 static_assert(NM_MATCH_KNN_U8_MAX_BATCH == NM_MATCH_U8_MAX_BATCH, "the k-NN entry shares the matcher's rows and norms launch");
 
 struct PairRows {                           // the rows of both entries: 4 x 64 pointers, 2 KB of kernel arguments
@@ -65,20 +61,6 @@ __host__ __device__ inline size_t rows_b(int capB) { return ((size_t)capB + TILE
 __host__ __device__ inline int *norms_of(void *ws, int k, int capA, int capB)
 {
     return static_cast<int *>(ws) + (size_t)k * (rows_a(capA) + rows_b(capB));
-}
-
-// The reference's last step on exact integer distances (every one of them is also an exact float): m1 at the lowest index
-// idx, m2 = the smallest of the others or anything >= NO_SECOND. The scan's min2 starts at MIN2_INIT and is overwritten at
-// every replacement of the minimum, so the start value survives only while the minimum sits at candidate 0; every real
-// distance is below it, so it shows only for nB == 1.
-__host__ __device__ __forceinline__ void emit_u8(int m1, int idx, int m2, float ambiguity, int *__restrict__ out)
-{
-    const float f1 = (float)m1;
-    const float f2 = m2 >= NO_SECOND ? MIN2_INIT : (float)m2;
-    if (f2 > 0.0f) {
-        const float q = f1 / f2;
-        *out = (q < ambiguity) ? idx : -1;
-    }
 }
 
 // ---- what half 0 stores for query qi of pair p from its merged ascending list (ld, lj) ----
@@ -159,30 +141,6 @@ __device__ __forceinline__ void fold_list(int (&ld)[L], int (&lj)[L], const int 
 #pragma unroll
             for (int e = 0; e < 16; ++e) off = min(off, (unsigned)key[e] - above);
             g1 = (int)(above + off);
-        }
-    }
-}
-
-// The top-2 fold, for an output that reads (ld[0], lj[0], ld[1]) only: the tile's two smallest keys in one min / max pass
-// (which finds the smallest again; the kernel's own is then dead code), merged under ONE vote; lj[1] is not kept (it stays
-// NO_ROW, so the merge of the halves never puts it in front of a real row). fold_list<2> gives the same three values: 5.6 %
-// faster on 16 pairs of 12k rows but 1.1 % slower on one pair of 4k rows, where a scan is few tiles.
-__device__ __forceinline__ void fold_top2(int (&ld)[2], int (&lj)[2], const int (&key)[16], int t, int h)
-{
-    int g1 = KEY_INF, g2 = KEY_INF;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-        g2 = min(g2, max(g1, key[e]));
-        g1 = min(g1, key[e]);
-    }
-    const int d1 = g1 >> 4;
-    if (__any(d1 < ld[1])) {
-        if (d1 < ld[0]) {
-            ld[1] = min(ld[0], g2 >> 4);
-            ld[0] = d1;
-            lj[0] = acc_row(t, g1 & 15, h);
-        } else {
-            ld[1] = min(ld[1], d1);
         }
     }
 }
@@ -306,6 +264,11 @@ void launch_scan(const PairRows &rows, const Out &out, int n, int capA, int capB
 }
 
 }  // namespace
+
+void nmu8::match_pair_host(const unsigned char *A, int nA, const unsigned char *B, int nB, float ambiguity, int *result)
+{
+    host_match_pair(A, nA, B, nB, ambiguity, result);
+}
 
 extern "C" size_t nm_sift_match_u8_workspace_bytes(int n, int capA, int capB)
 {

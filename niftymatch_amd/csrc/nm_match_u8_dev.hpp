@@ -1,6 +1,6 @@
-// nm_match_u8_dev.hpp -- what the three users of v_mfma_i32_32x32x32_i8 on unsigned-char descriptors share (the matcher and
-// the k-NN entry, which are one scan kernel with two outputs in nm_match_u8.hip, and the mutual filter's scan in
-// nm_match_mutual_u8.hip): the operand fragments of a 128-byte row (bytes - 128 as signed i8), the integer row norm
+// nm_match_u8_dev.hpp -- what the users of v_mfma_i32_32x32x32_i8 on unsigned-char descriptors share (the matcher and
+// the k-NN entry, which are one scan kernel with two outputs in nm_match_u8.hip, the mutual filter's scan in
+// nm_match_mutual_u8.hip, and the all-pairs vote scan in nm_link_propose.hip): the operand fragments of a 128-byte row (bytes - 128 as signed i8), the integer row norm
 // |row - 128|^2, the norm of a row that does not exist, the alignment test of the entries, the tile stream of their hot
 // kernels, and the plain integer distance of two rows that their host twins use.
 // A fragment is one lane's share of a row for the four k steps of a 32 x 32 x 128 product: lane (r = lane & 31, h = lane >>
@@ -11,7 +11,8 @@
 // their fragments Frag qf[QG] in 32 registers as the B operand. for_tiles streams the other side's rows in tiles of 32 as the
 // A operand straight from global memory, the next tile and its norms requested before this one is used; per tile the kernel's
 // body takes tile_product(cf, qf[g]) (a.b of 32 x 32 rows over the 4 k steps) and decodes a register with acc_row. What a
-// kernel makes of the 16 accumulators (an ordered list of the best few, a threshold test) is its own.
+// kernel makes of the 16 accumulators (an ordered list of the best few, a threshold test) is its own. The ratio test's pieces
+// (the top-2 fold of a tile's keys, the last step emit_u8 and their constants) are here for the matcher and the vote scan.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -30,6 +31,13 @@ constexpr int QW = 32 * QG;                 // items per wave
 constexpr int PAD_NORM = 1 << 25;           // norm of a streamed row that does not exist: d >= 2^25 - 2^22 > 2^23
 constexpr int KEY_INF = 0x7fffffff;
 static_assert(DIM * 255 * 255 < (1 << 23) && ((PAD_NORM + (1 << 23)) >> 27) == 0, "keys (d << 4 | e) stay positive ints");
+constexpr int NO_SECOND = 1 << 24;          // a min2 at or above this is "no second candidate"
+constexpr float MIN2_INIT = 2139095040.0f;  // match.cu:91, the int 0x7f800000 converted
+constexpr int LIST_INF = KEY_INF >> 4;      // an unused list entry: above every padded row's distance, and what KEY_INF decodes to
+constexpr int NO_ROW = KEY_INF;             // the index of an entry that names no row: behind every row at an equal distance
+static_assert(LIST_INF > PAD_NORM + (1 << 23), "an unused list entry sorts behind the padded rows");
+static_assert(PAD_NORM - (1 << 22) >= NO_SECOND && LIST_INF >= NO_SECOND,
+              "a padded row and an unused entry both read as no second candidate");
 
 __device__ __forceinline__ int row_norm(const unsigned char *__restrict__ row)
 {
@@ -104,6 +112,44 @@ __device__ __forceinline__ i32x16 tile_product(const Frag &cf, const Frag &qf)
 /* The streamed row that register e of tile t's accumulator holds in lane half h */
 __device__ __forceinline__ int acc_row(int t, int e, int h) { return t * TILE + (e & 3) + 8 * (e >> 2) + 4 * h; }
 
+// The top-2 fold, for an output that reads (ld[0], lj[0], ld[1]) only: the tile's two smallest keys in one min / max pass
+// (which finds the smallest again; the kernel's own is then dead code), merged under ONE vote; lj[1] is not kept (it stays
+// NO_ROW, so the merge of the halves never puts it in front of a real row). fold_list<2> gives the same three values: 5.6 %
+// faster on 16 pairs of 12k rows but 1.1 % slower on one pair of 4k rows, where a scan is few tiles.
+__device__ __forceinline__ void fold_top2(int (&ld)[2], int (&lj)[2], const int (&key)[16], int t, int h)
+{
+    int g1 = KEY_INF, g2 = KEY_INF;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+        g2 = min(g2, max(g1, key[e]));
+        g1 = min(g1, key[e]);
+    }
+    const int d1 = g1 >> 4;
+    if (__any(d1 < ld[1])) {
+        if (d1 < ld[0]) {
+            ld[1] = min(ld[0], g2 >> 4);
+            ld[0] = d1;
+            lj[0] = acc_row(t, g1 & 15, h);
+        } else {
+            ld[1] = min(ld[1], d1);
+        }
+    }
+}
+
+// The reference's last step on exact integer distances (every one of them is also an exact float): m1 at the lowest index
+// idx, m2 = the smallest of the others or anything >= NO_SECOND. The scan's min2 starts at MIN2_INIT and is overwritten at
+// every replacement of the minimum, so the start value survives only while the minimum sits at candidate 0; every real
+// distance is below it, so it shows only for nB == 1.
+__host__ __device__ __forceinline__ void emit_u8(int m1, int idx, int m2, float ambiguity, int *__restrict__ out)
+{
+    const float f1 = (float)m1;
+    const float f2 = m2 >= NO_SECOND ? MIN2_INIT : (float)m2;
+    if (f2 > 0.0f) {
+        const float q = f1 / f2;
+        *out = (q < ambiguity) ? idx : -1;
+    }
+}
+
 /* Host twins: the exact squared distance of two rows, a plain sum of DIM integer squares */
 inline int row_distance(const unsigned char *a, const unsigned char *b)
 {
@@ -114,6 +160,9 @@ inline int row_distance(const unsigned char *a, const unsigned char *b)
     }
     return d;
 }
+
+/* The matcher's host twin for one pair (nm_match_u8.hip): result[i], i < nA, as nm_sift_match_u8_host leaves it */
+void match_pair_host(const unsigned char *A, int nA, const unsigned char *B, int nB, float ambiguity, int *result);
 
 inline bool aligned16(int n, const unsigned char *const *t)
 {
