@@ -214,9 +214,16 @@ def test_chain_with_refinement_captures_and_replays(nm, oracle, cuda):
     torch.cuda.synchronize()
     assert np.array_equal(plain[0].cpu().numpy().view(np.uint32), H.view(np.uint32))
     assert np.array_equal(plain[1].cpu().numpy(), count) and (plain[2].cpu().numpy() == 1).all()
-    # reported, not asserted: the refit's and the refined maps against the views' true maps
+    # the refit's and the refined maps against the views' true maps: the refined map is no farther from the truth than the
+    # unquantised float64 model's, run on the same gray planes from the refit's map, plus the device-to-model bound of
+    # tests/test_gpu_loop_closure.py
+    from test_gpu_loop_closure import REFINE_TO_MODEL_PX
     from test_link_refine_host import true_maps
+    grays = [g.cpu().numpy() for g in nm.ingest_batch([v.clone() for v in v2])]
     for k, Ht in enumerate(true_maps()):
-        e0, e1 = R.corner_error(H[k], Ht, VW, VH), R.corner_error(Hr[k], Ht, VW, VH)
-        print("link %d: refit %.4f px, refined %.4f px, %d steps, end %d" % (k, e0, e1, rstats[k][6], rstats[k][8]))
+        model = R.model_f64(grays[k], grays[k + 1], H[k], stride=4, iterations=4)
+        e0, e1, em = (R.corner_error(m, Ht, VW, VH) for m in (H[k], Hr[k], model))
+        print("link %d: refit %.4f px, refined %.4f px, model %.4f px, device to model %.5f px, %d steps, end %d"
+              % (k, e0, e1, em, R.corner_error(Hr[k], model, VW, VH), rstats[k][6], rstats[k][8]))
+        assert e1 <= em + 4.0 * REFINE_TO_MODEL_PX, (k, e1, em)
     ch.close()
