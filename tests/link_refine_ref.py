@@ -56,8 +56,8 @@ def pixels_int(A, B, H, mask, stride):
     i, j = np.where(ok, i, 0), np.where(ok, j, 0)
     acc = np.full(x.shape, 32768, np.int64)
     for t, w in enumerate(((256 - a) * (256 - b), a * (256 - b), (256 - a) * b, a * b)):
-        ii, jj = i + (t & 1), j + (t >> 1)
-        okB, qt = V.levels(B[jj, ii])
+        ii, jj = np.where(ok, i + (t & 1), 0), np.where(ok, j + (t >> 1), 0)   # a rejected pixel reads (0, 0): a frame of
+        okB, qt = V.levels(B[jj, ii])                                           # one column or row has no (1, .) or (., 1)
         ok &= okB & seen[jj, ii]
         acc += w * qt
     return x, y, inL, ok, qa, acc >> 16, seen

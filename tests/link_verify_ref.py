@@ -85,8 +85,8 @@ def sums_int(A, B, H, mask=None, stride=4):
     weights = ((256 - a) * (256 - b), a * (256 - b), (256 - a) * b, a * b)
     assert all(int(v) == 65536 for v in sum(weights))
     for t, w in enumerate(weights):
-        ii, jj = i + (t & 1), j + (t >> 1)
-        okB, qt = levels(B[jj, ii])
+        ii, jj = np.where(ok, i + (t & 1), 0), np.where(ok, j + (t >> 1), 0)   # a rejected pixel reads (0, 0): a frame of
+        okB, qt = levels(B[jj, ii])                                             # one column or row has no (1, .) or (., 1)
         ok &= okB & seen[jj, ii]
         acc += w * qt
     qb = acc >> 16
