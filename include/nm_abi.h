@@ -1280,6 +1280,100 @@ NM_API int nm_mosaic_adjust_sums_host_f32(const float *src_x, const float *src_y
                                           const float *dst_y, const int *matches, const unsigned char *mask, int fw, int fh,
                                           const double *Ga, const double *Gb, double *sums, int *count);
 
+/* ---- Mosaic exposure compensation (no reference counterpart): per-frame, per-channel gains that level the brightness and
+ * colour steps between frames of different exposure, between nm_mosaic_adjust_dev_f32 / nm_mosaic_place_f32 and the blend.
+ * Three stages: measure (per-link overlap sums from the BGRA frames), solve (gains from the sums), apply (the gained
+ * blend). All on `stream` with no allocation, no synchronisation, no host read and no workspace; no kernel waits for
+ * another workgroup: measure -> solve -> place -> gained blend can be captured into one HIP graph.
+ *
+ * nm_mosaic_exposure_sums_dev (measure): n in [1, 64] frames, L in [1, NM_EXPOSURE_MAX_LINKS] links. frames: HOST table of n
+ * device pointers to fw x fh uchar4 (B, G, R, A) frames as the blend takes them; pointers may repeat. link_a, link_b: HOST
+ * int arrays of L (the adjustment's convention), indices in [0, n), a != b. H: device, L x 9 fp32, H_l maps frame-a pixels
+ * to frame-b pixels. mask: optional device fp32 plane fw x fh shared by all frames; a pixel is seen where mask > 0.5.
+ * link_status: optional device ints, L. stride in [1, 64]; lo, hi bytes, 0 <= lo <= hi <= 255.
+ *   Lattice, projection and sampler are those of nm_link_verify_batch_dev_f32 above: lattice pixels (x, y) =
+ *   (s u + s/2, s v + s/2), u < fw / s, v < fh / s; a lattice pixel passes when the mask sees it, den = project_den(H_l, x, y)
+ *   is finite and > 0, tex_setup accepts (xp + 0.5f, yp + 0.5f) on frame b, the four taps (i, j), (i+1, j), (i, j+1),
+ *   (i+1, j+1) all lie inside frame b and the mask sees all four; the integer weights are w_t = 65536 {(1-a)(1-b), a(1-b),
+ *   (1-a)b, ab}. For such a pixel and channel c in {B, G, R} (bytes 0, 1, 2 of a uchar4): a_c is frame a's byte at the
+ *   pixel, b_c = (w_0 p_0c + w_1 p_1c + w_2 p_2c + w_3 p_3c + 32768) >> 16 from frame b's four tap bytes p_tc. The pixel
+ *   COUNTS only when all three a_c and all twelve p_tc lie in [lo, hi] (a tap of weight 0 included; the alpha bytes are not
+ *   looked at): a clipped pixel carries no exposure information.
+ *   sums: device, L x NM_EXPOSURE_SUMS unsigned 64-bit = (N, Sa_B, Sa_G, Sa_R, Sb_B, Sb_G, Sb_R): the number of counting
+ *   pixels and the sums of their a_c and b_c. Integers: they depend on the link's inputs alone, never on L, n, the link's
+ *   slot, the launch grouping or scheduling. A link with link_status[l] != 1 or a non-finite H_l gets seven zeros.
+ *   ONE memset node (the sums) and ONE launch whatever L is: the frame pointers (512 B) and the link indices (512 B) travel
+ *   as kernel arguments; a link's lattice tiles are dealt to up to 256 workgroups, each ending in one vector atomic add per
+ *   sum. Returns hipErrorInvalidValue, touching no device memory, for n not in [1, 64], L not in [1, 256], fw or fh not in
+ *   [1, 32767], stride not in [1, 64], (fw / stride)(fh / stride) > 2^28, lo < 0, lo > hi, hi > 255, a NULL frames, link_a,
+ *   link_b, H or sums, a NULL among the first n frame pointers, a link index outside [0, n) or a link with a == b.
+ * nm_mosaic_exposure_sums_host: the same with every pointer in host memory, compiled from the same functions
+ * (csrc/nm_mosaic_exposure_math.hpp): identical bit for bit.
+ *
+ * nm_mosaic_gains_dev (solve): one launch of one workgroup. n, L, link_a, link_b as above; sums: device, L x 7 as measured;
+ * link_status optional device ints. Link l is USABLE when (link_status == NULL || link_status[l] == 1) and
+ * N_l >= min_pixels. mode NM_EXPOSURE_PER_CHANNEL solves one system per channel c with abar_l = Sa_c / N, bbar_l = Sb_c / N;
+ * NM_EXPOSURE_COMMON solves one system with abar_l = ((Sa_B + Sa_G) + Sa_R) / (3 N), bbar alike, and writes its gain to all
+ * three channels. All in fp64, fma explicit, IEEE division and sqrt. Per system the gains g minimise
+ *     sum over usable links  N_l [ (g_a abar_l - g_b bbar_l)^2 / sigma_n^2 + ((1 - g_a)^2 + (1 - g_b)^2) / sigma_g^2 ]
+ *   which is linear and, by the prior, strictly positive definite: no anchor. With N = (double)N_l,
+ *   wn = N / (sigma_n sigma_n), wg = N / (sigma_g sigma_g), the n x n matrix M and right-hand side r start at +0 and take
+ *   the usable links in ascending order, every entry its own chain s <- s + t or s <- s - t:
+ *     M[a][a] += fma(wn abar, abar, wg);  M[b][b] += fma(wn bbar, bbar, wg);  M[a][b] -= (wn abar) bbar;
+ *     M[b][a] -= (wn abar) bbar;  r[a] += wg;  r[b] += wg.
+ *   A frame with no usable link gets M[k][k] = 1, r[k] = 1: its gain is exactly 1. The Cholesky and the two substitutions
+ *   are the written-order ones of the adjustment (csrc/nm_chol_math.hpp): left-looking by columns, element i of column j
+ *   v = M[j][i], v = fma(-M[k][i], M[j][k], v) for k < j in order, pivot sqrt(v) (not > 0 or not finite: SINGULAR),
+ *   M[j][i] = M[i][j] = v / pivot, r as column n; backward x_i = (r_i - chain) / M[i][i], chain v = fma(-M[i][k], x_k, v)
+ *   for k = i+1 .. n-1. The cost of a system at gains g, links ascending from +0:
+ *     e = fma(g_a, abar, -(g_b bbar)), da = 1 - g_a, db = 1 - g_b, cost <- cost + fma(wn e, e, wg fma(da, da, db db)).
+ *   gains: device, n x 3 fp32 in B, G, R order, clamp((float)g, g_min, g_max). stats: device, NM_EXPOSURE_STATS doubles:
+ *   the cost at g = 1 (B, G, R), the cost at the unclamped solution (B, G, R) (COMMON: the one system's figure three
+ *   times), the usable links, the frames with at least one usable link, and the end reason NM_EXPOSURE_END_OK, _NO_LINK
+ *   (no usable link) or _SINGULAR (a failed pivot or a non-finite solution). On NO_LINK and SINGULAR all gains are 1 and
+ *   the second three costs repeat the first three. No output is ever NaN.
+ *   Returns hipErrorInvalidValue, touching no device memory, for n not in [1, 64], L not in [1, 256], a NULL link_a, link_b,
+ *   sums, gains or stats, a link index outside [0, n) or a link with a == b, min_pixels < 1, sigma_n or sigma_g outside
+ *   [NM_EXPOSURE_SIGMA_MIN, NM_EXPOSURE_SIGMA_MAX] (a NaN included; inside it no term can overflow), g_min or g_max not
+ *   finite, g_min <= 0, g_min > 1, g_max < 1, or an unknown mode.
+ * nm_mosaic_gains_host: the same with every pointer in host memory, compiled from the same functions: identical bit for bit.
+ *
+ * nm_transform_blend_batch_gain (apply): nm_transform_blend_batch above with gains (device, n x 3 fp32, or NULL). The blend
+ * step of frame k becomes blend_sample, then r[c] = r[c] * gains[3 k + c] for c = 0, 1, 2 (one fp32 multiply each), then
+ * blend_combine (csrc/nm_warp_math.hpp). Weights, mask, alpha and canvas_wts are untouched: canvas_wts equals the ungained
+ * call's for any gains. nm_u8_sat does the clipping: on a canvas pixel of weight 0 the stored byte is
+ * nm_u8_sat(r[c] g 255.9999f), so a gain of 0 stores 0 (what a black frame would, on every pixel) and a byte is 255 as soon as
+ * r[c] g 255.9999f >= 255; gains are not range-checked (a negative or NaN product stores 0 there). One launch; each
+ * canvas pixel is read once and written at most once. With gains == NULL, or every gain exactly 1.0f, canvas and canvas_wts
+ * equal nm_transform_blend_batch's bit for bit (x * 1.0f == x). The refusals are nm_transform_blend_batch's.            */
+#define NM_EXPOSURE_MAX_LINKS 256
+#define NM_EXPOSURE_SUMS 7
+#define NM_EXPOSURE_STATS 9
+#define NM_EXPOSURE_PER_CHANNEL 0
+#define NM_EXPOSURE_COMMON 1
+#define NM_EXPOSURE_END_OK 0
+#define NM_EXPOSURE_END_NO_LINK 1
+#define NM_EXPOSURE_END_SINGULAR 2
+#define NM_EXPOSURE_SIGMA_MIN 1e-6
+#define NM_EXPOSURE_SIGMA_MAX 1e6
+NM_API int nm_mosaic_exposure_sums_dev(int n, int L, const unsigned char *const *frames, const int *link_a,
+                                       const int *link_b, int fw, int fh, const float *mask, const float *H,
+                                       const int *link_status, int stride, int lo, int hi, unsigned long long *sums,
+                                       void *stream);
+NM_API int nm_mosaic_exposure_sums_host(int n, int L, const unsigned char *const *frames, const int *link_a,
+                                        const int *link_b, int fw, int fh, const float *mask, const float *H,
+                                        const int *link_status, int stride, int lo, int hi, unsigned long long *sums);
+NM_API int nm_mosaic_gains_dev(int n, int L, const int *link_a, const int *link_b, const unsigned long long *sums,
+                               const int *link_status, int min_pixels, double sigma_n, double sigma_g, float g_min,
+                               float g_max, int mode, float *gains, double *stats, void *stream);
+NM_API int nm_mosaic_gains_host(int n, int L, const int *link_a, const int *link_b, const unsigned long long *sums,
+                                const int *link_status, int min_pixels, double sigma_n, double sigma_g, float g_min,
+                                float g_max, int mode, float *gains, double *stats);
+NM_API int nm_transform_blend_batch_gain(unsigned char *canvas, int cw, int ch, float *canvas_wts, int n,
+                                         const unsigned char *const *frames, int fw, int fh, const void *const *masks,
+                                         int mask_format, const void *const *wts, int wts_format,
+                                         const nm_mosaic_record *records, const float *gains, void *stream);
+
 /* ---- Link proposal: which frame pairs of a sequence to link at all (no reference counterpart). Two steps, both on
  * `stream` with no allocation, no synchronisation and no host read -- capturable into a HIP graph.
  * nm_link_votes_dev_u8: the u8 matcher's ratio test for ALL ordered pairs of n in [1, NM_LINK_PROPOSE_MAX_FRAMES] frames,

@@ -151,6 +151,11 @@ _SIGNATURES = {
     "nm_mosaic_adjust_host_f32": (_I, [_I, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, C.c_double,
                                        C.c_double, _P, _P, _P, _P]),
     "nm_mosaic_adjust_sums_host_f32": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
+    "nm_mosaic_exposure_sums_dev": (_I, [_I, _I, _P, _P, _P, _I, _I, _P, _P, _P, _I, _I, _I, _P, _P]),
+    "nm_mosaic_exposure_sums_host": (_I, [_I, _I, _P, _P, _P, _I, _I, _P, _P, _P, _I, _I, _I, _P]),
+    "nm_mosaic_gains_dev": (_I, [_I, _I, _P, _P, _P, _P, _I, C.c_double, C.c_double, _F, _F, _I, _P, _P, _P]),
+    "nm_mosaic_gains_host": (_I, [_I, _I, _P, _P, _P, _P, _I, C.c_double, C.c_double, _F, _F, _I, _P, _P]),
+    "nm_transform_blend_batch_gain": (_I, [_P, _I, _I, _P, _I, _P, _I, _I, _P, _I, _P, _I, _P, _P, _P]),
     "nm_link_votes_workspace_bytes": (_SZ, [_I, _I]),
     "nm_link_votes_dev_u8": (_I, [_I, _P, _P, _I, _F, _P, _P, _P]),
     "nm_link_votes_host_u8": (_I, [_I, _P, _P, _I, _F, _P]),
@@ -1770,6 +1775,21 @@ def transform_blend_batch(canvas, canvas_wts, frames, masks, wts, records):
     bits as transform_blend(canvas, canvas_wts, frames[k], nw_k, nh_k, m_k, tx_k, ty_k, masks[k], wts[k]) for k in order,
     with the fields of records[k] (int32 device (n, 16), e.g. from mosaic_plan). masks / wts: one scalar plane for every
     frame, or a list of n planes of one format."""
+    _blend_batch("nm_transform_blend_batch", canvas, canvas_wts, frames, masks, wts, records, ())
+
+
+def transform_blend_batch_gain(canvas, canvas_wts, frames, masks, wts, records, gains=None):
+    """transform_blend_batch with frame k's B, G, R multiplied by gains[k] (float32 device (n, 3), e.g. mosaic_gains') between
+    the sample and the blend (nm_transform_blend_batch_gain), one launch. canvas_wts is the ungained call's; with gains None
+    or all 1 so is the canvas, bit for bit."""
+    torch = _torch()
+    if gains is not None and (tuple(gains.shape) != (len(frames), 3) or gains.device != canvas.device):
+        raise NmError("transform_blend_batch_gain: gains must be float32 (n, 3) on the canvas' device")
+    _blend_batch("nm_transform_blend_batch_gain", canvas, canvas_wts, frames, masks, wts, records,
+                 (_dev(gains, torch.float32) if gains is not None else None,))
+
+
+def _blend_batch(entry, canvas, canvas_wts, frames, masks, wts, records, extra):
     torch = _torch()
     n = len(frames)
     if not 0 < n <= MOSAIC_MAX_BATCH:
@@ -1798,10 +1818,9 @@ def transform_blend_batch(canvas, canvas_wts, frames, masks, wts, records):
     if any(t.device != device for t in tensors) or device.type != "cuda" or torch.cuda.current_device() != device.index:
         raise NmError("transform_blend_batch: all tensors must live on the current device")
     arr = lambda vals: (C.c_void_p * n)(*vals)
-    _check(lib().nm_transform_blend_batch(_dev(canvas, torch.uint8), cw, ch, _dev(canvas_wts, torch.float32), n,
-                                          arr([_dev(f, torch.uint8) for f in frames]), fw, fh,
-                                          arr([_dev(t) for t in masks]), mfmt, arr([_dev(t) for t in wts]), wfmt,
-                                          _dev(records, torch.int32), _stream()), "nm_transform_blend_batch")
+    _check(getattr(lib(), entry)(_dev(canvas, torch.uint8), cw, ch, _dev(canvas_wts, torch.float32), n,
+                                 arr([_dev(f, torch.uint8) for f in frames]), fw, fh, arr([_dev(t) for t in masks]), mfmt,
+                                 arr([_dev(t) for t in wts]), wfmt, _dev(records, torch.int32), *extra, _stream()), entry)
 
 
 def mosaic_place(chain, fw, fh, cw, ch, ox, oy, frame_status=None):
@@ -1964,6 +1983,154 @@ def mosaic_adjust_sums_host(src_x, src_y, nA, dst_x, dst_y, matches, fw, fh, Ga,
     _check(lib().nm_mosaic_adjust_sums_host_f32(ptr(sx), ptr(sy), int(nA), capA, ptr(dx), ptr(dy), ptr(mt), ptr(mask), fw, fh,
                                                 ptr(Ga), ptr(Gb), ptr(sums), C.byref(count)), "nm_mosaic_adjust_sums_host_f32")
     return sums, count.value
+
+
+EXPOSURE_MAX_LINKS, EXPOSURE_SUMS = MOSAIC_ADJUST_MAX_LINKS, 7
+EXPOSURE_PER_CHANNEL, EXPOSURE_COMMON = 0, 1
+EXPOSURE_STATS = ("cost_unit_b", "cost_unit_g", "cost_unit_r", "cost_b", "cost_g", "cost_r", "links", "frames", "end")
+EXPOSURE_END_OK, EXPOSURE_END_NO_LINK, EXPOSURE_END_SINGULAR = range(3)
+EXPOSURE_SIGMA_MIN, EXPOSURE_SIGMA_MAX = 1e-6, 1e6
+
+
+def _exposure_links(n, link_a, link_b):
+    L = len(link_a)
+    if not 1 <= n <= MOSAIC_MAX_BATCH or not 1 <= L <= EXPOSURE_MAX_LINKS or len(link_b) != L:
+        raise NmError("mosaic exposure: n in [1, %d] frames and two link lists of one length in [1, %d] expected"
+                      % (MOSAIC_MAX_BATCH, EXPOSURE_MAX_LINKS))
+    if any(not (0 <= int(a) < n and 0 <= int(b) < n and int(a) != int(b)) for a, b in zip(link_a, link_b)):
+        raise NmError("mosaic exposure: a link joins two different frames in [0, n)")
+    return L, (C.c_int * L)(*[int(a) for a in link_a]), (C.c_int * L)(*[int(b) for b in link_b])
+
+
+def _exposure_sums_check(n, link_a, link_b, fw, fh, stride, lo, hi):
+    L, la, lb = _exposure_links(n, link_a, link_b)
+    if not (1 <= fw <= _MOSAIC_SIZE_LIMIT and 1 <= fh <= _MOSAIC_SIZE_LIMIT):
+        raise NmError("mosaic exposure: frame %r x %r outside [1, %d]" % (fw, fh, _MOSAIC_SIZE_LIMIT))
+    if any(int(v) != v for v in (stride, lo, hi)) or not 1 <= stride <= 64 or not 0 <= lo <= hi <= 255:
+        raise NmError("mosaic exposure: stride in [1, 64] and bytes 0 <= lo <= hi <= 255 expected")
+    return L, la, lb
+
+
+def _exposure_gains_check(n, link_a, link_b, min_pixels, sigma_n, sigma_g, g_min, g_max, mode):
+    L, la, lb = _exposure_links(n, link_a, link_b)
+    if int(min_pixels) != min_pixels or min_pixels < 1:
+        raise NmError("mosaic exposure: min_pixels %r must be an integer >= 1" % (min_pixels,))
+    if not all(EXPOSURE_SIGMA_MIN <= s <= EXPOSURE_SIGMA_MAX for s in (sigma_n, sigma_g)):
+        raise NmError("mosaic exposure: sigma_n and sigma_g lie in [%g, %g]" % (EXPOSURE_SIGMA_MIN, EXPOSURE_SIGMA_MAX))
+    if not (math.isfinite(g_min) and math.isfinite(g_max) and 0 < g_min <= 1 <= g_max):
+        raise NmError("mosaic exposure: 0 < g_min <= 1 <= g_max, both finite, expected")
+    if mode not in (EXPOSURE_PER_CHANNEL, EXPOSURE_COMMON):
+        raise NmError("mosaic exposure: unknown mode %r" % (mode,))
+    return L, la, lb
+
+
+def mosaic_exposure_sums(frames, link_a, link_b, H, link_status=None, mask=None, stride=4, lo=5, hi=250, sums=None):
+    """Per-link, per-channel overlap sums of n = len(frames) <= 64 BGRA frames over L = len(link_a) <= 256 links
+    (nm_mosaic_exposure_sums_dev): one memset node and one launch on the current stream, no host read. frames: uint8 device
+    (fh, fw, 4), tensors may repeat; link_a, link_b: host ints; H float32 device (L, 9) or (L, 3, 3), H_l mapping frame
+    link_a[l] to frame link_b[l]; link_status int32 device (L,) or None; mask float32 device (fh, fw) or None; a pixel counts
+    when its three bytes and the twelve tap bytes lie in [lo, hi]. sums: an int64 device tensor of L x 7 to write into
+    (default: new). Returns it as (L, 7): N, Sa_B, Sa_G, Sa_R, Sb_B, Sb_G, Sb_R (unsigned 64-bit values below 2^63)."""
+    torch = _torch()
+    n = len(frames)
+    fh, fw = (frames[0].shape[0], frames[0].shape[1]) if n else (0, 0)
+    L, la, lb = _exposure_sums_check(n, link_a, link_b, fw, fh, stride, lo, hi)
+    if any(f.dim() != 3 or tuple(f.shape) != (fh, fw, 4) for f in frames):
+        raise NmError("mosaic exposure: frames must all be (fh, fw, 4) uint8")
+    if H.numel() != 9 * L or (link_status is not None and link_status.numel() != L) or \
+            (mask is not None and tuple(mask.shape) != (fh, fw)):
+        raise NmError("mosaic exposure: H L x 9, link_status L values and mask (fh, fw) expected")
+    if sums is None:
+        sums = torch.empty((L, EXPOSURE_SUMS), dtype=torch.int64, device=frames[0].device)
+    if sums.numel() != L * EXPOSURE_SUMS:
+        raise NmError("mosaic exposure: sums must hold L x 7 values")
+    _on_current_device(list(frames) + [H, sums] + [t for t in (link_status, mask) if t is not None], "mosaic_exposure_sums")
+    opt = lambda t, dt: _dev(t, dt) if t is not None else None
+    _check(lib().nm_mosaic_exposure_sums_dev(n, L, (C.c_void_p * n)(*[_dev(f, torch.uint8) for f in frames]), la, lb, fw, fh,
+                                             opt(mask, torch.float32), _dev(H, torch.float32), opt(link_status, torch.int32),
+                                             int(stride), int(lo), int(hi), _dev(sums, torch.int64), _stream()),
+           "nm_mosaic_exposure_sums_dev")
+    return sums.view(L, EXPOSURE_SUMS)
+
+
+def mosaic_exposure_sums_host(frames, link_a, link_b, H, link_status=None, mask=None, stride=4, lo=5, hi=250):
+    """mosaic_exposure_sums on the host (nm_mosaic_exposure_sums_host, the same functions): numpy in and out, identical
+    results. Returns uint64 (L, 7)."""
+    import numpy as np
+    frames = [np.ascontiguousarray(f, dtype=np.uint8) for f in frames]
+    n = len(frames)
+    fh, fw = (frames[0].shape[0], frames[0].shape[1]) if n else (0, 0)
+    L, la, lb = _exposure_sums_check(n, link_a, link_b, fw, fh, stride, lo, hi)
+    if any(f.shape != (fh, fw, 4) for f in frames):
+        raise NmError("mosaic exposure: frames must all be (fh, fw, 4) uint8")
+    H = np.ascontiguousarray(H, dtype=np.float32).reshape(-1)
+    link_status = None if link_status is None else np.ascontiguousarray(link_status, dtype=np.int32).reshape(-1)
+    mask = None if mask is None else np.ascontiguousarray(mask, dtype=np.float32)
+    if H.size != 9 * L or (link_status is not None and link_status.size != L) or (mask is not None and mask.shape != (fh, fw)):
+        raise NmError("mosaic exposure: H L x 9, link_status L values and mask (fh, fw) expected")
+    sums = np.zeros((L, EXPOSURE_SUMS), np.uint64)
+    ptr = _pair_host_ptr
+    _check(lib().nm_mosaic_exposure_sums_host(n, L, _pair_host_table(frames), la, lb, fw, fh, ptr(mask), ptr(H),
+                                              ptr(link_status), int(stride), int(lo), int(hi), ptr(sums)),
+           "nm_mosaic_exposure_sums_host")
+    return sums
+
+
+def mosaic_gains(n, link_a, link_b, sums, link_status=None, min_pixels=64, sigma_n=10.0, sigma_g=0.1, g_min=0.25, g_max=4.0,
+                 mode=EXPOSURE_PER_CHANNEL, gains=None, stats=None):
+    """Per-frame, per-channel gains of n frames from the links' overlap sums (nm_mosaic_gains_dev): one launch of one
+    workgroup on the current stream, no host read. sums: int64 device (L, 7) of mosaic_exposure_sums; link_status int32 device
+    (L,) or None; sigma_n in byte levels. gains / stats: float32 (n, 3) / float64 (9,) device tensors to write into (default:
+    new). Returns (gains[n, 3] in B, G, R order, stats[9] in the order of EXPOSURE_STATS, its last entry one of
+    EXPOSURE_END_*). gains goes to transform_blend_batch_gain as it is."""
+    torch = _torch()
+    L, la, lb = _exposure_gains_check(n, link_a, link_b, min_pixels, sigma_n, sigma_g, g_min, g_max, mode)
+    if sums.numel() != L * EXPOSURE_SUMS or (link_status is not None and link_status.numel() != L):
+        raise NmError("mosaic exposure: sums L x 7 and link_status L values expected")
+    if gains is None:
+        gains = torch.empty((n, 3), dtype=torch.float32, device=sums.device)
+    if stats is None:
+        stats = torch.empty(len(EXPOSURE_STATS), dtype=torch.float64, device=sums.device)
+    if gains.numel() != 3 * n or stats.numel() != len(EXPOSURE_STATS):
+        raise NmError("mosaic exposure: gains must hold n x 3 values and stats %d" % len(EXPOSURE_STATS))
+    _on_current_device([sums, gains, stats] + ([link_status] if link_status is not None else []), "mosaic_gains")
+    _check(lib().nm_mosaic_gains_dev(n, L, la, lb, _dev(sums, torch.int64),
+                                     _dev(link_status, torch.int32) if link_status is not None else None, int(min_pixels),
+                                     float(sigma_n), float(sigma_g), float(g_min), float(g_max), int(mode),
+                                     _dev(gains, torch.float32), _dev(stats, torch.float64), _stream()), "nm_mosaic_gains_dev")
+    return gains.view(n, 3), stats
+
+
+def mosaic_gains_host(n, link_a, link_b, sums, link_status=None, min_pixels=64, sigma_n=10.0, sigma_g=0.1, g_min=0.25,
+                      g_max=4.0, mode=EXPOSURE_PER_CHANNEL):
+    """mosaic_gains on the host (nm_mosaic_gains_host, the same functions in the same order): numpy in and out, bit-identical
+    results."""
+    import numpy as np
+    L, la, lb = _exposure_gains_check(n, link_a, link_b, min_pixels, sigma_n, sigma_g, g_min, g_max, mode)
+    sums = np.ascontiguousarray(sums).astype(np.uint64, copy=False).reshape(-1)
+    link_status = None if link_status is None else np.ascontiguousarray(link_status, dtype=np.int32).reshape(-1)
+    if sums.size != L * EXPOSURE_SUMS or (link_status is not None and link_status.size != L):
+        raise NmError("mosaic exposure: sums L x 7 and link_status L values expected")
+    gains = np.zeros((n, 3), np.float32)
+    stats = np.zeros(len(EXPOSURE_STATS), np.float64)
+    ptr = _pair_host_ptr
+    _check(lib().nm_mosaic_gains_host(n, L, la, lb, ptr(sums), ptr(link_status), int(min_pixels), float(sigma_n),
+                                      float(sigma_g), float(g_min), float(g_max), int(mode), ptr(gains), ptr(stats)),
+           "nm_mosaic_gains_host")
+    return gains, stats
+
+
+def mosaic_exposure(frames, link_a, link_b, H, link_status=None, mask=None, stride=4, lo=5, hi=250, min_pixels=64,
+                    sigma_n=10.0, sigma_g=0.1, g_min=0.25, g_max=4.0, mode=EXPOSURE_PER_CHANNEL, sums=None, gains=None,
+                    stats=None):
+    """Exposure gains of a mosaic's frames: mosaic_exposure_sums, then mosaic_gains, one memset node and two launches on the
+    current stream and no host read. Returns (gains, stats, sums), all device tensors."""
+    _exposure_gains_check(len(frames), link_a, link_b, min_pixels, sigma_n, sigma_g, g_min, g_max, mode)
+    sums = mosaic_exposure_sums(frames, link_a, link_b, H, link_status=link_status, mask=mask, stride=stride, lo=lo, hi=hi,
+                                sums=sums)
+    gains, stats = mosaic_gains(len(frames), link_a, link_b, sums, link_status=link_status, min_pixels=min_pixels,
+                                sigma_n=sigma_n, sigma_g=sigma_g, g_min=g_min, g_max=g_max, mode=mode, gains=gains, stats=stats)
+    return gains, stats, sums
 
 
 LINK_PROPOSE_MAX_FRAMES = _PAIR_MAX_BATCH

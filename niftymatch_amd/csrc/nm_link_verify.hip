@@ -34,22 +34,6 @@ struct FrameTables {                        // 2 x 64 pointers, 1 KB of kernel a
     const float *b[nmp::MAX_BATCH];
 };
 
-// The workgroup's totals of the lanes' sums, valid in thread 0 .. SUMS - 1 (thread q holds sum q).
-__device__ __forceinline__ u64 block_total(u64 s[SUMS], u64 (*part)[SUMS])
-{
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-    for (int q = 0; q < SUMS; ++q) s[q] = nmw::wave_reduce(s[q], nmw::Sum());
-    if (lane == 0)
-#pragma unroll
-        for (int q = 0; q < SUMS; ++q) part[wave][q] = s[q];
-    __syncthreads();
-    u64 t = 0;
-    if (tid < SUMS)
-        for (int w = 0; w < WAVES; ++w) t += part[w][tid];
-    return t;
-}
-
 __global__ __launch_bounds__(THREADS) void link_verify_accumulate_kernel(const FrameTables T, int fw, int fh,
                                                                          const float *__restrict__ mask,
                                                                          const float *__restrict__ H,
@@ -71,7 +55,7 @@ __global__ __launch_bounds__(THREADS) void link_verify_accumulate_kernel(const F
             for (int r = wave; r < TILE_H && v0 + r < lh; r += WAVES)
                 add_pixel(F, Hk, stride * u + stride / 2, stride * (v0 + r) + stride / 2, s);
     }
-    const u64 total = block_total(s, part);
+    const u64 total = nmw::block_totals<WAVES>(s, part);
     if (tid < SUMS) partials[((size_t)k * MAX_PARTS + blockIdx.x) * PART_STRIDE + tid] = total;
 }
 
@@ -99,7 +83,7 @@ __global__ __launch_bounds__(THREADS) void link_verify_finalize_kernel(int fw, i
     for (int r = tid; r < parts; r += THREADS)
 #pragma unroll
         for (int q = 0; q < SUMS; ++q) s[q] += partials[((size_t)k * MAX_PARTS + r) * PART_STRIDE + q];
-    const u64 total = block_total(s, part);
+    const u64 total = nmw::block_totals<WAVES>(s, part);
     if (tid < SUMS) tot[tid] = total;
     __syncthreads();
     if (tid == 0) {

@@ -59,20 +59,29 @@ __host__ __device__ __forceinline__ bool level_of(float v, int &q)
 
 __host__ __device__ __forceinline__ bool mask_ok(const float *mask, size_t p) { return !mask || mask[p] > 0.5f; }
 
+// The projection half of lattice pixel (x, y), shared with the exposure sums (nm_mosaic_exposure_math.hpp): true when the
+// denominator is finite and positive, the sampler accepts the projection on a fw x fh frame and its four taps (i, j),
+// (i+1, j), (i, j+1), (i+1, j+1) lie inside it; w are the sampler's weights, multiples of 2^-16.
+__host__ __device__ __forceinline__ bool lattice_taps(const float H[9], int fw, int fh, int x, int y, int &i, int &j,
+                                                      float w[4])
+{
+    const float den = nmw::project_den(H, (float)x, (float)y);
+    if (!(__builtin_isfinite(den) && den > 0.f)) return false;
+    float xp, yp;
+    nmw::project(H, (float)x, (float)y, xp, yp);
+    const nmw::Tex tex{nullptr, fw, fh, NM_TEX_F32};
+    if (!nmw::tex_setup(tex, xp + 0.5f, yp + 0.5f, i, j, w)) return false;
+    return !(i < 0 || j < 0 || i + 1 >= fw || j + 1 >= fh);
+}
+
 // Lattice pixel (x, y) of A. 0: it counts nowhere; 1: into L; 2: into L and N, with its levels qa and qb.
 __host__ __device__ __forceinline__ int pixel(const Frames &F, const float H[9], int x, int y, int &qa, int &qb)
 {
     const size_t p = (size_t)y * F.fw + x;
     if (!mask_ok(F.mask, p) || !level_of(F.a[p], qa)) return 0;
-    const float den = nmw::project_den(H, (float)x, (float)y);
-    if (!(__builtin_isfinite(den) && den > 0.f)) return 1;
-    float xp, yp;
-    nmw::project(H, (float)x, (float)y, xp, yp);
     int i, j;
     float w[4];
-    const nmw::Tex tex{F.b, F.fw, F.fh, NM_TEX_F32};
-    if (!nmw::tex_setup(tex, xp + 0.5f, yp + 0.5f, i, j, w)) return 1;
-    if (i < 0 || j < 0 || i + 1 >= F.fw || j + 1 >= F.fh) return 1;
+    if (!lattice_taps(H, F.fw, F.fh, x, y, i, j, w)) return 1;
     unsigned acc = 32768u;
     for (int t = 0; t < 4; ++t) {
         const size_t q = (size_t)(j + (t >> 1)) * F.fw + (i + (t & 1));

@@ -11,6 +11,8 @@
 //         pixels per wave. A wave ballots the frames whose rectangle meets its row (a wave-uniform 64-bit mask) and
 //         walks the set bits in index order; each lane runs transform_blend's per-pixel step (nm_warp_math.hpp) for
 //         every covering frame with the canvas pixel and weight in registers: one load, at most one store per pixel.
+//         nm_transform_blend_batch_gain is the same kernel body with a per-frame, per-channel gain on the frame's colour
+//         (the exposure compensation of nm_mosaic_exposure.hip), a compile-time switch.
 #include <climits>
 #include <cmath>
 
@@ -203,11 +205,16 @@ struct MbArgs {                                   // 3 x 64 pointers: 1.5 KB of 
 };
 static_assert(sizeof(MbArgs) + 64 < 4096, "blend kernel arguments exceed 4 KB");
 
+// GAIN: frame k's colour is multiplied by gains[3 k + c] between blend_sample and blend_combine (the gains staged in LDS
+// beside the records); without it the body is the ungained blend's, operation for operation.
+template <bool GAIN>
 __global__ __launch_bounds__(MB_THREADS) void transform_blend_batch_kernel(const MbArgs a, int n, uchar4 *__restrict__ canvas,
                                                                            int cw, int ch, float *__restrict__ canvas_wts,
                                                                            int fw, int fh, int mask_format, int wts_format,
-                                                                           const nm_mosaic_record *__restrict__ records)
+                                                                           const nm_mosaic_record *__restrict__ records,
+                                                                           const float *__restrict__ gains)
 {
+    __shared__ float s_gain[GAIN ? NM_MOSAIC_MAX_BATCH : 1][3];
     __shared__ float s_m[NM_MOSAIC_MAX_BATCH][9];
     __shared__ int2 s_t[NM_MOSAIC_MAX_BATCH];          // the records' tx, ty
     __shared__ int4 s_rect[NM_MOSAIC_MAX_BATCH];       // clipped (x0, y0, x1, y1); (0, 0, 0, 0) when empty
@@ -228,6 +235,8 @@ __global__ __launch_bounds__(MB_THREADS) void transform_blend_batch_kernel(const
             s_ptr[0][tid] = a.frames[tid];
             s_ptr[1][tid] = a.masks[tid];
             s_ptr[2][tid] = a.wts[tid];
+            if (GAIN)
+                for (int c = 0; c < 3; ++c) s_gain[tid][c] = gains[3 * tid + c];
         }
         s_rect[tid] = r;
         const bool empty = r.z == 0;                   // x1 > x0 >= 0 for every non-empty rectangle
@@ -264,6 +273,9 @@ __global__ __launch_bounds__(MB_THREADS) void transform_blend_batch_kernel(const
             wts.data = s_ptr[2][k]; wts.fmt = wts_format;
             float rgb[4], nwt;
             if (!blend_sample(s_m[k], frame, mask, wts, px - t0.x, row - t0.y, rgb, nwt)) continue;
+            if (GAIN) {
+                rgb[0] = rgb[0] * s_gain[k][0]; rgb[1] = rgb[1] * s_gain[k][1]; rgb[2] = rgb[2] * s_gain[k][2];
+            }
             if (!have) {
                 cwt = canvas_wts[idx];
                 c = canvas[idx];
@@ -347,9 +359,10 @@ int nm_mosaic_place_f32(int n, const float *chain, const int *frame_status, int 
     return 0;
 }
 
-int nm_transform_blend_batch(unsigned char *canvas, int cw, int ch, float *canvas_wts, int n,
-                             const unsigned char *const *frames, int fw, int fh, const void *const *masks, int mask_format,
-                             const void *const *wts, int wts_format, const nm_mosaic_record *records, void *stream)
+int nm_transform_blend_batch_gain(unsigned char *canvas, int cw, int ch, float *canvas_wts, int n,
+                                  const unsigned char *const *frames, int fw, int fh, const void *const *masks,
+                                  int mask_format, const void *const *wts, int wts_format, const nm_mosaic_record *records,
+                                  const float *gains, void *stream)
 {
     const auto scalar_fmt = [](int f) { return f == NM_TEX_U8N || f == NM_TEX_F32; };
     if (n < 1 || n > NM_MOSAIC_MAX_BATCH || cw < 1 || cw > MP_LIMIT || ch < 1 || ch > MP_LIMIT || fw < 1 || fh < 1 ||
@@ -368,10 +381,19 @@ int nm_transform_blend_batch(unsigned char *canvas, int cw, int ch, float *canva
     const long long canvas_tiles = (long long)nm_divup(cw, MB_TILE_W) * nm_divup(ch, MB_TILE_H);
     const long long fill = (long long)nm_cu_count() * MB_BLOCKS_PER_CU;
     const int grid = (int)(canvas_tiles < fill ? canvas_tiles : fill);
-    hipLaunchKernelGGL(transform_blend_batch_kernel, dim3(grid), dim3(MB_THREADS), 0, nm_stream(stream), a, n,
-                       reinterpret_cast<uchar4 *>(canvas), cw, ch, canvas_wts, fw, fh, mask_format, wts_format, records);
+    const auto kernel = gains ? transform_blend_batch_kernel<true> : transform_blend_batch_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(MB_THREADS), 0, nm_stream(stream), a, n,
+                       reinterpret_cast<uchar4 *>(canvas), cw, ch, canvas_wts, fw, fh, mask_format, wts_format, records, gains);
     NM_LAUNCH_CHECK();
     return 0;
+}
+
+int nm_transform_blend_batch(unsigned char *canvas, int cw, int ch, float *canvas_wts, int n,
+                             const unsigned char *const *frames, int fw, int fh, const void *const *masks, int mask_format,
+                             const void *const *wts, int wts_format, const nm_mosaic_record *records, void *stream)
+{
+    return nm_transform_blend_batch_gain(canvas, cw, ch, canvas_wts, n, frames, fw, fh, masks, mask_format, wts, wts_format,
+                                         records, nullptr, stream);
 }
 
 }  // extern "C"

@@ -20,6 +20,7 @@
 #include <cmath>
 #include <vector>
 
+#include "nm_chol_math.hpp"
 #include "nm_common.hpp"
 #include "nm_mosaic_adjust_math.hpp"
 #include "nm_pair_batch.hpp"
@@ -112,9 +113,8 @@ __global__ __launch_bounds__(LANES) void mosaic_adjust_solve_kernel(const Params
                                                                     const double *__restrict__ rows, double *M, Small *W,
                                                                     const Out O)
 {
-    __shared__ double s_row[LANES], s_x[LANES];
-    __shared__ double s_piv;
-    __shared__ int s_go, s_singular;
+    __shared__ nmc::CholShared<LANES> s_chol;
+    __shared__ int s_go;
     __shared__ LinkIdx s_X;                                      // indexed at run time: out of the kernel arguments
     const int tid = threadIdx.x;
     if (tid < MAX_LINKS) { s_X.a[tid] = Xarg.a[tid]; s_X.b[tid] = Xarg.b[tid]; }
@@ -122,7 +122,6 @@ __global__ __launch_bounds__(LANES) void mosaic_adjust_solve_kernel(const Params
     const LinkIdx &X = s_X;
     if (tid == 0) {
         s_go = begin_round(P, t, X, link_status, chain_in, rows, *W, O) ? 1 : 0;
-        s_singular = 0;
     }
     __syncthreads();
     if (!s_go) return;
@@ -155,46 +154,13 @@ __global__ __launch_bounds__(LANES) void mosaic_adjust_solve_kernel(const Params
         M[(size_t)tid * ld + tid] = d;
     }
     __syncthreads();
-    // Cholesky by columns; thread i owns row i, thread N the right-hand side
-    for (int j = 0; j < N; ++j) {
-        if (tid < j) s_row[tid] = M[(size_t)j * ld + tid];
-        __syncthreads();
-        double v = 0.0;
-        if (tid >= j && tid <= N) {
-            v = M[(size_t)j * ld + tid];
-#pragma unroll 8
-            for (int k = 0; k < j; ++k) v = fma_(-M[(size_t)k * ld + tid], s_row[k], v);
-        }
-        if (tid == j) {
-            if (!(v > 0.0 && __builtin_isfinite(v))) s_singular = 1;
-            s_piv = __builtin_sqrt(v);
-        }
-        __syncthreads();
-        if (s_singular) break;                                   // uniform
-        if (tid == j) {
-            M[(size_t)j * ld + j] = s_piv;
-        } else if (tid > j && tid <= N) {
-            const double q = v / s_piv;
-            M[(size_t)j * ld + tid] = q;
-            if (tid < N) M[(size_t)tid * ld + j] = q;
-        }
+    // Cholesky by columns; thread i owns row i, thread N the right-hand side (nm_chol_math.hpp)
+    const bool solved = nmc::chol_solve_block(M, ld, N, s_chol);
+    if (solved) {
+        if (tid < N) W->delta[tid] = s_chol.x[tid];
         __syncthreads();
     }
-    if (!s_singular) {
-        for (int i = N - 1; i >= 0; --i) {
-            if (tid > i && tid < N) s_row[tid] = M[(size_t)i * ld + tid];
-            __syncthreads();
-            if (tid == 0) {
-                double v = M[(size_t)i * ld + N];
-                for (int k = i + 1; k < N; ++k) v = fma_(-s_row[k], s_x[k], v);
-                s_x[i] = v / M[(size_t)i * ld + i];
-            }
-            __syncthreads();
-        }
-        if (tid < N) W->delta[tid] = s_x[tid];
-        __syncthreads();
-    }
-    if (tid == 0) finish_round(P, s_singular != 0, chain_in, *W, O);
+    if (tid == 0) finish_round(P, !solved, chain_in, *W, O);
 }
 
 // ---- the host twin: the same functions, the virtual lanes, the trees and the chains walked serially ----
@@ -247,28 +213,7 @@ bool host_solve(const Params &P, const LinkIdx &X, const double *rows, std::vect
         double d = M[(size_t)i * ld + i] * (1.0 + P.damping);
         M[(size_t)i * ld + i] = d == 0.0 ? 1.0 : d;
     }
-    for (int j = 0; j < N; ++j) {
-        double piv = 0.0;
-        for (int i = j; i <= N; ++i) {
-            double v = M[(size_t)j * ld + i];
-            for (int k = 0; k < j; ++k) v = fma_(-M[(size_t)k * ld + i], M[(size_t)j * ld + k], v);
-            if (i == j) {
-                if (!(v > 0.0 && std::isfinite(v))) return false;
-                piv = std::sqrt(v);
-                M[(size_t)j * ld + j] = piv;
-            } else {
-                const double q = v / piv;
-                M[(size_t)j * ld + i] = q;
-                if (i < N) M[(size_t)i * ld + j] = q;
-            }
-        }
-    }
-    for (int i = N - 1; i >= 0; --i) {
-        double v = M[(size_t)i * ld + N];
-        for (int k = i + 1; k < N; ++k) v = fma_(-M[(size_t)i * ld + k], W.delta[k], v);
-        W.delta[i] = v / M[(size_t)i * ld + i];
-    }
-    return true;
+    return nmc::chol_solve_serial(M.data(), ld, N, W.delta);
 }
 
 bool sizes_ok(int capA, int fw, int fh)

@@ -73,4 +73,23 @@ __device__ __forceinline__ int block_rank(bool flag, int *s_cnt, int &total)
     return before + lane_rank(m);
 }
 
+// The workgroup's totals of N per-lane sums, for a workgroup of WAVES waves; every thread calls it. Thread q < N returns
+// the total of sum q (the other threads return T()). part is the caller's T[WAVES][N] in LDS. Barriers: ONE, inside,
+// between the waves' writes of part and the reads. The wave step is the butterfly, the waves are added in ascending order.
+template <int WAVES, int N, class T>
+__device__ __forceinline__ T block_totals(T (&s)[N], T (*part)[N])
+{
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+    for (int q = 0; q < N; ++q) s[q] = wave_reduce(s[q], Sum());
+    if (lane == 0)
+#pragma unroll
+        for (int q = 0; q < N; ++q) part[wave][q] = s[q];
+    __syncthreads();
+    T t = T();
+    if (tid < N)
+        for (int w = 0; w < WAVES; ++w) t += part[w][tid];
+    return t;
+}
+
 }  // namespace nmw
