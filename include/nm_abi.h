@@ -1286,7 +1286,9 @@ NM_API int nm_mosaic_adjust_sums_host_f32(const float *src_x, const float *src_y
  * blend). All on `stream` with no allocation, no synchronisation, no host read and no workspace; no kernel waits for
  * another workgroup: measure -> solve -> place -> gained blend can be captured into one HIP graph.
  *
- * nm_mosaic_exposure_sums_dev (measure): n in [1, 64] frames, L in [1, NM_EXPOSURE_MAX_LINKS] links. frames: HOST table of n
+ * nm_mosaic_exposure_sums_dev (measure): n in [2, 64] frames, L in [1, NM_EXPOSURE_MAX_LINKS] links (a link joins two
+ * different frames and at least one link is required, so n = 1 is always refused: two frames and one link are the
+ * smallest input; the same holds for nm_mosaic_gains_dev). frames: HOST table of n
  * device pointers to fw x fh uchar4 (B, G, R, A) frames as the blend takes them; pointers may repeat. link_a, link_b: HOST
  * int arrays of L (the adjustment's convention), indices in [0, n), a != b. H: device, L x 9 fp32, H_l maps frame-a pixels
  * to frame-b pixels. mask: optional device fp32 plane fw x fh shared by all frames; a pixel is seen where mask > 0.5.
@@ -1304,7 +1306,7 @@ NM_API int nm_mosaic_adjust_sums_host_f32(const float *src_x, const float *src_y
  *   slot, the launch grouping or scheduling. A link with link_status[l] != 1 or a non-finite H_l gets seven zeros.
  *   ONE memset node (the sums) and ONE launch whatever L is: the frame pointers (512 B) and the link indices (512 B) travel
  *   as kernel arguments; a link's lattice tiles are dealt to up to 256 workgroups, each ending in one vector atomic add per
- *   sum. Returns hipErrorInvalidValue, touching no device memory, for n not in [1, 64], L not in [1, 256], fw or fh not in
+ *   sum. Returns hipErrorInvalidValue, touching no device memory, for n not in [2, 64], L not in [1, 256], fw or fh not in
  *   [1, 32767], stride not in [1, 64], (fw / stride)(fh / stride) > 2^28, lo < 0, lo > hi, hi > 255, a NULL frames, link_a,
  *   link_b, H or sums, a NULL among the first n frame pointers, a link index outside [0, n) or a link with a == b.
  * nm_mosaic_exposure_sums_host: the same with every pointer in host memory, compiled from the same functions
@@ -1332,7 +1334,7 @@ NM_API int nm_mosaic_adjust_sums_host_f32(const float *src_x, const float *src_y
  *   times), the usable links, the frames with at least one usable link, and the end reason NM_EXPOSURE_END_OK, _NO_LINK
  *   (no usable link) or _SINGULAR (a failed pivot or a non-finite solution). On NO_LINK and SINGULAR all gains are 1 and
  *   the second three costs repeat the first three. No output is ever NaN.
- *   Returns hipErrorInvalidValue, touching no device memory, for n not in [1, 64], L not in [1, 256], a NULL link_a, link_b,
+ *   Returns hipErrorInvalidValue, touching no device memory, for n not in [2, 64], L not in [1, 256], a NULL link_a, link_b,
  *   sums, gains or stats, a link index outside [0, n) or a link with a == b, min_pixels < 1, sigma_n or sigma_g outside
  *   [NM_EXPOSURE_SIGMA_MIN, NM_EXPOSURE_SIGMA_MAX] (a NaN included; inside it no term can overflow), g_min or g_max not
  *   finite, g_min <= 0, g_min > 1, g_max < 1, or an unknown mode.

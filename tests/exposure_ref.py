@@ -39,9 +39,10 @@ PER_CHANNEL, COMMON = 0, 1
 END_OK, END_NO_LINK, END_SINGULAR = 0, 1, 2
 
 
-def sums_int(A, B, H, mask=None, stride=4, lo=5, hi=250, a_only=False):
+def sums_int(A, B, H, mask=None, stride=4, lo=5, hi=250, a_only=False, counted=None):
     """The seven sums (Python ints) N, Sa_B, Sa_G, Sa_R, Sb_B, Sb_G, Sb_R of one link: A, B uint8 (fh, fw, 4), H maps A
-    pixels to B pixels. a_only is a MUTANT: the range test on frame A's bytes only."""
+    pixels to B pixels. a_only is a MUTANT: the range test on frame A's bytes only. counted: a list that receives the bool
+    array (lh, lw) of the lattice pixels that count (nothing for a non-finite H or an empty lattice)."""
     A, B = np.asarray(A, np.uint8), np.asarray(B, np.uint8)
     fh, fw = A.shape[:2]
     H = np.asarray(H, F32).reshape(9)
@@ -76,6 +77,8 @@ def sums_int(A, B, H, mask=None, stride=4, lo=5, hi=250, a_only=False):
             ok &= ((pt >= lo) & (pt <= hi)).all(axis=1)
         acc += w[:, None] * pt
     pb = acc >> 16
+    if counted is not None:
+        counted.append(ok.reshape(fh // stride, fw // stride))
     return [int(ok.sum())] + [int(v) for v in pa[ok].sum(axis=0)] + [int(v) for v in pb[ok].sum(axis=0)]
 
 
