@@ -1376,6 +1376,67 @@ NM_API int nm_transform_blend_batch_gain(unsigned char *canvas, int cw, int ch, 
                                          int mask_format, const void *const *wts, int wts_format,
                                          const nm_mosaic_record *records, const float *gains, void *stream);
 
+/* ---- Two-band mosaic blend (no reference counterpart): the step after gain compensation in Brown & Lowe's pipeline. Low
+ * frequencies are mixed smoothly across a seam, high frequencies come from ONE frame, the one of largest weight.
+ * Everything runs on `stream` with no allocation, no synchronisation and no host read, no kernel waits
+ * for another workgroup, the launch count does not depend on n: capturable into a HIP graph behind nm_mosaic_place_f32 and
+ * nm_mosaic_gains_dev.
+ *
+ * DEFINITION. For frame k with a placed record (m, tx, ty, nw, nh) and local pixel (x, y), 0 <= x < nw, 0 <= y < nh:
+ *   ok, r, w = blend_sample(m, frame k, mask k, weights k, x, y), exactly as the batched blend calls it
+ *   (csrc/nm_warp_math.hpp); C_k[c] = r[c] * gains[3 k + c] for c = 0, 1, 2 (one fp32 multiply, as in the gained blend; no
+ *   multiply when gains == NULL); the validity is v_k = ok && w > 0; where v_k is false, C_k = 0 and w_k = 0. A frame is
+ *   USED when it is placed, nw > 0, nh > 0 and nw * nh (in 64-bit) <= tile_cap; every other frame is skipped, everywhere.
+ *   The tile of a used frame holds (C_B, C_G, C_R, w) for EVERY local pixel, on the canvas or not.
+ *   Label. For each canvas pixel inside at least one used rectangle, k* is the used frame with the largest w_k there,
+ *   ties to the lowest index; "none" when no frame is valid there. I_k = (k* == k); I_k = 0 off the canvas.
+ *   Low band. g[0..R], R in [0, NM_BANDS_MAX_RADIUS]: t_i = exp(-i^2 / (2 sigma^2)), S = t_0 + 2 (t_1 + .. + t_R) summed in
+ *   ascending i, g[i] = (float)(t_i / S), all in double on the HOST (nm_mosaic_bands_taps returns them); the taps travel
+ *   as kernel arguments and exp is never evaluated on the device. Per frame, five planes are blurred over its own
+ *   nw x nh rectangle with zeros outside it, rows first, then columns:  L_k = g * (v_k C_k) (three channels),
+ *   V_k = g * v_k,  M_k = g * I_k. One pass of one plane s at one pixel is (csrc/nm_mosaic_bands_math.hpp, tap_sum)
+ *       acc = g[0] s(0);  for i = 1 .. R:  acc = fma(g[i], s(-i) + s(i), acc)
+ *   in fp32, nothing left to contraction. l_k = L_k / V_k where v_k holds (V_k >= g[0]^2 > 0 there).
+ *   Compose. For a labelled canvas pixel, over the used frames valid at that pixel (v_k) in index order, k* included:
+ *       num_c = fma(M_k, l_k,c - l_k*,c, num_c),  den = den + M_k      (both from 0)
+ *       out_c = C_k*,c + num_c / den;   the stored byte is nm_u8_sat(out_c * 255.9999f), alpha 255
+ *   canvas_wts, if given, receives w_k*. Unlabelled pixels (and every pixel outside all used rectangles) keep their bytes
+ *   and their weight; a labelled pixel is overwritten, not accumulated into. den > 0 wherever a label exists (the centre
+ *   taps). Where only one frame has M_k > 0 (single coverage, or more than R pixels, in both axes' maximum norm, from any
+ *   label change inside the frame) num is exactly 0 and the pixel is that frame's own sample bit for bit; R = 0 is exact
+ *   winner-take-all.
+ *
+ * nm_mosaic_warp_tiles (device only, ONE launch): frames, masks, wts (HOST tables of n device pointers), fw, fh, the
+ *   formats, records and gains (device; gains may be NULL) as nm_transform_blend_batch_gain takes them. tiles: device,
+ *   16-byte aligned, n x tile_cap x 4 floats; frame k owns the slot at k * tile_cap pixels, pixel (x, y) at y * nw + x;
+ *   nothing is written outside a used frame's first nw * nh pixels, nothing at all for a skipped frame. stats: device,
+ *   NM_BANDS_STATS ints: used frames, skipped frames.
+ *   Refused with hipErrorInvalidValue before any device memory is touched: n outside [1, NM_MOSAIC_MAX_BATCH], fw or fh
+ *   outside [1, 32767], a format other than NM_TEX_U8N / NM_TEX_F32, tile_cap outside [1, 2^30], a NULL table, table
+ *   entry, records, tiles or stats, tiles not 16-byte aligned.
+ * nm_mosaic_bands_dev (label, row blur, column blur, compose: FOUR launches whatever n is, no memset node): tiles and
+ *   records as above; canvas uchar4 cw x ch, cw and ch in [1, 32767]; canvas_wts fp32 cw x ch or NULL; R, sigma (sigma
+ *   is not read when R == 0). workspace: device, 16-byte aligned, nm_mosaic_bands_workspace_bytes(n, tile_cap, cw, ch)
+ *   bytes (0 out of range), any contents: the label plane (one byte per canvas pixel, rounded up to 256 bytes), then
+ *   2 x n x tile_cap x 20 bytes of blurred planes.
+ *   Refused the same way: n, tile_cap, cw or ch out of range, R outside [0, NM_BANDS_MAX_RADIUS], R > 0 with a sigma that
+ *   is not finite and positive, a NULL tiles, records, canvas or workspace, tiles or workspace not 16-byte aligned.
+ * nm_mosaic_bands_host: the same with every pointer in host memory, compiled from the same functions: canvas and
+ *   canvas_wts identical to the device's bit for bit. The warp launch has no host twin (the sampler is device code).   */
+#define NM_BANDS_MAX_RADIUS 32
+#define NM_BANDS_STATS 2
+NM_API size_t nm_mosaic_bands_workspace_bytes(int n, long long tile_cap, int cw, int ch);
+NM_API int nm_mosaic_bands_taps(int R, double sigma, float *g);
+NM_API int nm_mosaic_warp_tiles(int n, const unsigned char *const *frames, int fw, int fh, const void *const *masks,
+                                int mask_format, const void *const *wts, int wts_format, const nm_mosaic_record *records,
+                                const float *gains, float *tiles, long long tile_cap, int *stats, void *stream);
+NM_API int nm_mosaic_bands_dev(int n, const float *tiles, long long tile_cap, const nm_mosaic_record *records,
+                               unsigned char *canvas, int cw, int ch, float *canvas_wts, int R, double sigma,
+                               void *workspace, void *stream);
+NM_API int nm_mosaic_bands_host(int n, const float *tiles, long long tile_cap, const nm_mosaic_record *records,
+                                unsigned char *canvas, int cw, int ch, float *canvas_wts, int R, double sigma,
+                                void *workspace);
+
 /* ---- Link proposal: which frame pairs of a sequence to link at all (no reference counterpart). Two steps, both on
  * `stream` with no allocation, no synchronisation and no host read -- capturable into a HIP graph.
  * nm_link_votes_dev_u8: the u8 matcher's ratio test for ALL ordered pairs of n in [1, NM_LINK_PROPOSE_MAX_FRAMES] frames,

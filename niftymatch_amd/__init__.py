@@ -156,6 +156,11 @@ _SIGNATURES = {
     "nm_mosaic_gains_dev": (_I, [_I, _I, _P, _P, _P, _P, _I, C.c_double, C.c_double, _F, _F, _I, _P, _P, _P]),
     "nm_mosaic_gains_host": (_I, [_I, _I, _P, _P, _P, _P, _I, C.c_double, C.c_double, _F, _F, _I, _P, _P]),
     "nm_transform_blend_batch_gain": (_I, [_P, _I, _I, _P, _I, _P, _I, _I, _P, _I, _P, _I, _P, _P, _P]),
+    "nm_mosaic_bands_workspace_bytes": (_SZ, [_I, C.c_longlong, _I, _I]),
+    "nm_mosaic_bands_taps": (_I, [_I, C.c_double, _P]),
+    "nm_mosaic_warp_tiles": (_I, [_I, _P, _I, _I, _P, _I, _P, _I, _P, _P, _P, C.c_longlong, _P, _P]),
+    "nm_mosaic_bands_dev": (_I, [_I, _P, C.c_longlong, _P, _P, _I, _I, _P, _I, C.c_double, _P, _P]),
+    "nm_mosaic_bands_host": (_I, [_I, _P, C.c_longlong, _P, _P, _I, _I, _P, _I, C.c_double, _P]),
     "nm_link_votes_workspace_bytes": (_SZ, [_I, _I]),
     "nm_link_votes_dev_u8": (_I, [_I, _P, _P, _I, _F, _P, _P, _P]),
     "nm_link_votes_host_u8": (_I, [_I, _P, _P, _I, _F, _P]),
@@ -2131,6 +2136,150 @@ def mosaic_exposure(frames, link_a, link_b, H, link_status=None, mask=None, stri
     gains, stats = mosaic_gains(len(frames), link_a, link_b, sums, link_status=link_status, min_pixels=min_pixels,
                                 sigma_n=sigma_n, sigma_g=sigma_g, g_min=g_min, g_max=g_max, mode=mode, gains=gains, stats=stats)
     return gains, stats, sums
+
+
+BANDS_MAX_RADIUS, BANDS_STATS = 32, ("used", "skipped")
+_BANDS_MAX_TILE_CAP = 1 << 30
+
+
+class MosaicBandsWorkspace(_PairWorkspace):
+    """Device scratch for nm_mosaic_bands_dev: n frames of tile_cap pixels into a cw x ch canvas."""
+    _bytes_fn, _what, _shape_text = "nm_mosaic_bands_workspace_bytes", "mosaic bands workspace", "n=%d tile_cap=%d cw=%d ch=%d"
+
+    def __init__(self, n, tile_cap, cw, ch, device):
+        self._alloc(device, n=n, tile_cap=tile_cap, cw=cw, ch=ch)
+
+
+def _bands_check(n, tile_cap, cw, ch, R, sigma):
+    if not 0 < n <= MOSAIC_MAX_BATCH:
+        raise NmError("mosaic bands: %d frames (1 .. %d)" % (n, MOSAIC_MAX_BATCH))
+    if int(tile_cap) != tile_cap or not 1 <= tile_cap <= _BANDS_MAX_TILE_CAP:
+        raise NmError("mosaic bands: tile_cap %r outside [1, 2^30]" % (tile_cap,))
+    if not (1 <= cw <= _MOSAIC_SIZE_LIMIT and 1 <= ch <= _MOSAIC_SIZE_LIMIT):
+        raise NmError("mosaic bands: canvas %dx%d outside [1, %d]" % (cw, ch, _MOSAIC_SIZE_LIMIT))
+    if int(R) != R or not 0 <= R <= BANDS_MAX_RADIUS:
+        raise NmError("mosaic bands: radius %r outside [0, %d]" % (R, BANDS_MAX_RADIUS))
+    if R > 0 and not (math.isfinite(sigma) and sigma > 0):
+        raise NmError("mosaic bands: sigma %r must be finite and positive" % (sigma,))
+
+
+def mosaic_bands_taps(R, sigma):
+    """The low band's taps g[0..R] (float32 numpy) as nm_mosaic_bands_dev / _host compute them on the host."""
+    import numpy as np
+    _bands_check(1, 1, 1, 1, R, sigma)
+    g = np.zeros(int(R) + 1, np.float32)
+    _check(lib().nm_mosaic_bands_taps(int(R), float(sigma), g.ctypes.data), "nm_mosaic_bands_taps")
+    return g
+
+
+def mosaic_warp_tiles(frames, masks, wts, records, gains=None, tile_cap=None, tiles=None, stats=None):
+    """Every placed frame's gained colour and weight on its own rectangle (nm_mosaic_warp_tiles): one launch on the current
+    stream, no host read. frames, masks, wts, records, gains as transform_blend_batch_gain takes them. tile_cap: pixels per
+    slot (default fh * fw * 2); a frame whose nw * nh exceeds it is skipped. tiles / stats: float32 (n, tile_cap, 4) / int32
+    (2,) device tensors to write into (default: new, tiles uninitialised). Returns (tiles, stats): frame k's pixel (x, y) is
+    tiles[k, y * nw_k + x] = (C_B, C_G, C_R, w); stats in the order of BANDS_STATS."""
+    torch = _torch()
+    n = len(frames)
+    if not 0 < n <= MOSAIC_MAX_BATCH:
+        raise NmError("mosaic_warp_tiles: %d frames (1 .. %d)" % (n, MOSAIC_MAX_BATCH))
+    masks = list(masks) if isinstance(masks, (list, tuple)) else [masks] * n
+    wts = list(wts) if isinstance(wts, (list, tuple)) else [wts] * n
+    fh, fw = frames[0].shape[0], frames[0].shape[1]
+    if tile_cap is None:
+        tile_cap = 2 * fh * fw
+    _bands_check(n, tile_cap, 1, 1, 0, 1.0)
+    if len(masks) != n or len(wts) != n or any(f.dim() != 3 or tuple(f.shape) != (fh, fw, 4) for f in frames) or \
+            any(tuple(t.shape) != (fh, fw) for t in masks + wts) or not (1 <= fw <= _MOSAIC_SIZE_LIMIT and 1 <= fh <= _MOSAIC_SIZE_LIMIT):
+        raise NmError("mosaic_warp_tiles: n frames (fh, fw, 4) uint8 with (fh, fw) masks and weights expected")
+    mfmt, wfmt = _tex_format(masks[0]), _tex_format(wts[0])
+    if any(_tex_format(t) != mfmt for t in masks) or any(_tex_format(t) != wfmt for t in wts):
+        raise NmError("mosaic_warp_tiles: one mask format and one weight format per call")
+    if tuple(records.shape) != (n, 16) or records.dtype != torch.int32:
+        raise NmError("mosaic_warp_tiles: records must be int32 (n, 16)")
+    if gains is not None and tuple(gains.shape) != (n, 3):
+        raise NmError("mosaic_warp_tiles: gains must be float32 (n, 3)")
+    device = frames[0].device
+    if tiles is None:
+        tiles = torch.empty((n, int(tile_cap), 4), dtype=torch.float32, device=device)
+    if stats is None:
+        stats = torch.empty(len(BANDS_STATS), dtype=torch.int32, device=device)
+    if tiles.numel() != n * int(tile_cap) * 4 or stats.numel() != len(BANDS_STATS):
+        raise NmError("mosaic_warp_tiles: tiles must hold n x tile_cap x 4 floats and stats %d ints" % len(BANDS_STATS))
+    _on_current_device(list(frames) + masks + wts + [records, tiles, stats] + ([gains] if gains is not None else []),
+                       "mosaic_warp_tiles")
+    arr = lambda vals: (C.c_void_p * n)(*vals)
+    _check(lib().nm_mosaic_warp_tiles(n, arr([_dev(f, torch.uint8) for f in frames]), fw, fh, arr([_dev(t) for t in masks]),
+                                      mfmt, arr([_dev(t) for t in wts]), wfmt, _dev(records, torch.int32),
+                                      _dev(gains, torch.float32) if gains is not None else None, _dev(tiles, torch.float32),
+                                      int(tile_cap), _dev(stats, torch.int32), _stream()), "nm_mosaic_warp_tiles")
+    return tiles.view(n, int(tile_cap), 4), stats
+
+
+def _bands_canvas_shape(canvas_shape, wts_shape):
+    if len(canvas_shape) != 3 or canvas_shape[2] != 4 or (wts_shape is not None and tuple(wts_shape) != tuple(canvas_shape[:2])):
+        raise NmError("mosaic bands: canvas must be (ch, cw, 4) uint8 with (ch, cw) float32 weights or None")
+    return canvas_shape[1], canvas_shape[0]
+
+
+def mosaic_bands(canvas, canvas_wts, tiles, records, R=16, sigma=None, workspace=None):
+    """Two-band composite of the tiles of mosaic_warp_tiles into the canvas IN PLACE (nm_mosaic_bands_dev): label, two blur
+    passes and compose, four launches on the current stream whatever n is, no host read. canvas uint8 device (ch, cw, 4);
+    canvas_wts float32 (ch, cw) or None; tiles float32 (n, tile_cap, 4); records int32 (n, 16); R in [0, 32], sigma default
+    R / 2. A labelled pixel is overwritten, every other keeps its bytes and weight. Returns the workspace used."""
+    torch = _torch()
+    if tiles.dim() != 3 or tiles.shape[2] != 4:
+        raise NmError("mosaic_bands: tiles must be float32 (n, tile_cap, 4)")
+    n, tile_cap = tiles.shape[0], tiles.shape[1]
+    cw, ch = _bands_canvas_shape(tuple(canvas.shape), None if canvas_wts is None else tuple(canvas_wts.shape))
+    sigma = (max(R, 1) / 2.0) if sigma is None else sigma
+    _bands_check(n, tile_cap, cw, ch, R, sigma)
+    if tuple(records.shape) != (n, 16) or records.dtype != torch.int32:
+        raise NmError("mosaic_bands: records must be int32 (n, 16)")
+    device = _on_current_device([canvas, tiles, records] + ([canvas_wts] if canvas_wts is not None else []) +
+                                ([workspace.buf] if workspace is not None else []), "mosaic_bands")
+    workspace = _pair_workspace(MosaicBandsWorkspace, workspace, device, n, tile_cap, cw, ch)
+    _check(lib().nm_mosaic_bands_dev(n, _dev(tiles, torch.float32), tile_cap, _dev(records, torch.int32),
+                                     _dev(canvas, torch.uint8), cw, ch,
+                                     _dev(canvas_wts, torch.float32) if canvas_wts is not None else None, int(R),
+                                     float(sigma), _dev(workspace.buf), _stream()), "nm_mosaic_bands_dev")
+    return workspace
+
+
+def mosaic_bands_host(canvas, canvas_wts, tiles, records, R=16, sigma=None):
+    """mosaic_bands on the host (nm_mosaic_bands_host, the same functions): numpy arrays, canvas (ch, cw, 4) uint8 and
+    canvas_wts (ch, cw) float32 or None written IN PLACE, bit-identical to the device."""
+    import numpy as np
+    tiles, records = np.ascontiguousarray(tiles, dtype=np.float32), np.ascontiguousarray(records, dtype=np.int32)
+    if tiles.ndim != 3 or tiles.shape[2] != 4 or records.shape != (tiles.shape[0], 16):
+        raise NmError("mosaic_bands_host: tiles float32 (n, tile_cap, 4) and records int32 (n, 16) expected")
+    n, tile_cap = tiles.shape[0], tiles.shape[1]
+    for a, dt in ((canvas, np.uint8), (canvas_wts, np.float32)):
+        if a is not None and (a.dtype != dt or not a.flags.c_contiguous or not a.flags.writeable):
+            raise NmError("mosaic_bands_host: canvas uint8 and canvas_wts float32, contiguous and writeable")
+    cw, ch = _bands_canvas_shape(canvas.shape, None if canvas_wts is None else canvas_wts.shape)
+    sigma = (max(R, 1) / 2.0) if sigma is None else sigma
+    _bands_check(n, tile_cap, cw, ch, R, sigma)
+    nbytes = lib().nm_mosaic_bands_workspace_bytes(n, tile_cap, cw, ch)
+    ws, tl = _aligned_host(nbytes, np), _aligned_host(tiles.nbytes, np)
+    tl[:] = tiles.reshape(-1).view(np.uint8)
+    _check(lib().nm_mosaic_bands_host(n, tl.ctypes.data, tile_cap, records.ctypes.data, canvas.ctypes.data, cw, ch,
+                                      _pair_host_ptr(canvas_wts), int(R), float(sigma), ws.ctypes.data),
+           "nm_mosaic_bands_host")
+
+
+def _aligned_host(nbytes, np, align=16):
+    raw = np.empty(nbytes + align, np.uint8)
+    off = (-raw.ctypes.data) % align
+    return raw[off:off + nbytes]
+
+
+def mosaic_blend_bands(canvas, canvas_wts, frames, masks, wts, records, gains=None, R=16, sigma=None, tile_cap=None,
+                       tiles=None, stats=None, workspace=None):
+    """mosaic_warp_tiles, then mosaic_bands: five launches on the current stream, no host read. Returns (tiles, stats,
+    workspace) for reuse in the next call."""
+    tiles, stats = mosaic_warp_tiles(frames, masks, wts, records, gains=gains, tile_cap=tile_cap, tiles=tiles, stats=stats)
+    workspace = mosaic_bands(canvas, canvas_wts, tiles, records, R=R, sigma=sigma, workspace=workspace)
+    return tiles, stats, workspace
 
 
 LINK_PROPOSE_MAX_FRAMES = _PAIR_MAX_BATCH
