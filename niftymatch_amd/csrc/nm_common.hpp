@@ -7,6 +7,8 @@
 
 #define NM_WAVE 64
 
+constexpr int NM_SIZE_LIMIT = 32767;    // frame, canvas and output extents of every stage lie in [1, NM_SIZE_LIMIT]
+
 #define NM_RETURN_IF(expr)                                  \
     do {                                                    \
         hipError_t nm_e_ = (expr);                          \

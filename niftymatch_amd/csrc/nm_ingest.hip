@@ -16,7 +16,6 @@ namespace {
 using namespace nmw;
 using nmg::gray_of;
 
-constexpr int IG_LIMIT = 32767;                 // frame and output sizes
 constexpr int IG_THREADS = 256;
 constexpr int IG_UNROLL = 4;                    // frames whose taps are in flight together
 constexpr int IG_FILL_BLOCKS_PER_CU = 8;        // below this many pixel workgroups per CU, frames split over grid y
@@ -105,7 +104,7 @@ int nm_frame_ingest_batch_f32(int n, const unsigned char *const *frames, int fw,
                               const float *map_y, int cols, int rows, float *const *gray,
                               unsigned char *const *undistorted, void *stream)
 {
-    const auto size_ok = [](int v) { return v >= 1 && v <= IG_LIMIT; };
+    const auto size_ok = [](int v) { return v >= 1 && v <= NM_SIZE_LIMIT; };
     if (n < 1 || n > NM_INGEST_MAX_BATCH || !size_ok(fw) || !size_ok(fh) || !size_ok(cols) || !size_ok(rows))
         return (int)hipErrorInvalidValue;
     if (!frames || !gray || (!map_x) != (!map_y)) return (int)hipErrorInvalidValue;

@@ -30,12 +30,7 @@ static_assert(SUMS == 67 && sizeof(State) == 128, "the workspace layout of nm_ab
 
 constexpr int ROW = 68;                     // doubles per row of partials: the 67 sums and one of padding
 constexpr int SOLVE_THREADS = 128;
-constexpr long long MAX_LATTICE = 1ll << 28;
-
-struct FrameTables {                        // 2 x 64 pointers, 1 KB of kernel arguments
-    const float *a[nmp::MAX_BATCH];
-    const float *b[nmp::MAX_BATCH];
-};
+using nmlat::FrameTables; using nmlat::frames_ok; using nmlat::lattice_of;
 
 __global__ __launch_bounds__(THREADS) void link_refine_accumulate_kernel(const FrameTables T, int fw, int fh,
                                                                          const float *__restrict__ mask,
@@ -64,7 +59,7 @@ __global__ __launch_bounds__(THREADS) void link_refine_accumulate_kernel(const F
     double s[SUMS];
 #pragma unroll
     for (int q = 0; q < SUMS; ++q) s[q] = 0.0;
-    walk_lane(F, G, Hk, stride, lw, lh, tiles_x, tiles, blockIdx.x, wave, lane, s);
+    walk_lane(F, G, Hk, stride, Lattice{lw, lh, tiles_x, tiles}, blockIdx.x, wave, lane, s);
 #pragma unroll
     for (int q = 0; q < SUMS; ++q) {
         const double v = nmw::wave_reduce(s[q], nmw::Sum());
@@ -113,9 +108,8 @@ __global__ __launch_bounds__(SOLVE_THREADS) void link_refine_solve_kernel(const 
 // ---- the host twin: the same functions, the virtual lanes, the trees and the rows walked serially ----
 void host_sums(const Frames &F, const float *H, int stride, double tot[SUMS])
 {
-    const int lw = F.fw / stride, lh = F.fh / stride;
-    const int tiles_x = nm_divup(lw, TILE_W), tiles = tiles_x * nm_divup(lh, TILE_H);
-    const int parts = tiles < PARTS ? tiles : PARTS;
+    const Lattice L = lattice_of(F.fw, F.fh, stride);
+    const int parts = L.tiles < PARTS ? L.tiles : PARTS;
     const Norm G = norm_of(F.fw, F.fh);
     for (int q = 0; q < SUMS; ++q) tot[q] = 0.0;
     static thread_local double v[64][SUMS];
@@ -125,7 +119,7 @@ void host_sums(const Frames &F, const float *H, int stride, double tot[SUMS])
         for (int w = 0; w < WAVES; ++w) {
             for (int l = 0; l < 64; ++l) {
                 for (int q = 0; q < SUMS; ++q) v[l][q] = 0.0;
-                walk_lane(F, G, H, stride, lw, lh, tiles_x, tiles, g, w, l, v[l]);
+                walk_lane(F, G, H, stride, L, g, w, l, v[l]);
             }
             for (int d = 32; d >= 1; d >>= 1)
                 for (int l = 0; l < d; ++l)
@@ -134,13 +128,6 @@ void host_sums(const Frames &F, const float *H, int stride, double tot[SUMS])
         }
         for (int q = 0; q < SUMS; ++q) tot[q] = tot[q] + row[q];
     }
-}
-
-bool frames_ok(int n, const float *const *grayA, const float *const *grayB, int fw, int fh, const float *H, int stride)
-{
-    if (n < 1 || n > nmp::MAX_BATCH || fw < 1 || fw > 32767 || fh < 1 || fh > 32767 || stride < 1 || stride > 64) return false;
-    if ((long long)(fw / stride) * (long long)(fh / stride) > MAX_LATTICE) return false;
-    return nmp::tables_ok(n, {grayA, grayB}, {}, {H});
 }
 
 bool lr_args_ok(int n, const float *const *grayA, const float *const *grayB, int fw, int fh, const float *H, int model,
@@ -168,9 +155,8 @@ extern "C" int nm_link_refine_batch_dev_f32(int n, const float *const *grayA, co
     if (!lr_args_ok(n, grayA, grayB, fw, fh, H_in, model, stride, iterations, min_pixels, max_step, H_out, status_out, stats) ||
         !workspace)
         return (int)hipErrorInvalidValue;
-    const int lw = fw / stride, lh = fh / stride;
-    const int tiles_x = nm_divup(lw, TILE_W), tiles = tiles_x * nm_divup(lh, TILE_H);
-    const int parts = tiles < PARTS ? tiles : PARTS;
+    const Lattice L = lattice_of(fw, fh, stride);
+    const int parts = L.tiles < PARTS ? L.tiles : PARTS;
     double *partials = static_cast<double *>(workspace);
     State *states = reinterpret_cast<State *>(partials + (size_t)n * PARTS * ROW);
     const Params P{fw, fh, model, min_pixels, max_step};
@@ -180,7 +166,7 @@ extern "C" int nm_link_refine_batch_dev_f32(int n, const float *const *grayA, co
     for (int it = 0; it < iterations; ++it) {
         if (parts > 0) {                                         // a stride beyond the frame: an empty lattice, all sums 0
             hipLaunchKernelGGL(link_refine_accumulate_kernel, dim3(parts, n), dim3(THREADS), 0, nm_stream(stream), T, fw, fh,
-                               mask, H_in, status_in, states, it == 0 ? 1 : 0, stride, lw, lh, tiles_x, tiles, partials);
+                               mask, H_in, status_in, states, it == 0 ? 1 : 0, stride, L.lw, L.lh, L.tiles_x, L.tiles, partials);
             NM_LAUNCH_CHECK();
         }
         hipLaunchKernelGGL(link_refine_solve_kernel, dim3(n), dim3(SOLVE_THREADS), 0, nm_stream(stream), P, it, iterations - 1,

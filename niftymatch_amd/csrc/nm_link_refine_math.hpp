@@ -5,6 +5,7 @@
 // partials in the order nm_abi.h states. The accumulation multiplies and adds separately (the build has -ffp-contract=off);
 // the solve and the step use explicit fma. Lattice, mask rule, levels and the sample of B are nml::pixel.
 #pragma once
+#include "nm_lattice.hpp"
 #include "nm_link_verify_math.hpp"
 
 namespace nmlr {
@@ -17,8 +18,7 @@ constexpr int TRI = COLS * (COLS + 1) / 2;  // upper triangle of J^T J, row-majo
 constexpr int S_JTR = TRI, S_RR = TRI + COLS, S_L = S_RR + 1;
 constexpr int SUMS = S_L + 1;               // 67
 constexpr int STATS = NM_LINK_REFINE_STATS;
-constexpr int THREADS = 256, WAVES = THREADS / 64;
-constexpr int TILE_W = 64, TILE_H = 32;     // the verification's lattice tiles
+using nmlat::THREADS; using nmlat::WAVES; using nmlat::TILE_W; using nmlat::TILE_H; using nmlat::Lattice;
 constexpr int PARTS = 256;                  // virtual workgroups = rows of partials per pair
 constexpr int WORK = COLS * COLS + 2 * COLS;  // doubles of scratch for solve_system
 constexpr double GAIN_SCALE = NM_LINK_REFINE_GAIN_SCALE, BIAS_SCALE = NM_LINK_REFINE_BIAS_SCALE;
@@ -73,16 +73,16 @@ __host__ __device__ __forceinline__ void add_pixel(const Frames &F, const Norm &
     s[S_RR] = s[S_RR] + r * r;
 }
 
-// Virtual lane (g, wave, lane): tiles g, g + PARTS, ..; in a tile the rows wave, wave + WAVES, .. of column `lane`.
-__host__ __device__ __forceinline__ void walk_lane(const Frames &F, const Norm &G, const float H[9], int stride, int lw, int lh,
-                                                   int tiles_x, int tiles, int g, int wave, int lane, double s[SUMS])
+// Virtual lane (g, wave, lane) of the lattice walk, step PARTS, X once per column (one of three copies: nm_lattice.hpp)
+__host__ __device__ __forceinline__ void walk_lane(const Frames &F, const Norm &G, const float H[9], int stride,
+                                                   const Lattice L, int g, int wave, int lane, double s[SUMS])
 {
-    for (int t = g; t < tiles; t += PARTS) {
-        const int u = (t % tiles_x) * TILE_W + lane, v0 = (t / tiles_x) * TILE_H;
-        if (u >= lw) continue;
+    for (int t = g; t < L.tiles; t += PARTS) {
+        const int u = (t % L.tiles_x) * TILE_W + lane, v0 = (t / L.tiles_x) * TILE_H;
+        if (u >= L.lw) continue;
         const int x = stride * u + stride / 2;
         const double X = ((double)x - G.cx) / G.h;
-        for (int r = wave; r < TILE_H && v0 + r < lh; r += WAVES) {
+        for (int r = wave; r < TILE_H && v0 + r < L.lh; r += WAVES) {
             const int y = stride * (v0 + r) + stride / 2;
             add_pixel(F, G, H, x, y, X, ((double)y - G.cy) / G.h, s);
         }

@@ -2,8 +2,8 @@
 // plan? Four gates per pair (usable, support, geometry, photometric; include/nm_abi.h has the written semantics). No
 // reference counterpart. TWO launches per call whatever n is, on the caller's stream, no allocation, no synchronisation,
 // no host read:
-//   accumulate  grid (parts, n). A's lattice is cut into tiles of 64 columns x 32 rows; a workgroup of four waves walks
-//               the tiles blockIdx.x, blockIdx.x + parts, ..: a wave takes a lattice row, its lanes 64 neighbouring
+//   accumulate  grid (parts, n). The lattice walk over A (one of three copies: nm_lattice.hpp): a workgroup of four waves
+//               walks the tiles blockIdx.x, blockIdx.x + parts, ..: a wave takes a lattice row, its lanes 64 neighbouring
 //               lattice columns (at stride 1 one coalesced 256-byte read of A), each lane gathers its four taps of B. The
 //               seven sums are integers: u64 per lane -> nmw::wave_reduce -> the four waves through LDS -> one row of
 //               partials per workgroup in the workspace (plain vector stores, no atomics, no reset).
@@ -13,6 +13,7 @@
 #include <cmath>
 
 #include "nm_common.hpp"
+#include "nm_lattice.hpp"
 #include "nm_link_verify_math.hpp"
 #include "nm_pair_batch.hpp"
 #include "../../include/nm_abi.h"
@@ -20,19 +21,12 @@
 namespace {
 
 using namespace nml;
+using namespace nmlat;
 
 static_assert(NM_LINK_VERIFY_MAX_BATCH == nmp::MAX_BATCH, "public header and pair-batch convention disagree");
 
-constexpr int THREADS = 256, WAVES = THREADS / 64;
-constexpr int TILE_W = 64, TILE_H = 32;
 constexpr int MAX_PARTS = 256;              // workgroups (rows of partials) per pair
 constexpr int PART_STRIDE = 8;              // u64 per row of partials: the seven sums and one of padding (64 bytes)
-constexpr long long MAX_LATTICE = 1ll << 28;
-
-struct FrameTables {                        // 2 x 64 pointers, 1 KB of kernel arguments
-    const float *a[nmp::MAX_BATCH];
-    const float *b[nmp::MAX_BATCH];
-};
 
 __global__ __launch_bounds__(THREADS) void link_verify_accumulate_kernel(const FrameTables T, int fw, int fh,
                                                                          const float *__restrict__ mask,
@@ -49,7 +43,7 @@ __global__ __launch_bounds__(THREADS) void link_verify_accumulate_kernel(const F
     if (!usable(status_in ? status_in[k] : 1, Hk)) return;      // uniform: the finalize does not read this pair's rows
     const Frames F{T.a[k], T.b[k], mask, fw, fh};
     u64 s[SUMS] = {0, 0, 0, 0, 0, 0, 0};
-    for (int t = blockIdx.x; t < tiles; t += gridDim.x) {
+    for (int t = blockIdx.x; t < tiles; t += gridDim.x) {        // the lattice walk: one of three copies (nm_lattice.hpp)
         const int u = (t % tiles_x) * TILE_W + lane, v0 = (t / tiles_x) * TILE_H;
         if (u < lw)
             for (int r = wave; r < TILE_H && v0 + r < lh; r += WAVES)
@@ -101,17 +95,10 @@ __global__ __launch_bounds__(THREADS) void link_verify_finalize_kernel(int fw, i
 // ---- the host twin: the same functions, the lattice walked row by row ----
 void host_sums(const Frames &F, const float *H, int stride, u64 s[SUMS])
 {
-    const int lw = F.fw / stride, lh = F.fh / stride;
+    const Lattice L = lattice_of(F.fw, F.fh, stride);
     for (int q = 0; q < SUMS; ++q) s[q] = 0;
-    for (int v = 0; v < lh; ++v)
-        for (int u = 0; u < lw; ++u) add_pixel(F, H, stride * u + stride / 2, stride * v + stride / 2, s);
-}
-
-bool frames_ok(int n, const float *const *grayA, const float *const *grayB, int fw, int fh, const float *H, int stride)
-{
-    if (n < 1 || n > nmp::MAX_BATCH || fw < 1 || fw > 32767 || fh < 1 || fh > 32767 || stride < 1 || stride > 64) return false;
-    if ((long long)(fw / stride) * (long long)(fh / stride) > MAX_LATTICE) return false;
-    return nmp::tables_ok(n, {grayA, grayB}, {}, {H});
+    for (int v = 0; v < L.lh; ++v)
+        for (int u = 0; u < L.lw; ++u) add_pixel(F, H, stride * u + stride / 2, stride * v + stride / 2, s);
 }
 
 bool lv_args_ok(int n, const float *const *grayA, const float *const *grayB, int fw, int fh, const float *H, int stride,
@@ -140,16 +127,15 @@ extern "C" int nm_link_verify_batch_dev_f32(int n, const float *const *grayA, co
     if (!lv_args_ok(n, grayA, grayB, fw, fh, H, stride, min_inliers, max_area_ratio, min_overlap, min_ncc, status_out, reason,
                     stats) || !workspace)
         return (int)hipErrorInvalidValue;
-    const int lw = fw / stride, lh = fh / stride;
-    const int tiles_x = nm_divup(lw, TILE_W), tiles = tiles_x * nm_divup(lh, TILE_H);
-    const int parts = tiles < MAX_PARTS ? tiles : MAX_PARTS;
+    const Lattice L = lattice_of(fw, fh, stride);
+    const int parts = L.tiles < MAX_PARTS ? L.tiles : MAX_PARTS;
     u64 *partials = static_cast<u64 *>(workspace);
     if (parts > 0) {                                             // a stride beyond the frame: an empty lattice, all sums 0
         FrameTables T;
         nmp::fill_slots(T.a, grayA, 0, n);
         nmp::fill_slots(T.b, grayB, 0, n);
         hipLaunchKernelGGL(link_verify_accumulate_kernel, dim3(parts, n), dim3(THREADS), 0, nm_stream(stream), T, fw, fh, mask,
-                           H, status_in, stride, lw, lh, tiles_x, tiles, partials);
+                           H, status_in, stride, L.lw, L.lh, L.tiles_x, L.tiles, partials);
         NM_LAUNCH_CHECK();
     }
     hipLaunchKernelGGL(link_verify_finalize_kernel, dim3(n), dim3(THREADS), 0, nm_stream(stream), fw, fh, H, status_in,

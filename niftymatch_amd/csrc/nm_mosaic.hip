@@ -6,29 +6,27 @@
 //         __device__ functions build the host twin, so the two agree bit for bit.
 //   place (1 launch, 1 workgroup): the plan's placement half on a given chain (e.g. the adjusted one of
 //         nm_mosaic_adjust.hip): one lane per frame through the same mp_frame, the same extent.
-//   blend (1 launch, fixed grid): every workgroup stages the n records and frame pointers in LDS and clips the
-//         rectangles; a grid-stride loop walks the 64 x 4 tiles of the rectangles' bounding box, one canvas row of 64
-//         pixels per wave. A wave ballots the frames whose rectangle meets its row (a wave-uniform 64-bit mask) and
-//         walks the set bits in index order; each lane runs transform_blend's per-pixel step (nm_warp_math.hpp) for
-//         every covering frame with the canvas pixel and weight in registers: one load, at most one store per pixel.
+//   blend (1 launch, fixed grid; this walk is repeated in mosaic_bands_canvas_kernel, see nm_mosaic_batch.hpp): every
+//         workgroup stages the n records and frame pointers in LDS and clips the rectangles; a grid-stride loop walks
+//         the 64 x 4 tiles of the rectangles' bounding box, one canvas row of 64 pixels per wave. A wave ballots the
+//         frames whose rectangle meets its row (a wave-uniform 64-bit mask) and walks the set bits in index order; each
+//         lane runs transform_blend's per-pixel step (nm_warp_math.hpp) for every covering frame with the canvas pixel
+//         and weight in registers: one load, at most one store per pixel.
 //         nm_transform_blend_batch_gain is the same kernel body with a per-frame, per-channel gain on the frame's colour
 //         (the exposure compensation of nm_mosaic_exposure.hip), a compile-time switch.
 #include <climits>
 #include <cmath>
 
+#include "nm_mosaic_batch.hpp"
 #include "nm_warp_math.hpp"
 
 namespace {
 
 using namespace nmw;
+using namespace nmmb;
 
-constexpr int MP_LIMIT = 32767;                 // frame and canvas sizes
 constexpr int MP_OFFSET_LIMIT = 1 << 20;        // |ox|, |oy|
-constexpr int MB_THREADS = 256;                 // 4 waves: a tile is 64 x 4 canvas pixels, one row per wave
-constexpr int MB_TILE_W = 64, MB_TILE_H = MB_THREADS / 64;
 constexpr int MB_BLOCKS_PER_CU = 8;
-
-static_assert(sizeof(nm_mosaic_record) == 64, "nm_mosaic_record must stay 64 bytes");
 
 __host__ __device__ __forceinline__ bool mp_finite(float v) { return __builtin_isfinite(v); }
 
@@ -128,12 +126,30 @@ __host__ __device__ __forceinline__ int mp_given(const float *M, int status)
     return ok ? 1 : 0;
 }
 
-inline bool mp_args_ok(int n, const float *H, int fw, int fh, int cw, int ch, int ox, int oy, const void *records)
+inline bool mp_sizes_ok(int n, int fw, int fh, int cw, int ch, int ox, int oy, const void *records)
 {
-    const auto size_ok = [](int v) { return v >= 1 && v <= MP_LIMIT; };
+    const auto size_ok = [](int v) { return v >= 1 && v <= NM_SIZE_LIMIT; };
     return n >= 1 && n <= NM_MOSAIC_MAX_BATCH && size_ok(fw) && size_ok(fh) && size_ok(cw) && size_ok(ch) &&
-           ox > -MP_OFFSET_LIMIT && ox < MP_OFFSET_LIMIT && oy > -MP_OFFSET_LIMIT && oy < MP_OFFSET_LIMIT && records &&
-           (H || n == 1);
+           ox > -MP_OFFSET_LIMIT && ox < MP_OFFSET_LIMIT && oy > -MP_OFFSET_LIMIT && oy < MP_OFFSET_LIMIT && records;
+}
+
+// A frame's box into the extent of the frames placed before it, in index order (the host twins)
+inline void mp_extent_add(bool &any, float e[4], const float box[4])
+{
+    for (int q = 0; q < 2; ++q) e[q] = (!any || box[q] < e[q]) ? box[q] : e[q];
+    for (int q = 2; q < 4; ++q) e[q] = (!any || box[q] > e[q]) ? box[q] : e[q];
+    any = true;
+}
+
+// The extent of a wave's placed frames, lane k with frame k's box. Every box value is an integer-valued finite float (no
+// -0), so min / max are order-independent: equal to mp_extent_add's in-order loop.
+__device__ __forceinline__ void mp_extent_store(bool placed, const float box[4], int k, float *__restrict__ extent)
+{
+    float e[4] = {placed ? box[0] : INFINITY, placed ? box[1] : INFINITY, placed ? box[2] : -INFINITY,
+                  placed ? box[3] : -INFINITY};
+    e[0] = nmw::wave_min(e[0]); e[1] = nmw::wave_min(e[1]); e[2] = nmw::wave_max(e[2]); e[3] = nmw::wave_max(e[3]);
+    const bool any = __ballot(placed) != 0ull;
+    if (k < 4) extent[k] = any ? e[k] : 0.f;
 }
 
 __global__ __launch_bounds__(64) void mosaic_plan_kernel(int n, const float *__restrict__ H, const int *__restrict__ status,
@@ -165,13 +181,7 @@ __global__ __launch_bounds__(64) void mosaic_plan_kernel(int n, const float *__r
             for (int q = 0; q < 9; ++q) chain[9 * k + q] = s_M[k][q];
     }
     if (!extent) return;                                  // uniform
-    // every box value is an integer-valued finite float (no -0), so min / max are order-independent: equal to the
-    // host twin's in-order loop
-    float e[4] = {placed ? box[0] : INFINITY, placed ? box[1] : INFINITY, placed ? box[2] : -INFINITY,
-                  placed ? box[3] : -INFINITY};
-    e[0] = nmw::wave_min(e[0]); e[1] = nmw::wave_min(e[1]); e[2] = nmw::wave_max(e[2]); e[3] = nmw::wave_max(e[3]);
-    const bool any = __ballot(placed) != 0ull;
-    if (k < 4) extent[k] = any ? e[k] : 0.f;
+    mp_extent_store(placed, box, k, extent);
 }
 
 // The placement half of the plan on a given chain: one lane per frame, the extent as in the plan
@@ -191,28 +201,17 @@ __global__ __launch_bounds__(64) void mosaic_place_kernel(int n, const float *__
         records[k] = rec;
     }
     if (!extent) return;                                  // uniform
-    float e[4] = {placed ? box[0] : INFINITY, placed ? box[1] : INFINITY, placed ? box[2] : -INFINITY,
-                  placed ? box[3] : -INFINITY};
-    e[0] = nmw::wave_min(e[0]); e[1] = nmw::wave_min(e[1]); e[2] = nmw::wave_max(e[2]); e[3] = nmw::wave_max(e[3]);
-    const bool any = __ballot(placed) != 0ull;
-    if (k < 4) extent[k] = any ? e[k] : 0.f;
+    mp_extent_store(placed, box, k, extent);
 }
-
-struct MbArgs {                                   // 3 x 64 pointers: 1.5 KB of the 4 KB of kernel arguments
-    const void *frames[NM_MOSAIC_MAX_BATCH];
-    const void *masks[NM_MOSAIC_MAX_BATCH];
-    const void *wts[NM_MOSAIC_MAX_BATCH];
-};
-static_assert(sizeof(MbArgs) + 64 < 4096, "blend kernel arguments exceed 4 KB");
 
 // GAIN: frame k's colour is multiplied by gains[3 k + c] between blend_sample and blend_combine (the gains staged in LDS
 // beside the records); without it the body is the ungained blend's, operation for operation.
 template <bool GAIN>
-__global__ __launch_bounds__(MB_THREADS) void transform_blend_batch_kernel(const MbArgs a, int n, uchar4 *__restrict__ canvas,
-                                                                           int cw, int ch, float *__restrict__ canvas_wts,
-                                                                           int fw, int fh, int mask_format, int wts_format,
-                                                                           const nm_mosaic_record *__restrict__ records,
-                                                                           const float *__restrict__ gains)
+__global__ __launch_bounds__(CANVAS_THREADS) void transform_blend_batch_kernel(const FrameArgs a, int n, uchar4 *__restrict__ canvas,
+                                                                        int cw, int ch, float *__restrict__ canvas_wts,
+                                                                        int fw, int fh, int mask_format, int wts_format,
+                                                                        const nm_mosaic_record *__restrict__ records,
+                                                                        const float *__restrict__ gains)
 {
     __shared__ float s_gain[GAIN ? NM_MOSAIC_MAX_BATCH : 1][3];
     __shared__ float s_m[NM_MOSAIC_MAX_BATCH][9];
@@ -248,14 +247,14 @@ __global__ __launch_bounds__(MB_THREADS) void transform_blend_batch_kernel(const
     const int4 U = s_union;
     if (U.z <= U.x) return;                            // no frame touches the canvas (uniform)
     const int4 mine = s_rect[lane];                    // lane l tests frame l's rectangle (empty beyond n)
-    const int tiles_x = (U.z - U.x + MB_TILE_W - 1) / MB_TILE_W;
-    const int tiles = tiles_x * ((U.w - U.y + MB_TILE_H - 1) / MB_TILE_H);
+    const int tiles_x = (U.z - U.x + CANVAS_TILE_W - 1) / CANVAS_TILE_W;
+    const int tiles = tiles_x * ((U.w - U.y + CANVAS_TILE_H - 1) / CANVAS_TILE_H);
     const Tex none{nullptr, fw, fh, 0};
     for (int t = blockIdx.x; t < tiles; t += gridDim.x) {
         const int ty_ = t / tiles_x, tx_ = t - ty_ * tiles_x;
-        const int row = U.y + ty_ * MB_TILE_H + wave, xs = U.x + tx_ * MB_TILE_W;
+        const int row = U.y + ty_ * CANVAS_TILE_H + wave, xs = U.x + tx_ * CANVAS_TILE_W;
         const int px = xs + lane;
-        unsigned long long fm = __ballot(mine.y <= row && row < mine.w && mine.x < xs + MB_TILE_W && xs < mine.z);
+        unsigned long long fm = __ballot(mine.y <= row && row < mine.w && mine.x < xs + CANVAS_TILE_W && xs < mine.z);
         if (!fm) continue;                             // wave-uniform
         const size_t idx = (size_t)row * cw + px;
         bool have = false;
@@ -297,7 +296,7 @@ extern "C" {
 int nm_mosaic_plan_host_f32(int n, const float *H, const int *status, int fw, int fh, int cw, int ch, int ox, int oy,
                             const float *M_first, nm_mosaic_record *records, float *chain, float *extent)
 {
-    if (!mp_args_ok(n, H, fw, fh, cw, ch, ox, oy, records)) return (int)hipErrorInvalidValue;
+    if (!mp_sizes_ok(n, fw, fh, cw, ch, ox, oy, records) || !(H || n == 1)) return (int)hipErrorInvalidValue;
     float M[NM_MOSAIC_MAX_BATCH][9];
     int ok[NM_MOSAIC_MAX_BATCH];
     mp_chain(n, H, status, M_first, M, ok);
@@ -308,10 +307,7 @@ int nm_mosaic_plan_host_f32(int n, const float *H, const int *status, int fw, in
         const bool placed = mp_frame(M[k], ok[k], fw, fh, cw, ch, ox, oy, records[k], box);
         if (chain)
             for (int q = 0; q < 9; ++q) chain[9 * k + q] = M[k][q];
-        if (!placed) continue;
-        for (int q = 0; q < 2; ++q) e[q] = (!any || box[q] < e[q]) ? box[q] : e[q];
-        for (int q = 2; q < 4; ++q) e[q] = (!any || box[q] > e[q]) ? box[q] : e[q];
-        any = true;
+        if (placed) mp_extent_add(any, e, box);
     }
     if (extent)
         for (int q = 0; q < 4; ++q) extent[q] = e[q];
@@ -321,7 +317,7 @@ int nm_mosaic_plan_host_f32(int n, const float *H, const int *status, int fw, in
 int nm_mosaic_plan_f32(int n, const float *H, const int *status, int fw, int fh, int cw, int ch, int ox, int oy,
                        const float *M_first, nm_mosaic_record *records, float *chain, float *extent, void *stream)
 {
-    if (!mp_args_ok(n, H, fw, fh, cw, ch, ox, oy, records)) return (int)hipErrorInvalidValue;
+    if (!mp_sizes_ok(n, fw, fh, cw, ch, ox, oy, records) || !(H || n == 1)) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(mosaic_plan_kernel, dim3(1), dim3(64), 0, nm_stream(stream), n, H, status, fw, fh, cw, ch, ox, oy,
                        M_first, records, chain, extent);
     NM_LAUNCH_CHECK();
@@ -331,17 +327,14 @@ int nm_mosaic_plan_f32(int n, const float *H, const int *status, int fw, int fh,
 int nm_mosaic_place_host_f32(int n, const float *chain, const int *frame_status, int fw, int fh, int cw, int ch, int ox,
                              int oy, nm_mosaic_record *records, float *extent)
 {
-    // mp_args_ok lets its second pointer (the plan's H) be null for n == 1; a chain is needed for every n
-    if (!mp_args_ok(n, chain, fw, fh, cw, ch, ox, oy, records) || !chain) return (int)hipErrorInvalidValue;
+    if (!mp_sizes_ok(n, fw, fh, cw, ch, ox, oy, records) || !chain) return (int)hipErrorInvalidValue;
     bool any = false;
     float e[4] = {0.f, 0.f, 0.f, 0.f};
     for (int k = 0; k < n; ++k) {
         float box[4];
         const float *M = chain + 9 * k;
         if (!mp_frame(M, mp_given(M, frame_status ? frame_status[k] : 1), fw, fh, cw, ch, ox, oy, records[k], box)) continue;
-        for (int q = 0; q < 2; ++q) e[q] = (!any || box[q] < e[q]) ? box[q] : e[q];
-        for (int q = 2; q < 4; ++q) e[q] = (!any || box[q] > e[q]) ? box[q] : e[q];
-        any = true;
+        mp_extent_add(any, e, box);
     }
     if (extent)
         for (int q = 0; q < 4; ++q) extent[q] = e[q];
@@ -351,8 +344,7 @@ int nm_mosaic_place_host_f32(int n, const float *chain, const int *frame_status,
 int nm_mosaic_place_f32(int n, const float *chain, const int *frame_status, int fw, int fh, int cw, int ch, int ox, int oy,
                         nm_mosaic_record *records, float *extent, void *stream)
 {
-    // mp_args_ok lets its second pointer (the plan's H) be null for n == 1; a chain is needed for every n
-    if (!mp_args_ok(n, chain, fw, fh, cw, ch, ox, oy, records) || !chain) return (int)hipErrorInvalidValue;
+    if (!mp_sizes_ok(n, fw, fh, cw, ch, ox, oy, records) || !chain) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(mosaic_place_kernel, dim3(1), dim3(64), 0, nm_stream(stream), n, chain, frame_status, fw, fh, cw, ch,
                        ox, oy, records, extent);
     NM_LAUNCH_CHECK();
@@ -364,25 +356,19 @@ int nm_transform_blend_batch_gain(unsigned char *canvas, int cw, int ch, float *
                                   int mask_format, const void *const *wts, int wts_format, const nm_mosaic_record *records,
                                   const float *gains, void *stream)
 {
-    const auto scalar_fmt = [](int f) { return f == NM_TEX_U8N || f == NM_TEX_F32; };
-    if (n < 1 || n > NM_MOSAIC_MAX_BATCH || cw < 1 || cw > MP_LIMIT || ch < 1 || ch > MP_LIMIT || fw < 1 || fh < 1 ||
+    if (n < 1 || n > NM_MOSAIC_MAX_BATCH || cw < 1 || cw > NM_SIZE_LIMIT || ch < 1 || ch > NM_SIZE_LIMIT || fw < 1 || fh < 1 ||
         !scalar_fmt(mask_format) || !scalar_fmt(wts_format))
         return (int)hipErrorInvalidValue;
-    if (!canvas || !canvas_wts || !frames || !masks || !wts || !records) return (int)hipErrorInvalidValue;
-    MbArgs a;
-    for (int k = 0; k < NM_MOSAIC_MAX_BATCH; ++k) {
-        if (k < n && (!frames[k] || !masks[k] || !wts[k])) return (int)hipErrorInvalidValue;
-        a.frames[k] = k < n ? frames[k] : nullptr;
-        a.masks[k] = k < n ? masks[k] : nullptr;
-        a.wts[k] = k < n ? wts[k] : nullptr;
-    }
+    if (!canvas || !canvas_wts || !records) return (int)hipErrorInvalidValue;
+    FrameArgs a;
+    if (!fill_frame_args(a, n, frames, masks, wts)) return (int)hipErrorInvalidValue;
     // The grid is fixed here, before the rectangles exist: enough workgroups to fill the chip, never more than the
     // canvas has tiles. A workgroup whose tiles lie outside every rectangle returns after staging the records.
-    const long long canvas_tiles = (long long)nm_divup(cw, MB_TILE_W) * nm_divup(ch, MB_TILE_H);
+    const long long canvas_tiles = (long long)nm_divup(cw, CANVAS_TILE_W) * nm_divup(ch, CANVAS_TILE_H);
     const long long fill = (long long)nm_cu_count() * MB_BLOCKS_PER_CU;
     const int grid = (int)(canvas_tiles < fill ? canvas_tiles : fill);
     const auto kernel = gains ? transform_blend_batch_kernel<true> : transform_blend_batch_kernel<false>;
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(MB_THREADS), 0, nm_stream(stream), a, n,
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(CANVAS_THREADS), 0, nm_stream(stream), a, n,
                        reinterpret_cast<uchar4 *>(canvas), cw, ch, canvas_wts, fw, fh, mask_format, wts_format, records, gains);
     NM_LAUNCH_CHECK();
     return 0;

@@ -31,8 +31,6 @@ namespace {
 
 using namespace nmma;
 
-constexpr int SIZE_LIMIT = 32767;           // frame sizes, as for the plan
-
 struct AccArgs {                            // 6 x 64 pointers and the links' frames: 3.2 KB of kernel arguments
     nmp::PointTables p;
     unsigned char a[GROUP], b[GROUP];
@@ -218,7 +216,7 @@ bool host_solve(const Params &P, const LinkIdx &X, const double *rows, std::vect
 
 bool sizes_ok(int capA, int fw, int fh)
 {
-    return nmp::cap_ok(capA) && fw >= 1 && fw <= SIZE_LIMIT && fh >= 1 && fh <= SIZE_LIMIT;
+    return nmp::cap_ok(capA) && fw >= 1 && fw <= NM_SIZE_LIMIT && fh >= 1 && fh <= NM_SIZE_LIMIT;
 }
 
 bool ma_args_ok(int n, int L, const int *link_a, const int *link_b, const float *const *src_x, const float *const *src_y,

@@ -5,7 +5,7 @@
 //               the running total grid-stride: a wave takes a tile row, a lane one local pixel, through blend_sample and
 //               the gain multiply exactly as the batched blend calls them; one float4 store per pixel.
 //   bands       FOUR launches whatever n is:
-//     label     the batched blend's canvas walk (records in LDS, 64-bit clipping, ballot of covering frames per wave
+//     label     a copy of the batched blend's canvas walk (nm_mosaic.hip; 64-bit clipping, ballot of covering frames per wave
 //               row, grid-stride over 64 x 4 tiles): the covering frame of largest weight, one byte per pixel.
 //     blur x 2  the hot path. Separable, so two launches: a fused 2-D pass would carry a (2R + 1)^2 halo (at R = 32 a
 //               64 x 64 tile would load 4x its pixels and need 5 x 128 x 128 x 4 B = 320 KB of LDS), while two 1-D passes
@@ -24,20 +24,15 @@
 #include <cmath>
 
 #include "nm_mosaic_bands_math.hpp"
+#include "nm_mosaic_batch.hpp"
 #include "nm_warp_math.hpp"
 
 namespace {
 
 using namespace nmb;
+using namespace nmmb;
 
-constexpr int MAX_FRAMES = NM_MOSAIC_MAX_BATCH;
-constexpr int THREADS = 256;
-constexpr int SIZE_LIMIT = 32767;
-constexpr int BLOCKS_PER_CU = 8;
-constexpr int CANVAS_TILE_W = 64, CANVAS_TILE_H = THREADS / 64;   // the batched blend's tile: one canvas row per wave
-
-static_assert(sizeof(nm_mosaic_record) == 64, "nm_mosaic_record must stay 64 bytes");
-static_assert(MAX_FRAMES == 64, "one lane per frame in a wave of 64");
+constexpr int THREADS = CANVAS_THREADS, BLOCKS_PER_CU = 8;
 
 // ---- the walk over the frames' own rectangles: every used frame's tiles on one running total ----
 struct Walk {
@@ -81,15 +76,8 @@ __device__ __forceinline__ void walk_find(const Walk &W, long long t, long long 
     tx_ = (int)(local - (long long)ty_ * tiles_x);
 }
 
-struct WtArgs {                                   // 3 x 64 pointers: 1.5 KB of the 4 KB of kernel arguments
-    const void *frames[MAX_FRAMES];
-    const void *masks[MAX_FRAMES];
-    const void *wts[MAX_FRAMES];
-};
-static_assert(sizeof(WtArgs) + 128 < 4096, "warp-tiles kernel arguments exceed 4 KB");
-
 template <bool GAIN>
-__global__ __launch_bounds__(THREADS) void mosaic_warp_tiles_kernel(const WtArgs a, int n, int fw, int fh, int mask_format,
+__global__ __launch_bounds__(THREADS) void mosaic_warp_tiles_kernel(const FrameArgs a, int n, int fw, int fh, int mask_format,
                                                                     int wts_format,
                                                                     const nm_mosaic_record *__restrict__ records,
                                                                     const float *__restrict__ gains, long long tile_cap,
@@ -299,7 +287,7 @@ bool tile_cap_ok(long long tile_cap) { return tile_cap >= 1 && tile_cap <= MAX_T
 bool bands_args_ok(int n, const void *tiles, long long tile_cap, const void *records, const void *canvas, int cw, int ch,
                    int R, double sigma, const void *workspace)
 {
-    return n >= 1 && n <= MAX_FRAMES && tile_cap_ok(tile_cap) && cw >= 1 && cw <= SIZE_LIMIT && ch >= 1 && ch <= SIZE_LIMIT &&
+    return n >= 1 && n <= MAX_FRAMES && tile_cap_ok(tile_cap) && cw >= 1 && cw <= NM_SIZE_LIMIT && ch >= 1 && ch <= NM_SIZE_LIMIT &&
            R >= 0 && R <= MAX_R && (R == 0 || (std::isfinite(sigma) && sigma > 0.0)) && tiles && records && canvas &&
            workspace && ((reinterpret_cast<size_t>(workspace) | reinterpret_cast<size_t>(tiles)) & 15) == 0;
 }
@@ -340,7 +328,7 @@ extern "C" {
 
 size_t nm_mosaic_bands_workspace_bytes(int n, long long tile_cap, int cw, int ch)
 {
-    if (n < 1 || n > MAX_FRAMES || !tile_cap_ok(tile_cap) || cw < 1 || cw > SIZE_LIMIT || ch < 1 || ch > SIZE_LIMIT) return 0;
+    if (n < 1 || n > MAX_FRAMES || !tile_cap_ok(tile_cap) || cw < 1 || cw > NM_SIZE_LIMIT || ch < 1 || ch > NM_SIZE_LIMIT) return 0;
     return workspace_bytes(n, tile_cap, cw, ch);
 }
 
@@ -357,19 +345,12 @@ int nm_mosaic_warp_tiles(int n, const unsigned char *const *frames, int fw, int 
                          int mask_format, const void *const *wts, int wts_format, const nm_mosaic_record *records,
                          const float *gains, float *tiles, long long tile_cap, int *stats, void *stream)
 {
-    const auto scalar_fmt = [](int f) { return f == NM_TEX_U8N || f == NM_TEX_F32; };
-    if (n < 1 || n > MAX_FRAMES || fw < 1 || fw > SIZE_LIMIT || fh < 1 || fh > SIZE_LIMIT || !scalar_fmt(mask_format) ||
+    if (n < 1 || n > MAX_FRAMES || fw < 1 || fw > NM_SIZE_LIMIT || fh < 1 || fh > NM_SIZE_LIMIT || !scalar_fmt(mask_format) ||
         !scalar_fmt(wts_format) || !tile_cap_ok(tile_cap))
         return (int)hipErrorInvalidValue;
-    if (!frames || !masks || !wts || !records || !tiles || !stats || (reinterpret_cast<size_t>(tiles) & 15))
-        return (int)hipErrorInvalidValue;
-    WtArgs a;
-    for (int k = 0; k < MAX_FRAMES; ++k) {
-        if (k < n && (!frames[k] || !masks[k] || !wts[k])) return (int)hipErrorInvalidValue;
-        a.frames[k] = k < n ? frames[k] : nullptr;
-        a.masks[k] = k < n ? masks[k] : nullptr;
-        a.wts[k] = k < n ? wts[k] : nullptr;
-    }
+    if (!records || !tiles || !stats || (reinterpret_cast<size_t>(tiles) & 15)) return (int)hipErrorInvalidValue;
+    FrameArgs a;
+    if (!fill_frame_args(a, n, frames, masks, wts)) return (int)hipErrorInvalidValue;
     const auto kernel = gains ? mosaic_warp_tiles_kernel<true> : mosaic_warp_tiles_kernel<false>;
     hipLaunchKernelGGL(kernel, dim3(fill_grid()), dim3(THREADS), 0, nm_stream(stream), a, n, fw, fh, mask_format, wts_format,
                        records, gains, tile_cap, reinterpret_cast<float4 *>(tiles), stats);

@@ -3,10 +3,10 @@
 // The gained blend that applies the gains is nm_transform_blend_batch_gain (nm_mosaic.hip). On the caller's stream, no
 // allocation, no synchronisation, no host read, no workspace; no kernel waits for another workgroup:
 //   measure  ONE memset node (the L x 7 sums to zero) and ONE launch whatever L is: the 64 frame pointers (512 B) and the
-//            links' frame indices (2 x 256 B) travel as kernel arguments. Grid (parts, L): frame a's lattice is cut into the
-//            verification's tiles of 64 columns x 32 rows, and a link's tiles are dealt to its `parts` workgroups of four
-//            waves (parts x L ~ 4096 workgroups when the lattice has that many tiles, so one link alone spreads over up to
-//            256). A wave takes a lattice row, its lanes 64 neighbouring lattice columns: one uchar4 of frame a (at stride 1
+//            links' frame indices (2 x 256 B) travel as kernel arguments. Grid (parts, L): the lattice walk over frame a
+//            (one of three copies: nm_lattice.hpp), a link's tiles dealt to its `parts` workgroups of four waves (parts x
+//            L ~ 4096 workgroups when the lattice has that many tiles, so one link alone spreads over up to 256). A wave
+//            takes a lattice row, its lanes 64 neighbouring lattice columns: one uchar4 of frame a (at stride 1
 //            a coalesced 256-byte read), one projection, four gathered uchar4 taps of frame b. The seven sums are integers:
 //            u64 per lane -> nmw::block_totals -> one vector atomic add per workgroup and sum. Integer adds commute, so
 //            the totals do not depend on arrival order.
@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "nm_common.hpp"
+#include "nm_lattice.hpp"
 #include "nm_mosaic_exposure_math.hpp"
 #include "nm_pair_batch.hpp"
 #include "../../include/nm_abi.h"
@@ -26,15 +27,12 @@
 namespace {
 
 using namespace nmx;
+using namespace nmlat;
 
 static_assert(NM_EXPOSURE_MAX_LINKS == NM_MOSAIC_ADJUST_MAX_LINKS, "exposure links follow the adjustment's convention");
 
-constexpr int THREADS = 256, WAVES = THREADS / 64;
-constexpr int TILE_W = 64, TILE_H = 32;     // the verification's tile walk
 constexpr int MAX_PARTS = 256;              // workgroups per link at most
 constexpr int GRID_TARGET = 4096;           // workgroups per launch aimed at: 16 per CU
-constexpr long long MAX_LATTICE = 1ll << 28;
-constexpr int SIZE_LIMIT = 32767;
 constexpr int SOLVE_THREADS = 128;          // > MAX_FRAMES: thread n owns the right-hand side
 
 struct SumsArgs {                           // 64 pointers and the links' frames: 1 KB of kernel arguments
@@ -58,7 +56,7 @@ __global__ __launch_bounds__(THREADS) void mosaic_exposure_sums_kernel(const Sum
     if (!nml::usable(link_status ? link_status[l] : 1, Hl)) return;      // uniform: the memset's zeros stay
     const Frames F{A.frames[A.X.a[l]], A.frames[A.X.b[l]], mask, fw, fh};
     u64 s[SUMS] = {0, 0, 0, 0, 0, 0, 0};
-    for (int t = blockIdx.x; t < tiles; t += gridDim.x) {
+    for (int t = blockIdx.x; t < tiles; t += gridDim.x) {        // the lattice walk: one of three copies (nm_lattice.hpp)
         const int u = (t % tiles_x) * TILE_W + lane, v0 = (t / tiles_x) * TILE_H;
         if (u < lw)
             for (int r = wave; r < TILE_H && v0 + r < lh; r += WAVES)
@@ -124,10 +122,7 @@ bool links_ok(int n, int L, const int *link_a, const int *link_b)
 bool sums_args_ok(int n, int L, const unsigned char *const *frames, const int *link_a, const int *link_b, int fw, int fh,
                   const float *H, int stride, int lo, int hi, const void *sums)
 {
-    if (!links_ok(n, L, link_a, link_b) || fw < 1 || fw > SIZE_LIMIT || fh < 1 || fh > SIZE_LIMIT || stride < 1 ||
-        stride > 64 || lo < 0 || lo > hi || hi > 255)
-        return false;
-    if ((long long)(fw / stride) * (long long)(fh / stride) > MAX_LATTICE) return false;
+    if (!links_ok(n, L, link_a, link_b) || !lattice_ok(fw, fh, stride) || lo < 0 || lo > hi || hi > 255) return false;
     return nmp::tables_ok(n, {frames}, {}, {H, sums});
 }
 
@@ -159,17 +154,16 @@ extern "C" int nm_mosaic_exposure_sums_dev(int n, int L, const unsigned char *co
 {
     if (!sums_args_ok(n, L, frames, link_a, link_b, fw, fh, H, stride, lo, hi, sums)) return (int)hipErrorInvalidValue;
     NM_RETURN_IF(hipMemsetAsync(sums, 0, (size_t)L * SUMS * sizeof(u64), nm_stream(stream)));
-    const int lw = fw / stride, lh = fh / stride;
-    const int tiles_x = nm_divup(lw, TILE_W), tiles = tiles_x * nm_divup(lh, TILE_H);
-    if (tiles == 0) return 0;                                    // a stride beyond the frame: an empty lattice, all sums 0
+    const Lattice T = lattice_of(fw, fh, stride);
+    if (T.tiles == 0) return 0;                                    // a stride beyond the frame: an empty lattice, all sums 0
     int parts = nm_divup(GRID_TARGET, L);
     parts = parts > MAX_PARTS ? MAX_PARTS : parts;
-    parts = parts > tiles ? tiles : parts;
+    parts = parts > T.tiles ? T.tiles : parts;
     SumsArgs A;
     for (int k = 0; k < MAX_FRAMES; ++k) A.frames[k] = k < n ? reinterpret_cast<const uchar4 *>(frames[k]) : nullptr;
     A.X = link_index(L, link_a, link_b);
     hipLaunchKernelGGL(mosaic_exposure_sums_kernel, dim3(parts, L), dim3(THREADS), 0, nm_stream(stream), A, fw, fh, mask, H,
-                       link_status, stride, lo, hi, lw, lh, tiles_x, tiles, sums);
+                       link_status, stride, lo, hi, T.lw, T.lh, T.tiles_x, T.tiles, sums);
     NM_LAUNCH_CHECK();
     return 0;
 }
@@ -179,15 +173,15 @@ extern "C" int nm_mosaic_exposure_sums_host(int n, int L, const unsigned char *c
                                             const int *link_status, int stride, int lo, int hi, unsigned long long *sums)
 {
     if (!sums_args_ok(n, L, frames, link_a, link_b, fw, fh, H, stride, lo, hi, sums)) return (int)hipErrorInvalidValue;
-    const int lw = fw / stride, lh = fh / stride;
+    const Lattice T = lattice_of(fw, fh, stride);
     for (int l = 0; l < L; ++l) {
         u64 *s = sums + (size_t)l * SUMS;
         for (int q = 0; q < SUMS; ++q) s[q] = 0;
         if (!nml::usable(link_status ? link_status[l] : 1, H + 9 * l)) continue;
         const Frames F{reinterpret_cast<const uchar4 *>(frames[link_a[l]]), reinterpret_cast<const uchar4 *>(frames[link_b[l]]),
                        mask, fw, fh};
-        for (int v = 0; v < lh; ++v)
-            for (int u = 0; u < lw; ++u) add_pixel(F, H + 9 * l, lo, hi, stride * u + stride / 2, stride * v + stride / 2, s);
+        for (int v = 0; v < T.lh; ++v)
+            for (int u = 0; u < T.lw; ++u) add_pixel(F, H + 9 * l, lo, hi, stride * u + stride / 2, stride * v + stride / 2, s);
     }
     return 0;
 }
