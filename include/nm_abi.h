@@ -1437,6 +1437,49 @@ NM_API int nm_mosaic_bands_host(int n, const float *tiles, long long tile_cap, c
                                 unsigned char *canvas, int cw, int ch, float *canvas_wts, int R, double sigma,
                                 void *workspace);
 
+/* ---- Median mosaic composite (no reference counterpart): a per-pixel order statistic over the stack of tiles that
+ * nm_mosaic_warp_tiles wrote. Whatever shows in fewer than half of the frames valid at a canvas pixel (an instrument, a
+ * bubble, a highlight moving over a still background) is rejected there; the feather blend shows it as a ghost and the
+ * two-band blend as a patch cut along a seam. ONE launch, plus one single-workgroup launch that zeroes counts only when
+ * counts is given (a kernel, not a memset node: see DESIGN.md section 7); on `stream` with no
+ * allocation, no synchronisation and no host read, no workspace, no workgroup waits for another: capturable into a HIP
+ * graph behind nm_mosaic_place_f32, nm_mosaic_gains_dev and nm_mosaic_warp_tiles.
+ *
+ * DEFINITION. tiles, tile_cap and records as nm_mosaic_bands_dev takes them.
+ *   Frames and samples. Frame k is USED exactly as in the two-band blend: placed, nw > 0, nh > 0 and nw * nh (in 64-bit) <=
+ *   tile_cap. For canvas pixel (X, Y) and a used frame whose rectangle [tx, tx + nw) x [ty, ty + nh) (clipped to the canvas
+ *   in 64-bit) contains it, the sample is t_k = tiles[k * tile_cap + (Y - ty) * nw + (X - tx)] = (C_B, C_G, C_R, w).
+ *   Key. y_k = (0.07f * C_B + 0.72f * C_G) + 0.21f * C_R: three fp32 products and two fp32 sums, each rounded, no fma
+ *   (numpy float32 reproduces it bit for bit).
+ *   Validity. v_k = w > w_min && w <= FLT_MAX && y_k is finite. m is the number of valid frames at the pixel. Where
+ *   m == 0, every output at that pixel keeps its contents.
+ *   Median frame. rank(k) = #{ valid j : y_j < y_k, or y_j == y_k and j < k }: a total order (+0 and -0 are equal keys
+ *   and fall to the index), so any selection algorithm gives the same answer. k~ is the valid frame of rank
+ *   floor((m - 1) / 2), the LOWER median.
+ *   Inliers. A valid k is an inlier when fabsf(y_k - y_k~) <= tau, with one fp32 subtraction. s is the number of inliers;
+ *   k~ is one, so s >= 1.
+ *   Modes. NM_MEDIAN_SELECT: out = C_k~ and the weight written is w_k~. NM_MEDIAN_MEAN: over the inliers in index order,
+ *   from 0, num_c = fmaf(w_k, C_k,c, num_c), den = den + w_k; out_c = num_c / den and the weight written is den.
+ *   Stores. The byte stored is nm_u8_sat(out_c * 255.9999f), alpha 255. canvas_wts (optional, fp32 cw x ch) receives the
+ *   weight; support (optional, unsigned char cw x ch) receives s; label (optional, unsigned char cw x ch) receives k~. A
+ *   pixel with m > 0 is overwritten, not accumulated into.
+ *   Counts. counts (optional, device, n x 2 unsigned 64-bit; zeroed by the call): counts[2 k] is the number of
+ *   canvas pixels at which frame k is valid, counts[2 k + 1] the number at which it is valid but not an inlier. Exact
+ *   integers, whatever the scheduling: a client reads from them which frames hold a moving object.
+ *   Refused with hipErrorInvalidValue before any device memory is touched: n outside [1, NM_MOSAIC_MAX_BATCH], tile_cap
+ *   outside [1, 2^30], cw or ch outside [1, 32767], an unknown mode, w_min negative or not finite, tau negative or NaN
+ *   (+inf is allowed: every valid frame is an inlier), a NULL tiles, records or canvas, tiles not 16-byte aligned.
+ * nm_mosaic_median_host: the same with every pointer in host memory, compiled from the same functions
+ *   (csrc/nm_mosaic_median_math.hpp): every output identical to the device's bit for bit.                             */
+#define NM_MEDIAN_SELECT 0
+#define NM_MEDIAN_MEAN 1
+NM_API int nm_mosaic_median_dev(int n, const float *tiles, long long tile_cap, const nm_mosaic_record *records,
+                                unsigned char *canvas, int cw, int ch, float *canvas_wts, int mode, float w_min, float tau,
+                                unsigned char *support, unsigned char *label, unsigned long long *counts, void *stream);
+NM_API int nm_mosaic_median_host(int n, const float *tiles, long long tile_cap, const nm_mosaic_record *records,
+                                 unsigned char *canvas, int cw, int ch, float *canvas_wts, int mode, float w_min, float tau,
+                                 unsigned char *support, unsigned char *label, unsigned long long *counts);
+
 /* ---- Link proposal: which frame pairs of a sequence to link at all (no reference counterpart). Two steps, both on
  * `stream` with no allocation, no synchronisation and no host read -- capturable into a HIP graph.
  * nm_link_votes_dev_u8: the u8 matcher's ratio test for ALL ordered pairs of n in [1, NM_LINK_PROPOSE_MAX_FRAMES] frames,

@@ -161,6 +161,8 @@ _SIGNATURES = {
     "nm_mosaic_warp_tiles": (_I, [_I, _P, _I, _I, _P, _I, _P, _I, _P, _P, _P, C.c_longlong, _P, _P]),
     "nm_mosaic_bands_dev": (_I, [_I, _P, C.c_longlong, _P, _P, _I, _I, _P, _I, C.c_double, _P, _P]),
     "nm_mosaic_bands_host": (_I, [_I, _P, C.c_longlong, _P, _P, _I, _I, _P, _I, C.c_double, _P]),
+    "nm_mosaic_median_dev": (_I, [_I, _P, C.c_longlong, _P, _P, _I, _I, _P, _I, _F, _F, _P, _P, _P, _P]),
+    "nm_mosaic_median_host": (_I, [_I, _P, C.c_longlong, _P, _P, _I, _I, _P, _I, _F, _F, _P, _P, _P]),
     "nm_link_votes_workspace_bytes": (_SZ, [_I, _I]),
     "nm_link_votes_dev_u8": (_I, [_I, _P, _P, _I, _F, _P, _P, _P]),
     "nm_link_votes_host_u8": (_I, [_I, _P, _P, _I, _F, _P]),
@@ -2280,6 +2282,88 @@ def mosaic_blend_bands(canvas, canvas_wts, frames, masks, wts, records, gains=No
     tiles, stats = mosaic_warp_tiles(frames, masks, wts, records, gains=gains, tile_cap=tile_cap, tiles=tiles, stats=stats)
     workspace = mosaic_bands(canvas, canvas_wts, tiles, records, R=R, sigma=sigma, workspace=workspace)
     return tiles, stats, workspace
+
+
+MEDIAN_SELECT, MEDIAN_MEAN = 0, 1
+# The default inlier half-width, in units of the key (a luminance in [0, 1]). A parameter, not a result: chosen on the
+# synthetic loop-closure views of tests/median_ref.py ("Median composite"), not on real footage.
+MEDIAN_TAU = 0.05
+
+
+def _median_check(n, tile_cap, cw, ch, mode, w_min, tau):
+    _bands_check(n, tile_cap, cw, ch, 0, 1.0)
+    if mode not in (MEDIAN_SELECT, MEDIAN_MEAN):
+        raise NmError("mosaic median: unknown mode %r" % (mode,))
+    if not (math.isfinite(w_min) and w_min >= 0):
+        raise NmError("mosaic median: w_min %r must be finite and not negative" % (w_min,))
+    if not tau >= 0:
+        raise NmError("mosaic median: tau %r must not be negative or NaN" % (tau,))
+
+
+def mosaic_median(canvas, canvas_wts, tiles, records, mode=MEDIAN_SELECT, w_min=0.0, tau=MEDIAN_TAU, support=None, label=None,
+                  counts=None):
+    """Median composite of the tiles of mosaic_warp_tiles into the canvas IN PLACE (nm_mosaic_median_dev): per canvas pixel
+    the frame of lower-median key among the valid frames (w > w_min), either its own sample (MEDIAN_SELECT) or the weighted
+    mean of the frames whose key lies within tau of its key (MEDIAN_MEAN). One launch on the current stream, plus one tiny
+    zeroing launch when counts is given; no workspace, no host read. canvas uint8 device (ch, cw, 4); canvas_wts float32 (ch, cw) or
+    None; tiles float32 (n, tile_cap, 4); records int32 (n, 16). Optional outputs: support / label uint8 (ch, cw) (the
+    number of inliers / the median frame), counts int64 (n, 2) (pixels at which frame k is valid / valid but no inlier). A
+    pixel with a valid frame is overwritten, every other keeps its contents. The default tau was chosen on synthetic views
+    (MEDIAN_TAU); tune it on real footage. Returns counts."""
+    torch = _torch()
+    if tiles.dim() != 3 or tiles.shape[2] != 4:
+        raise NmError("mosaic_median: tiles must be float32 (n, tile_cap, 4)")
+    n, tile_cap = tiles.shape[0], tiles.shape[1]
+    cw, ch = _bands_canvas_shape(tuple(canvas.shape), None if canvas_wts is None else tuple(canvas_wts.shape))
+    _median_check(n, tile_cap, cw, ch, mode, w_min, tau)
+    if tuple(records.shape) != (n, 16) or records.dtype != torch.int32:
+        raise NmError("mosaic_median: records must be int32 (n, 16)")
+    if any(p is not None and tuple(p.shape) != (ch, cw) for p in (support, label)) or \
+            (counts is not None and counts.numel() != 2 * n):
+        raise NmError("mosaic_median: support and label must be uint8 (ch, cw) and counts int64 (n, 2)")
+    _on_current_device([canvas, tiles, records] + [t for t in (canvas_wts, support, label, counts) if t is not None],
+                       "mosaic_median")
+    opt = lambda t, dtype: _dev(t, dtype) if t is not None else None
+    _check(lib().nm_mosaic_median_dev(n, _dev(tiles, torch.float32), tile_cap, _dev(records, torch.int32),
+                                      _dev(canvas, torch.uint8), cw, ch, opt(canvas_wts, torch.float32), int(mode),
+                                      float(w_min), float(tau), opt(support, torch.uint8), opt(label, torch.uint8),
+                                      opt(counts, torch.int64), _stream()), "nm_mosaic_median_dev")
+    return counts
+
+
+def mosaic_median_host(canvas, canvas_wts, tiles, records, mode=MEDIAN_SELECT, w_min=0.0, tau=MEDIAN_TAU, support=None,
+                       label=None, counts=None):
+    """mosaic_median on the host (nm_mosaic_median_host, the same functions): numpy arrays written IN PLACE, canvas
+    (ch, cw, 4) uint8, canvas_wts (ch, cw) float32 or None, support / label (ch, cw) uint8 or None, counts (n, 2) uint64 or
+    None; bit-identical to the device."""
+    import numpy as np
+    tiles, records = np.ascontiguousarray(tiles, dtype=np.float32), np.ascontiguousarray(records, dtype=np.int32)
+    if tiles.ndim != 3 or tiles.shape[2] != 4 or records.shape != (tiles.shape[0], 16):
+        raise NmError("mosaic_median_host: tiles float32 (n, tile_cap, 4) and records int32 (n, 16) expected")
+    n, tile_cap = tiles.shape[0], tiles.shape[1]
+    for a, dt in ((canvas, np.uint8), (canvas_wts, np.float32), (support, np.uint8), (label, np.uint8), (counts, np.uint64)):
+        if a is not None and (a.dtype != dt or not a.flags.c_contiguous or not a.flags.writeable):
+            raise NmError("mosaic_median_host: outputs must be contiguous, writeable and of their documented types")
+    cw, ch = _bands_canvas_shape(canvas.shape, None if canvas_wts is None else canvas_wts.shape)
+    _median_check(n, tile_cap, cw, ch, mode, w_min, tau)
+    if any(p is not None and p.shape != (ch, cw) for p in (support, label)) or (counts is not None and counts.size != 2 * n):
+        raise NmError("mosaic_median_host: support and label must be (ch, cw) and counts (n, 2)")
+    tl = _aligned_host(tiles.nbytes, np)
+    tl[:] = tiles.reshape(-1).view(np.uint8)
+    ptr = _pair_host_ptr
+    _check(lib().nm_mosaic_median_host(n, tl.ctypes.data, tile_cap, records.ctypes.data, canvas.ctypes.data, cw, ch,
+                                       ptr(canvas_wts), int(mode), float(w_min), float(tau), ptr(support), ptr(label),
+                                       ptr(counts)), "nm_mosaic_median_host")
+
+
+def mosaic_blend_median(canvas, canvas_wts, frames, masks, wts, records, gains=None, mode=MEDIAN_SELECT, w_min=0.0,
+                        tau=MEDIAN_TAU, tile_cap=None, tiles=None, stats=None, support=None, label=None, counts=None):
+    """mosaic_warp_tiles, then mosaic_median: two launches on the current stream (and one tiny zeroing launch when counts is given),
+    no host read. Returns (tiles, stats) for reuse in the next call."""
+    tiles, stats = mosaic_warp_tiles(frames, masks, wts, records, gains=gains, tile_cap=tile_cap, tiles=tiles, stats=stats)
+    mosaic_median(canvas, canvas_wts, tiles, records, mode=mode, w_min=w_min, tau=tau, support=support, label=label,
+                  counts=counts)
+    return tiles, stats
 
 
 LINK_PROPOSE_MAX_FRAMES = _PAIR_MAX_BATCH

@@ -1,8 +1,8 @@
-// nm_mosaic_batch.hpp -- what the mosaic's blend kernels (nm_mosaic.hip, nm_mosaic_bands.hip) take the same way: n <=
-// MAX_FRAMES frames, canvas tiles of CANVAS_TILE_W x CANVAS_TILE_H pixels (a canvas row per wave), and the sampler's three
-// pointer tables as kernel arguments, on nm_pair_batch.hpp's helpers. The canvas walk (64-bit clipping, staging, tile step,
-// ballot) is NOT here: transform_blend_batch_kernel and mosaic_bands_canvas_kernel each write it out, and
-// nm_mosaic_bands_host the clipping a third time. Change one, change the others.
+// nm_mosaic_batch.hpp -- what the mosaic's blend kernels (nm_mosaic.hip, nm_mosaic_bands.hip, nm_mosaic_median.hip) take the
+// same way: n <= MAX_FRAMES frames, canvas tiles of CANVAS_TILE_W x CANVAS_TILE_H pixels (a canvas row per wave), and the
+// sampler's three pointer tables as kernel arguments, on nm_pair_batch.hpp's helpers. The canvas walk (64-bit clipping,
+// staging, tile step, ballot) is NOT here: transform_blend_batch_kernel, mosaic_bands_canvas_kernel and mosaic_median_kernel
+// (two waves: 64 x 2 tiles) each write it out, and nm_mosaic_bands_host the clipping once more. Change one, change the others.
 #pragma once
 #include "nm_pair_batch.hpp"
 #include "../../include/nm_abi.h"

@@ -44,6 +44,9 @@ __device__ __forceinline__ T wave_inclusive_scan(T v)
     return v;
 }
 
+// Number of the wave's active lanes whose flag is set (every lane returns it): the sum of a flag without a butterfly.
+__device__ __forceinline__ int wave_count(bool flag) { return __popcll(__ballot(flag)); }
+
 // Set bits of a ballot below the own lane: the lane's rank among the wave's flagged lanes.
 __device__ __forceinline__ int lane_rank(unsigned long long ballot)
 {
