@@ -32,32 +32,18 @@ def warp_records(fw, fh, cw, ch, cap_w, cap_h):
                      rec(cw + 5, 2, cap_w, cap_h, 1), rec(1, 1, cap_w * cap_h + 1, 1, 1)])
 
 
-@pytest.mark.parametrize("fw,fh", [(67, 45), (131, 97)])
-@pytest.mark.parametrize("mask_u8,wts_u8", [(True, False), (False, True)])
-@pytest.mark.parametrize("gain_kind", ["none", "unit", "random"])
-def test_warp_tiles_equal_the_gained_blend_of_each_record_alone(nm, cuda, fw, fh, mask_u8, wts_u8, gain_kind):
+def check_warp_tiles(nm, cuda, frames, mask, wts, recs, d_gains, cap, cw, ch, want_stats):
+    """nm_mosaic_warp_tiles on device frames, mask and weights with the (n, 16) records `recs`: every used record's tile
+    against the canvas weights (exactly) and bytes that nm_transform_blend_batch_gain writes for that record alone, nothing
+    written beyond a rectangle or into a skipped frame's slot or outside the slots. Returns the sentinel-guarded tiles."""
     import torch
-    rng = np.random.default_rng(fw + 2 * mask_u8 + wts_u8)
-    cw, ch = fw + 40, fh + 30
-    cap_w, cap_h = fw + 6, fh + 6
-    cap = cap_w * cap_h
-    recs = warp_records(fw, fh, cw, ch, cap_w, cap_h)
     n = len(recs)
-    base = [_t(rng.integers(0, 256, (fh, fw, 4), dtype=np.uint8), cuda) for _ in range(2)]
-    frames = [base[k % 2] for k in range(n)]                               # repeated pointers
-    y, x = np.mgrid[0:fh, 0:fw]
-    disc = ((x - fw / 2) ** 2 / (fw / 2) ** 2 + (y - fh / 2) ** 2 / (fh / 2) ** 2) < 0.95
-    feather = (np.minimum(np.minimum(x, fw - 1 - x), np.minimum(y, fh - 1 - y)) / (fh / 2.0)).astype(F32)   # 0 on the border
-    mask = _t((disc * 255).astype(np.uint8) if mask_u8 else disc.astype(F32), cuda)
-    wts = _t(np.round(feather * 255).astype(np.uint8) if wts_u8 else feather, cuda)
-    gains = {"none": None, "unit": np.ones((n, 3), F32), "random": rng.uniform(0.5, 2.0, (n, 3)).astype(F32)}[gain_kind]
-    d_gains = None if gains is None else _t(gains, cuda)
     d_recs = _t(recs, cuda)
     whole = torch.full((n + 2, cap, 4), SENTINEL, dtype=torch.float32, device=cuda)
     tiles, stats = nm.mosaic_warp_tiles(frames, mask, wts, d_recs, gains=d_gains, tile_cap=cap, tiles=whole[1:n + 1])
     h = whole.cpu().numpy()
     assert (h[0] == SENTINEL).all() and (h[-1] == SENTINEL).all()
-    assert stats.cpu().tolist() == [4, 2]
+    assert stats.cpu().tolist() == want_stats
     t = h[1:n + 1]
     for k in range(n):
         tx, ty, nw, nh, placed = (int(v) for v in recs[k, 9:14])
@@ -85,6 +71,31 @@ def test_warp_tiles_equal_the_gained_blend_of_each_record_alone(nm, cuda, fw, fh
         outside = np.ones((ch, cw), bool)
         outside[cs] = False
         assert not hw[outside].any()
+    return whole
+
+
+@pytest.mark.parametrize("fw,fh", [(67, 45), (131, 97)])
+@pytest.mark.parametrize("mask_u8,wts_u8", [(True, False), (False, True)])
+@pytest.mark.parametrize("gain_kind", ["none", "unit", "random"])
+def test_warp_tiles_equal_the_gained_blend_of_each_record_alone(nm, cuda, fw, fh, mask_u8, wts_u8, gain_kind):
+    import torch
+    rng = np.random.default_rng(fw + 2 * mask_u8 + wts_u8)
+    cw, ch = fw + 40, fh + 30
+    cap_w, cap_h = fw + 6, fh + 6
+    cap = cap_w * cap_h
+    recs = warp_records(fw, fh, cw, ch, cap_w, cap_h)
+    n = len(recs)
+    base = [_t(rng.integers(0, 256, (fh, fw, 4), dtype=np.uint8), cuda) for _ in range(2)]
+    frames = [base[k % 2] for k in range(n)]                               # repeated pointers
+    y, x = np.mgrid[0:fh, 0:fw]
+    disc = ((x - fw / 2) ** 2 / (fw / 2) ** 2 + (y - fh / 2) ** 2 / (fh / 2) ** 2) < 0.95
+    feather = (np.minimum(np.minimum(x, fw - 1 - x), np.minimum(y, fh - 1 - y)) / (fh / 2.0)).astype(F32)   # 0 on the border
+    mask = _t((disc * 255).astype(np.uint8) if mask_u8 else disc.astype(F32), cuda)
+    wts = _t(np.round(feather * 255).astype(np.uint8) if wts_u8 else feather, cuda)
+    gains = {"none": None, "unit": np.ones((n, 3), F32), "random": rng.uniform(0.5, 2.0, (n, 3)).astype(F32)}[gain_kind]
+    d_gains = None if gains is None else _t(gains, cuda)
+    whole = check_warp_tiles(nm, cuda, frames, mask, wts, recs, d_gains, cap, cw, ch, [4, 2])
+    d_recs = _t(recs, cuda)
     if gain_kind == "unit":                                                 # x * 1.0f == x: the ungained tiles
         whole2 = torch.full((n + 2, cap, 4), SENTINEL, dtype=torch.float32, device=cuda)
         nm.mosaic_warp_tiles(frames, mask, wts, d_recs, gains=None, tile_cap=cap, tiles=whole2[1:n + 1])
@@ -230,7 +241,7 @@ def test_warp_tiles_and_bands_in_one_call_and_in_a_graph(nm, cuda):
 def test_measure_solve_place_tiles_bands_on_the_loop_closure_views(nm, cuda):
     """The ten loop-closure views with per-view channel factors in [0.8, 1.25] and maps perturbed by B.E2E_PERTURB_PX at the
     corners: measure -> solve -> place -> warp tiles -> bands, eagerly and as ONE HIP graph replayed on a second scene, bit
-    for bit. The mean squared Laplacian over the pixels with at least two valid frames, bands against feather against the
+    for bit. The eager canvas and weights equal nm_mosaic_bands_host on the device's own tiles and records. The mean squared Laplacian over the pixels with at least two valid frames, bands against feather against the
     winning frame alone (the last from the float64 model on the CPU): the device's bands mosaic is closer to the single frame
     than the device's feather mosaic is."""
     import ctypes as C
@@ -276,6 +287,11 @@ def test_measure_solve_place_tiles_bands_on_the_loop_closure_views(nm, cuda):
     eager = host()
     assert np.array_equal(eager[2], recs16) and np.array_equal(eager[1].view(np.uint32), gains_host.view(np.uint32))
     assert eager[3].tolist() == [K, 0]
+    # the device's own tiles and records through the host twin: the same canvas and weights, bit for bit
+    twin_c, twin_w = np.zeros((ch, cw, 4), np.uint8), np.zeros((ch, cw), F32)
+    nm.mosaic_bands_host(twin_c, twin_w, tiles.cpu().numpy(), eager[2], R=B.E2E_R, sigma=B.E2E_SIGMA)
+    assert np.array_equal(eager[4], twin_c) and np.array_equal(eager[5].view(np.int32), twin_w.view(np.int32))
+    assert twin_c.any() and twin_w.any()
     # sharpness: bands and feather from the device, the winning frame alone from the model
     fcanvas, fwts = torch.zeros_like(canvas), torch.zeros_like(cwts)
     nm.transform_blend_batch_gain(fcanvas, fwts, frames, ones, wts, records, gains=gains)

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import bands_ref as B
+import mosaic_edges_ref as E
 
 F32 = np.float32
 NS, RS = (1, 2, 3, 17, 64), (0, 1, 2, 7, 32)
@@ -124,10 +125,8 @@ def test_pixels_far_from_every_label_change_equal_the_winner(nm, R):
 
 
 def tie_case():
-    rng = np.random.default_rng(5)
-    a, b = B.texture(rng, 40, 30, holes=False), B.texture(rng, 40, 30, holes=False)
-    a[..., 3] = b[..., 3] = F32(1.5)
-    return [a, b], [(2, 2, 40, 30, 1), (2, 2, 40, 30, 1)], 1200
+    """two frames on one rectangle, every weight equal: mosaic_edges_ref.bands_tie_case, which the GPU edge test runs too"""
+    return E.bands_tie_case()[:3]
 
 
 def test_tied_weights_label_the_lower_index(nm):

@@ -9,6 +9,7 @@ import pytest
 
 import bands_ref as B
 import median_ref as M
+import mosaic_edges_ref as E
 
 F32 = np.float32
 INVALID = 1      # hipErrorInvalidValue
@@ -59,39 +60,36 @@ def test_rectangles_at_off_and_beyond_every_canvas_side(nm, mode):
     assert (md["counts"][:19, 0] > 0).all() and md["valid"][11, 60, 230]
 
 
-def grey(level, w, nw=9, nh=4):
-    t = np.empty((nh, nw, 4), F32)
-    t[..., :3], t[..., 3] = F32(level), F32(w)
-    return t
+grey = E.grey
 
 
 def test_equal_keys_and_signed_zeros_fall_to_the_index(nm):
-    recs, cap = [(1, 1, 9, 4, 1)] * 4, 36
-    tiles = [grey(0.5, 1.0 + k) for k in range(4)]                     # four equal keys: rank 1 is frame 1
-    got, md = check_against_model(nm, tiles, recs, cap, 12, 6, M.SELECT)
-    assert (got[3][1:5, 1:10] == 1).all() and (got[1][1:5, 1:10] == 2.0).all()
-    tiles = [grey(-0.0, 3.0), grey(0.0, 4.0), grey(-0.0, 5.0)]          # -0 == +0: rank 1 is frame 1, not a -0 frame
-    got, md = check_against_model(nm, tiles, recs[:3], cap, 12, 6, M.SELECT)
-    assert np.signbit(md["key"][0, 2, 2]) and not np.signbit(md["key"][1, 2, 2])
-    assert (got[3][1:5, 1:10] == 1).all() and (got[1][1:5, 1:10] == 4.0).all()
-    tiles = [grey(0.0, 3.0), grey(-0.0, 4.0), grey(0.7, 5.0), grey(-0.0, 6.0), grey(0.0, 7.0)]
-    got, _ = check_against_model(nm, tiles, recs + recs[:1], cap, 12, 6, M.SELECT)
+    """the stacks of mosaic_edges_ref.median_equal_greys, which the GPU edge test runs too"""
+    tiles, recs, cap, cw, ch = E.median_equal_greys(0)                  # four equal keys: rank 1 is frame 1
+    got, md = check_against_model(nm, tiles, recs, cap, cw, ch, M.SELECT)
+    assert len(tiles) == 4 and (got[3][1:5, 1:10] == 1).all() and (got[1][1:5, 1:10] == 2.0).all()
+    tiles, recs, cap, cw, ch = E.median_equal_greys(1)                  # -0 == +0: rank 1 is frame 1, not a -0 frame
+    got, md = check_against_model(nm, tiles, recs, cap, cw, ch, M.SELECT)
+    assert len(tiles) == 3 and np.signbit(md["key"][0, 2, 2]) and not np.signbit(md["key"][1, 2, 2])
+    assert np.signbit(md["key"][2, 2, 2]) and (got[3][1:5, 1:10] == 1).all() and (got[1][1:5, 1:10] == 4.0).all()
+    tiles, recs, cap, cw, ch = E.median_equal_greys(2)
+    got, md = check_against_model(nm, tiles, recs, cap, cw, ch, M.SELECT)
+    assert len(tiles) == 5 and (md["key"][:, 2, 2] == np.array([0, 0, md["key"][2, 2, 2], 0, 0], F32)).all()
     assert (got[3][1:5, 1:10] == 3).all()                               # order 0, 1, 3, 4, 2: rank 2 is frame 3
+    for q, (label, weight) in enumerate(E.EQUAL_GREYS_WANT):
+        got = M.run_host(nm, *E.median_equal_greys(q), M.SELECT)
+        assert (got[3][1:5, 1:10] == label).all() and (got[1][1:5, 1:10] == weight).all()
 
 
 @pytest.mark.parametrize("mode", MODES)
 def test_invalid_samples_nan_inf_and_the_weight_limits(nm, mode):
-    recs, cap = [(0, 0, 9, 4, 1)] * 6, 36
-    tiles = [grey(0.11 * (k + 1), 2.0) for k in range(6)]
-    tiles[0][0, 0, 2] = np.nan                       # a NaN colour
-    tiles[1][0, 1, 0] = np.inf                       # an infinite colour
-    tiles[2][0, 2, 1] = -np.inf                      # the other infinity
-    tiles[3][0, 3, 3] = F32(0.5)                     # w == w_min exactly: invalid
-    tiles[4][0, 4, 3] = np.inf                       # w = inf: invalid
-    tiles[4][0, 5, 3] = F32(M.FLT_MAX)               # w = FLT_MAX: valid
-    tiles[5][0, 6, 3] = np.nan                       # w NaN
-    tiles[5][0, 7, 3] = np.nextafter(F32(0.5), F32(1))   # the float after w_min: valid
-    got, md = check_against_model(nm, tiles, recs, cap, 9, 4, mode, w_min=0.5, tau=INF if mode == M.SELECT else 0.25)
+    tiles, recs, cap, cw, ch = E.median_limits_case()     # shared with the GPU edge test
+    assert np.isnan(tiles[0][0, 0, 2]) and tiles[1][0, 1, 0] == np.inf and tiles[2][0, 2, 1] == -np.inf      # colours
+    assert tiles[3][0, 3, 3] == F32(0.5) and tiles[4][0, 4, 3] == np.inf                # w == w_min exactly, w = inf: invalid
+    assert tiles[4][0, 5, 3] == F32(M.FLT_MAX) and np.isnan(tiles[5][0, 6, 3])          # w = FLT_MAX: valid; w NaN
+    assert tiles[5][0, 7, 3] == np.nextafter(F32(0.5), F32(1)) and (cw, ch) == (9, 4)   # the float after w_min: valid
+    got, md = check_against_model(nm, tiles, recs, cap, 9, 4, mode, w_min=E.LIMITS_W_MIN,
+                                  tau=INF if mode == M.SELECT else 0.25)
     assert md["m"][0].tolist() == [5, 5, 5, 5, 5, 6, 5, 6, 6]
     assert md["m"][1:].min() == 6
     for k, x in enumerate((0, 1, 2, 3, 4)):
@@ -99,9 +97,8 @@ def test_invalid_samples_nan_inf_and_the_weight_limits(nm, mode):
 
 
 def test_tau_zero_infinite_and_equal_to_a_key_difference(nm):
-    levels = (0.1, 0.3, 0.45, 0.7, 0.95)
-    recs, cap = [(2, 1, 9, 4, 1)] * 5, 36
-    tiles = [grey(v, 1.0 + k) for k, v in enumerate(levels)]
+    tiles, recs, cap = E.median_tau_case()[:3]            # shared with the GPU edge test, as are the taus
+    assert E.TAU_LEVELS == (0.1, 0.3, 0.45, 0.7, 0.95) and E.median_tau_case()[3:] == (14, 6) and E.LIMITS_W_MIN == 0.5
     ys = [M.key(t[0, 0, :3]) for t in tiles]
     for mode in MODES:
         got, md = check_against_model(nm, tiles, recs, cap, 14, 6, mode, tau=0.0)
@@ -109,6 +106,7 @@ def test_tau_zero_infinite_and_equal_to_a_key_difference(nm):
         got, md = check_against_model(nm, tiles, recs, cap, 14, 6, mode, tau=INF)
         assert (got[2][1:5, 2:11] == 5).all() and not md["counts"][:, 1].any()
         exact = float(np.abs(F32(ys[3] - ys[2])))                      # the fp32 difference itself: <= keeps frame 3
+        assert E.tau_values()["exact"] == exact and E.tau_values()["below"] == float(np.nextafter(F32(exact), F32(0)))
         got, md = check_against_model(nm, tiles, recs, cap, 14, 6, mode, tau=exact)
         assert (got[2][1:5, 2:11] == 3).all() and md["counts"][:, 1].tolist() == [36, 0, 0, 0, 36]
         below = float(np.nextafter(F32(exact), F32(0)))
