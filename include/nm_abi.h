@@ -1480,6 +1480,64 @@ NM_API int nm_mosaic_median_host(int n, const float *tiles, long long tile_cap, 
                                  unsigned char *canvas, int cw, int ch, float *canvas_wts, int mode, float w_min, float tau,
                                  unsigned char *support, unsigned char *label, unsigned long long *counts);
 
+/* ---- Frame masks and feather weights (no reference counterpart): per frame and per pixel, what is not scene at all (the
+ * black surround of an endoscope's disc, a saturated highlight, whatever a shared base plane rules out) and how much to
+ * trust the rest (a feather that falls to 0 towards the nearest such pixel). The planes are the mask / weight inputs of
+ * every later stage: nm_sift_arena_set_mask, the `mask > 0.5` planes of link verification, refinement and the exposure
+ * sums, masks[k] / wts[k] of nm_transform_blend_batch(_gain) and nm_mosaic_warp_tiles. TWO launches whatever n is, plus one
+ * single-workgroup launch that zeroes counts only when counts is given (a kernel, not a memset node: see the median
+ * composite above and DESIGN.md section 7); on `stream` with no allocation, no synchronisation and no host read, no
+ * workgroup waits for another: capturable into a HIP graph behind nm_frame_ingest_batch_f32.
+ *
+ * DEFINITION. frames: HOST table of n device pointers to fw x fh uchar4 (BGRA) frames, as nm_frame_ingest_batch_f32 takes
+ * them; pointers may repeat. For frame k and pixel p = (x, y):
+ *   Photometric test. mx = max(B, G, R) of the byte pixel; alpha is ignored. p is RAW-BAD when mx < lo (dark: outside the
+ *   optics) or mx > hi (saturated). lo = 0 turns the dark test off, hi = 255 the bright one.
+ *   Seeds. p is a SEED when base != NULL and base[y fw + x] == 0 (base: optional device plane, fw x fh unsigned chars,
+ *   shared by all frames, e.g. what nm_resample_mask_u8 made from the undistortion map; unconditional), or when p is
+ *   raw-bad and at least min_count pixels of the 3 x 3 window centred on p are raw-bad. The window includes p; window pixels
+ *   outside the frame do not count. min_count in [1, 9]; with 1 every raw-bad pixel is a seed. (The despeckle step: one dark
+ *   noise pixel does not punch a hole of radius margin.)
+ *   Clipped squared distance. S is the set of seeds of frame k and, when border != 0, every integer lattice point outside
+ *   [0, fw) x [0, fh). D(p) = min(R R, min over q in S of |p - q|^2): an exact integer in [0, R R], R in [1, 64]. A seed
+ *   farther than R in either axis cannot change it.
+ *   Outputs. VALID = D(p) > margin margin, margin in [0, R).
+ *     masks[k][p] = valid ? 255 : 0 (mask_format NM_TEX_U8N, unsigned char) or valid ? 1.0f : 0.0f (NM_TEX_F32): both
+ *       satisfy every consumer's rule.
+ *     wts[k][p]   = valid ? (sqrtf((float)D) - (float)margin) / (float)(R - margin) : 0.0f: the square root, the
+ *       subtraction and the division are fp32, each correctly rounded, no fma; the value lies in (0, 1].
+ *     dist2[k][p] = D (unsigned short).
+ *     counts[2 k] = the number of seeds inside frame k, counts[2 k + 1] its number of valid pixels (device, n x 2 unsigned
+ *       64-bit, zeroed by the call). Exact integers, whatever the scheduling.
+ *   masks, wts, dist2 are HOST tables of n device pointers to fw x fh planes; each of the three tables and counts is
+ *   optional (NULL), at least one must be given. Outputs must not overlap each other, the inputs or the workspace.
+ *   Input-only dependence. A frame's outputs depend on its pixels, base and the parameters alone: not on n, on its slot, on
+ *   the previous contents of any output or of the workspace, or on scheduling.
+ *   workspace: device, nm_frame_weights_workspace_bytes(n, fw, fh) bytes (0 for arguments out of range; one byte per pixel
+ *   with rows padded to 64, no alignment rule), no contents expected or preserved.
+ *   Refused with hipErrorInvalidValue before any device access: n outside [1, NM_FRAME_WEIGHTS_MAX_BATCH], fw or fh outside
+ *   [1, 32767], lo or hi outside [0, 255], min_count outside [1, 9], R outside [1, NM_FRAME_WEIGHTS_MAX_RADIUS], margin
+ *   outside [0, R), an unknown mask_format, no output requested, a NULL frames, a NULL among the first n entries of any
+ *   given table, a NULL workspace.
+ * nm_frame_weights_host: the same with every pointer in host memory, no workspace and no stream, compiled from the same
+ *   functions (csrc/nm_frame_weights_math.hpp): every output identical to the device's bit for bit.
+ * nm_frame_weights_set_grid_cap (tuning and tests, process-wide): both passes launch min(units, cap) workgroups that stride
+ *   over their units; cap >= 1 fixes the cap, any other value restores the default (8 per compute unit). Results are
+ *   identical for every cap. Returns the previous setting (0: the default).                                           */
+#define NM_FRAME_WEIGHTS_MAX_BATCH 64
+#define NM_FRAME_WEIGHTS_MAX_RADIUS 64
+NM_API size_t nm_frame_weights_workspace_bytes(int n, int fw, int fh);
+NM_API int nm_frame_weights_batch_dev(int n, const unsigned char *const *frames, int fw, int fh,
+                                      const unsigned char *base, int lo, int hi, int min_count, int border, int R,
+                                      int margin, void *const *masks, int mask_format, float *const *wts,
+                                      unsigned short *const *dist2, unsigned long long *counts, void *workspace,
+                                      void *stream);
+NM_API int nm_frame_weights_host(int n, const unsigned char *const *frames, int fw, int fh, const unsigned char *base,
+                                 int lo, int hi, int min_count, int border, int R, int margin, void *const *masks,
+                                 int mask_format, float *const *wts, unsigned short *const *dist2,
+                                 unsigned long long *counts);
+NM_API int nm_frame_weights_set_grid_cap(int cap);
+
 /* ---- Link proposal: which frame pairs of a sequence to link at all (no reference counterpart). Two steps, both on
  * `stream` with no allocation, no synchronisation and no host read -- capturable into a HIP graph.
  * nm_link_votes_dev_u8: the u8 matcher's ratio test for ALL ordered pairs of n in [1, NM_LINK_PROPOSE_MAX_FRAMES] frames,

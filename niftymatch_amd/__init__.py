@@ -163,6 +163,10 @@ _SIGNATURES = {
     "nm_mosaic_bands_host": (_I, [_I, _P, C.c_longlong, _P, _P, _I, _I, _P, _I, C.c_double, _P]),
     "nm_mosaic_median_dev": (_I, [_I, _P, C.c_longlong, _P, _P, _I, _I, _P, _I, _F, _F, _P, _P, _P, _P]),
     "nm_mosaic_median_host": (_I, [_I, _P, C.c_longlong, _P, _P, _I, _I, _P, _I, _F, _F, _P, _P, _P]),
+    "nm_frame_weights_workspace_bytes": (_SZ, [_I, _I, _I]),
+    "nm_frame_weights_batch_dev": (_I, [_I, _P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P]),
+    "nm_frame_weights_host": (_I, [_I, _P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P]),
+    "nm_frame_weights_set_grid_cap": (_I, [_I]),
     "nm_link_votes_workspace_bytes": (_SZ, [_I, _I]),
     "nm_link_votes_dev_u8": (_I, [_I, _P, _P, _I, _F, _P, _P, _P]),
     "nm_link_votes_host_u8": (_I, [_I, _P, _P, _I, _F, _P]),
@@ -2556,6 +2560,121 @@ def ingest_batch(frames, u=None, v=None, undistorted=False):
                                            arr([_dev(g) for g in gray]), arr([_dev(t) for t in und]) if und else None,
                                            _stream()), "nm_frame_ingest_batch_f32")
     return (gray, und) if undistorted else gray
+
+
+FRAME_WEIGHTS_MAX_BATCH, FRAME_WEIGHTS_MAX_RADIUS = 64, 64
+FRAME_WEIGHTS_KINDS = ("mask", "wts", "dist2")
+
+
+class FrameWeightsWorkspace(_PairWorkspace):
+    """Device scratch for nm_frame_weights_batch_dev: n frames of fw x fh (one byte per pixel, rows padded to 64)."""
+    _bytes_fn, _what, _shape_text = "nm_frame_weights_workspace_bytes", "frame-weights workspace", "n=%d fw=%d fh=%d"
+
+    def __init__(self, n, fw, fh, device):
+        self._alloc(device, n=n, fw=fw, fh=fh)
+
+
+def _frame_weights_check(n, fw, fh, lo, hi, R, margin, min_count, mask_format, want, counts):
+    if not 0 < n <= FRAME_WEIGHTS_MAX_BATCH:
+        raise NmError("frame weights: %d frames (1 .. %d)" % (n, FRAME_WEIGHTS_MAX_BATCH))
+    if not (1 <= fw <= _INGEST_SIZE_LIMIT and 1 <= fh <= _INGEST_SIZE_LIMIT):
+        raise NmError("frame weights: frame %dx%d outside [1, %d]" % (fw, fh, _INGEST_SIZE_LIMIT))
+    if any(int(v) != v for v in (lo, hi, R, margin, min_count)):
+        raise NmError("frame weights: lo, hi, R, margin and min_count are integers")
+    if not (0 <= lo <= 255 and 0 <= hi <= 255):
+        raise NmError("frame weights: lo %r and hi %r must lie in [0, 255]" % (lo, hi))
+    if not 1 <= min_count <= 9:
+        raise NmError("frame weights: min_count %r outside [1, 9]" % (min_count,))
+    if not 1 <= R <= FRAME_WEIGHTS_MAX_RADIUS:
+        raise NmError("frame weights: radius %r outside [1, %d]" % (R, FRAME_WEIGHTS_MAX_RADIUS))
+    if not 0 <= margin < R:
+        raise NmError("frame weights: margin %r outside [0, R)" % (margin,))
+    if mask_format not in (TEX_U8N, TEX_F32):
+        raise NmError("frame weights: mask_format must be TEX_U8N or TEX_F32")
+    want = tuple(want)
+    if any(w not in FRAME_WEIGHTS_KINDS for w in want) or len(set(want)) != len(want):
+        raise NmError("frame weights: want holds each of %r at most once" % (FRAME_WEIGHTS_KINDS,))
+    if not want and not counts:
+        raise NmError("frame weights: no output requested")
+    return want
+
+
+def frame_weights_batch(frames, lo=0, hi=255, R=32, margin=0, min_count=1, border=True, base=None, mask_format=TEX_U8N,
+                        want=("mask", "wts"), counts=False, workspace=None):
+    """Per-frame validity masks and feather weights of n = len(frames) <= FRAME_WEIGHTS_MAX_BATCH BGRA frames (uint8 device
+    (fh, fw, 4)) on the device (nm_frame_weights_batch_dev): two launches on the current stream whatever n is, plus one tiny
+    zeroing launch with counts=True; no host read. A pixel is a seed when base (optional uint8 (fh, fw) plane shared by all
+    frames) is 0 there, or when max(B, G, R) < lo or > hi there and in at least min_count pixels of its 3 x 3 window; D is
+    the squared distance to the nearest seed (with border: or lattice point outside the frame), clipped to R * R; a pixel
+    is valid when D > margin^2; mask = 255 / 1.0 where valid (mask_format TEX_U8N / TEX_F32), wts = (sqrt(D) - margin) /
+    (R - margin) where valid, else 0. want: which of "mask", "wts", "dist2" to compute. Returns the requested tensors in the
+    order of want, each ONE (n, fh, fw) allocation (mask uint8 or float32, wts float32, dist2 int16: the values are at most
+    4096, so the signed view holds them as they are), followed by the int64 (n, 2) counts (seeds, valid pixels) when
+    counts=True; a single result comes back bare. out[k] of a returned tensor goes straight into transform_blend_batch,
+    mosaic_warp_tiles and mosaic_blend_median. workspace: a FrameWeightsWorkspace (default: new)."""
+    torch = _torch()
+    frames = list(frames)
+    n = len(frames)
+    if not n or any(f.dim() != 3 or f.shape[2] != 4 or f.dtype != torch.uint8 for f in frames):
+        raise NmError("frame_weights_batch: frames must be (fh, fw, 4) uint8")
+    fh, fw = frames[0].shape[0], frames[0].shape[1]
+    if any(tuple(f.shape) != (fh, fw, 4) for f in frames):
+        raise NmError("frame_weights_batch: all frames must have one shape")
+    want = _frame_weights_check(n, fw, fh, lo, hi, R, margin, min_count, mask_format, want, counts)
+    if base is not None and (tuple(base.shape) != (fh, fw) or base.dtype != torch.uint8):
+        raise NmError("frame_weights_batch: base must be uint8 (fh, fw)")
+    device = _on_current_device(frames + ([base] if base is not None else []) +
+                                ([workspace.buf] if workspace is not None else []), "frame_weights_batch")
+    workspace = _pair_workspace(FrameWeightsWorkspace, workspace, device, n, fw, fh)
+    dtypes = {"mask": torch.uint8 if mask_format == TEX_U8N else torch.float32, "wts": torch.float32, "dist2": torch.int16}
+    out = {w: torch.empty((n, fh, fw), dtype=dtypes[w], device=device) for w in want}
+    cnt = torch.empty((n, 2), dtype=torch.int64, device=device) if counts else None
+    arr = lambda vals: (C.c_void_p * n)(*vals)
+    table = lambda w: arr([_dev(out[w][k]) for k in range(n)]) if w in out else None
+    _check(lib().nm_frame_weights_batch_dev(n, arr([_dev(f, torch.uint8) for f in frames]), fw, fh,
+                                            _dev(base, torch.uint8) if base is not None else None, int(lo), int(hi),
+                                            int(min_count), 1 if border else 0, int(R), int(margin), table("mask"),
+                                            int(mask_format), table("wts"), table("dist2"),
+                                            _dev(cnt, torch.int64) if counts else None, _dev(workspace.buf), _stream()),
+           "nm_frame_weights_batch_dev")
+    res = tuple(out[w] for w in want) + ((cnt,) if counts else ())
+    return res[0] if len(res) == 1 else res
+
+
+def frame_weights_host(frames, lo=0, hi=255, R=32, margin=0, min_count=1, border=True, base=None, mask_format=TEX_U8N,
+                       want=("mask", "wts"), counts=False):
+    """frame_weights_batch on the host (nm_frame_weights_host, the same functions): frames are numpy uint8 (fh, fw, 4) arrays,
+    base a uint8 (fh, fw) array or None. Returns numpy arrays in the same order: mask uint8 or float32, wts float32, dist2
+    uint16, each (n, fh, fw), and counts uint64 (n, 2); bit-identical to the device."""
+    import numpy as np
+    frames = [np.ascontiguousarray(f, dtype=np.uint8) for f in frames]
+    n = len(frames)
+    if not n or any(f.ndim != 3 or f.shape[2] != 4 for f in frames):
+        raise NmError("frame_weights_host: frames must be (fh, fw, 4) uint8")
+    fh, fw = frames[0].shape[0], frames[0].shape[1]
+    if any(f.shape != (fh, fw, 4) for f in frames):
+        raise NmError("frame_weights_host: all frames must have one shape")
+    want = _frame_weights_check(n, fw, fh, lo, hi, R, margin, min_count, mask_format, want, counts)
+    if base is not None:
+        base = np.ascontiguousarray(base, dtype=np.uint8)
+        if base.shape != (fh, fw):
+            raise NmError("frame_weights_host: base must be uint8 (fh, fw)")
+    dtypes = {"mask": np.uint8 if mask_format == TEX_U8N else np.float32, "wts": np.float32, "dist2": np.uint16}
+    out = {w: np.empty((n, fh, fw), dtypes[w]) for w in want}
+    cnt = np.empty((n, 2), np.uint64) if counts else None
+    table = lambda w: _pair_host_table([out[w][k] for k in range(n)]) if w in out else None
+    _check(lib().nm_frame_weights_host(n, _pair_host_table(frames), fw, fh, _pair_host_ptr(base), int(lo), int(hi),
+                                       int(min_count), 1 if border else 0, int(R), int(margin), table("mask"),
+                                       int(mask_format), table("wts"), table("dist2"), _pair_host_ptr(cnt)),
+           "nm_frame_weights_host")
+    res = tuple(out[w] for w in want) + ((cnt,) if counts else ())
+    return res[0] if len(res) == 1 else res
+
+
+def frame_weights_set_grid_cap(cap=0):
+    """Tuning and tests: the most workgroups either pass of frame_weights_batch launches (nm_frame_weights_set_grid_cap); 0
+    restores the default. Results do not depend on it. Returns the previous setting."""
+    return lib().nm_frame_weights_set_grid_cap(int(cap))
 
 
 SIFT_MAX_BATCH = 64
