@@ -1304,7 +1304,8 @@ NM_API int nm_mosaic_adjust_sums_host_f32(const float *src_x, const float *src_y
  *   sums: device, L x NM_EXPOSURE_SUMS unsigned 64-bit = (N, Sa_B, Sa_G, Sa_R, Sb_B, Sb_G, Sb_R): the number of counting
  *   pixels and the sums of their a_c and b_c. Integers: they depend on the link's inputs alone, never on L, n, the link's
  *   slot, the launch grouping or scheduling. A link with link_status[l] != 1 or a non-finite H_l gets seven zeros.
- *   ONE memset node (the sums) and ONE launch whatever L is: the frame pointers (512 B) and the link indices (512 B) travel
+ *   TWO launches whatever L is, the first a single workgroup that zeroes the sums (a kernel, not a memset node: see DESIGN.md
+ *   section 7, "Median composite"): the frame pointers (512 B) and the link indices (512 B) travel
  *   as kernel arguments; a link's lattice tiles are dealt to up to 256 workgroups, each ending in one vector atomic add per
  *   sum. Returns hipErrorInvalidValue, touching no device memory, for n not in [2, 64], L not in [1, 256], fw or fh not in
  *   [1, 32767], stride not in [1, 64], (fw / stride)(fh / stride) > 2^28, lo < 0, lo > hi, hi > 255, a NULL frames, link_a,

@@ -914,6 +914,125 @@ def _point_tables_dev(src_xs, src_ys, d_nAs, dst_xs, dst_ys, matches):
     return [_pair_dev_table(ts, dt) for ts, dt in ((src_xs, f), (src_ys, f), (d_nAs, i32), (dst_xs, f), (dst_ys, f), (matches, i32))]
 
 
+# ---- the frame-sequence stages (ingest, frame weights, link verify and refine, mosaic plan to median), DESIGN.md section 7 ----
+# A call takes n <= 64 frames of one shape as a list; every frame, map and canvas extent lies in [1, _SIZE_LIMIT], which is
+# NM_SIZE_LIMIT of csrc/nm_common.hpp; device wrappers want torch tensors on the current device, host twins take numpy. The
+# checks below read shapes and dtypes only, so they serve both.
+_SIZE_LIMIT = 32767
+_FRAMES_MAX_BATCH = _PAIR_MAX_BATCH
+
+
+def _opt(t, dtype=None):
+    """_dev of an optional tensor"""
+    return None if t is None else _dev(t, dtype)
+
+
+def _on_current_device(tensors, what):
+    """The device of a call: every tensor (None: an optional one that was not given) on the current CUDA device."""
+    tensors = [t for t in tensors if t is not None]
+    device = tensors[0].device
+    if any(t.device != device for t in tensors) or device.type != "cuda" or _torch().cuda.current_device() != device.index:
+        raise NmError("%s: all tensors must live on the current device" % what)
+    return device
+
+
+def _is_dtype(a, name):
+    return str(a.dtype).split(".")[-1] == name              # torch.uint8 and numpy's uint8 alike
+
+
+def _size_check(what, name, w, h):
+    if not (1 <= w <= _SIZE_LIMIT and 1 <= h <= _SIZE_LIMIT):
+        raise NmError("%s: %s %r x %r outside [1, %d]" % (what, name, w, h, _SIZE_LIMIT))
+
+
+def _frames_check(what, frames):
+    """(n, fw, fh) of a list of n in [1, 64] BGRA frames, uint8 and of one (fh, fw, 4) shape."""
+    n = len(frames)
+    if not 0 < n <= _FRAMES_MAX_BATCH:
+        raise NmError("%s: %d frames (1 .. %d)" % (what, n, _FRAMES_MAX_BATCH))
+    if any(len(f.shape) != 3 or f.shape[2] != 4 or not _is_dtype(f, "uint8") for f in frames):
+        raise NmError("%s: frames must be (fh, fw, 4) uint8" % what)
+    fh, fw = frames[0].shape[:2]
+    if any(tuple(f.shape) != (fh, fw, 4) for f in frames):
+        raise NmError("%s: all frames must have one shape" % what)
+    _size_check(what, "frame", fw, fh)
+    return n, fw, fh
+
+
+def _planes_check(what, planes, mask):
+    """(fw, fh) of gray planes and an optional mask, all of one (fh, fw) shape."""
+    shape = tuple(planes[0].shape)
+    if len(shape) != 2 or any(tuple(p.shape) != shape for p in planes + ([mask] if mask is not None else [])):
+        raise NmError("%s: planes of one (height, width) shape expected" % what)
+    return shape[1], shape[0]
+
+
+def _lattice_check(what, fw, fh, stride):
+    """A frame and the stride of the lattice the link and exposure stages walk over it (csrc/nm_lattice.hpp)."""
+    _size_check(what, "frame", fw, fh)
+    if int(stride) != stride or not 1 <= stride <= 64 or (fw // stride) * (fh // stride) > 1 << 28:
+        raise NmError("%s: stride %r outside [1, 64] or a lattice beyond 2^28 pixels" % (what, stride))
+
+
+def _scalar_planes(what, n, fw, fh, masks, wts):
+    """masks and wts as two lists of n (fh, fw) planes (one plane stands for every frame) and their formats, one per call."""
+    masks, wts = (list(v) if isinstance(v, (list, tuple)) else [v] * n for v in (masks, wts))
+    if len(masks) != n or len(wts) != n:
+        raise NmError("%s: %d frames, %d masks, %d weight planes" % (what, n, len(masks), len(wts)))
+    if any(tuple(t.shape) != (fh, fw) for t in masks + wts):
+        raise NmError("%s: masks and weights must be (fh, fw) planes" % what)
+    mfmt, wfmt = _tex_format(masks[0]), _tex_format(wts[0])
+    if any(_tex_format(t) != mfmt for t in masks) or any(_tex_format(t) != wfmt for t in wts):
+        raise NmError("%s: one mask format and one weight format per call" % what)
+    return masks, wts, mfmt, wfmt
+
+
+def _records_check(what, records, n):
+    if tuple(records.shape) != (n, 16) or not _is_dtype(records, "int32"):
+        raise NmError("%s: records must be int32 (n, 16)" % what)
+
+
+def _canvas_check(what, canvas, canvas_wts, wts_optional=False):
+    """(cw, ch) of a (ch, cw, 4) canvas and its (ch, cw) weights, which may be None where the stage says so."""
+    shape = tuple(canvas.shape)
+    if len(shape) != 3 or shape[2] != 4 or (canvas_wts is None and not wts_optional) or \
+            (canvas_wts is not None and tuple(canvas_wts.shape) != shape[:2]):
+        raise NmError("%s: canvas must be (ch, cw, 4) uint8 with (ch, cw) float32 weights%s"
+                      % (what, " or None" if wts_optional else ""))
+    _size_check(what, "canvas", shape[1], shape[0])
+    return shape[1], shape[0]
+
+
+def _composite_head(what, canvas, canvas_wts, tiles, records):
+    """What mosaic_bands and mosaic_median look at first: tiles (n, tile_cap, 4), records (n, 16), the canvas. Returns
+    (n, tile_cap, cw, ch)."""
+    if len(tiles.shape) != 3 or tiles.shape[2] != 4:
+        raise NmError("%s: tiles must be float32 (n, tile_cap, 4)" % what)
+    n, tile_cap = tiles.shape[:2]
+    _records_check(what, records, n)
+    return (n, tile_cap) + _canvas_check(what, canvas, canvas_wts, wts_optional=True)
+
+
+def _composite_head_host(what, canvas, canvas_wts, tiles, records, outputs=()):
+    """_composite_head of the host twins: tiles and records converted, every in-place output ((array, dtype) pairs) contiguous,
+    writeable and of its type, the tiles copied to 16-byte aligned memory. Returns (n, tile_cap, cw, ch, tiles, records)."""
+    import numpy as np
+    tiles, records = np.ascontiguousarray(tiles, dtype=np.float32), np.ascontiguousarray(records, dtype=np.int32)
+    for a, dt in ((canvas, np.uint8), (canvas_wts, np.float32)) + tuple(outputs):
+        if a is not None and (a.dtype != dt or not a.flags.c_contiguous or not a.flags.writeable):
+            raise NmError("%s: outputs must be contiguous, writeable and of their documented types" % what)
+    head = _composite_head(what, canvas, canvas_wts, tiles, records)
+    aligned = _aligned_host(tiles.nbytes, np)
+    aligned[:] = tiles.reshape(-1).view(np.uint8)
+    return head + (aligned, records)
+
+
+def _aligned_host(nbytes, np, align=16):
+    raw = np.empty(nbytes + align, np.uint8)
+    off = (-raw.ctypes.data) % align
+    return raw[off:off + nbytes]
+
+
 class _PairWorkspace:
     """Device scratch of a pair-batch stage: `buf` holds what the stage's *_workspace_bytes asks for the shape, which is
     kept as attributes. A subclass names the C function, the stage (for messages) and how it words a refused shape."""
@@ -1058,15 +1177,14 @@ class LinkVerifyWorkspace(_PairWorkspace):
         self._alloc(device, n=n)
 
 
-def _link_check(n, fw, fh, stride, min_inliers, max_area_ratio, min_overlap, min_ncc):
-    if not (1 <= fw <= 32767 and 1 <= fh <= 32767):
-        raise NmError("link verification: frame %r x %r outside [1, 32767]" % (fw, fh))
-    if int(stride) != stride or not 1 <= stride <= 64 or (fw // stride) * (fh // stride) > 1 << 28:
-        raise NmError("link verification: stride %r outside [1, 64] or a lattice beyond 2^28 pixels" % (stride,))
+def _link_check(grayAs, grayBs, mask, stride, min_inliers, max_area_ratio, min_overlap, min_ncc):
+    fw, fh = _planes_check("link verification", list(grayAs) + list(grayBs), mask)
+    _lattice_check("link verification", fw, fh, stride)
     if int(min_inliers) != min_inliers or min_inliers < 0:
         raise NmError("link verification: min_inliers %r must be an integer >= 0" % (min_inliers,))
     if not all(math.isfinite(v) for v in (max_area_ratio, min_overlap, min_ncc)) or max_area_ratio < 1:
         raise NmError("link verification: thresholds must be finite and max_area_ratio >= 1")
+    return fw, fh
 
 
 def link_verify_batch_dev(grayAs, grayBs, H, status=None, inliers=None, mask=None, stride=4, min_inliers=16,
@@ -1079,10 +1197,7 @@ def link_verify_batch_dev(grayAs, grayBs, H, status=None, inliers=None, mask=Non
     LINK_STATS. status_out goes to mosaic_plan, ransac_refit_batch_dev and the guided matchers as it is."""
     torch = _torch()
     n = _pair_count(grayAs, grayBs)
-    if any(t.ndim != 2 or t.shape != grayAs[0].shape for t in list(grayAs) + list(grayBs) + ([mask] if mask is not None else [])):
-        raise NmError("link verification: planes of one (height, width) shape expected")
-    fh, fw = grayAs[0].shape
-    _link_check(n, fw, fh, stride, min_inliers, max_area_ratio, min_overlap, min_ncc)
+    fw, fh = _link_check(grayAs, grayBs, mask, stride, min_inliers, max_area_ratio, min_overlap, min_ncc)
     _pair_model_shape(n, H.numel(), None if status is None else status.numel())
     if inliers is not None and inliers.numel() != n:
         raise NmError("link verification: inliers must hold n values")
@@ -1091,10 +1206,9 @@ def link_verify_batch_dev(grayAs, grayBs, H, status=None, inliers=None, mask=Non
     workspace = _pair_workspace(LinkVerifyWorkspace, workspace, device, n)
     st, why = (torch.empty(n, dtype=torch.int32, device=device) for _ in range(2))
     stats = torch.empty((n, 8), dtype=torch.float64, device=device)
-    opt = lambda t, dt: _dev(t, dt) if t is not None else None
     _check(lib().nm_link_verify_batch_dev_f32(n, _pair_dev_table(grayAs, torch.float32), _pair_dev_table(grayBs, torch.float32),
-                                              fw, fh, opt(mask, torch.float32), _dev(H, torch.float32),
-                                              opt(status, torch.int32), opt(inliers, torch.int32), int(stride),
+                                              fw, fh, _opt(mask, torch.float32), _dev(H, torch.float32),
+                                              _opt(status, torch.int32), _opt(inliers, torch.int32), int(stride),
                                               int(min_inliers), max_area_ratio, min_overlap, min_ncc, _dev(st), _dev(why),
                                               _dev(stats), _dev(workspace.buf), _stream()), "nm_link_verify_batch_dev_f32")
     return st, why, stats
@@ -1108,10 +1222,7 @@ def link_verify_host(grayAs, grayBs, H, status=None, inliers=None, mask=None, st
     n = _pair_count(grayAs, grayBs)
     grayAs, grayBs = (_pair_host_arrays(vs, np.float32, flat=False) for vs in (grayAs, grayBs))
     mask = None if mask is None else np.ascontiguousarray(mask, dtype=np.float32)
-    if any(a.ndim != 2 or a.shape != grayAs[0].shape for a in grayAs + grayBs + ([mask] if mask is not None else [])):
-        raise NmError("link verification: planes of one (height, width) shape expected")
-    fh, fw = grayAs[0].shape
-    _link_check(n, fw, fh, stride, min_inliers, max_area_ratio, min_overlap, min_ncc)
+    fw, fh = _link_check(grayAs, grayBs, mask, stride, min_inliers, max_area_ratio, min_overlap, min_ncc)
     H, status = _pair_host_model(n, H, status)
     inliers = None if inliers is None else np.ascontiguousarray(inliers, dtype=np.int32).reshape(-1)
     if inliers is not None and inliers.size != n:
@@ -1147,11 +1258,9 @@ class LinkRefineWorkspace(_PairWorkspace):
         self._alloc(device, n=n)
 
 
-def _link_refine_check(fw, fh, model, stride, iterations, min_pixels, max_step):
-    if not (1 <= fw <= 32767 and 1 <= fh <= 32767):
-        raise NmError("link refinement: frame %r x %r outside [1, 32767]" % (fw, fh))
-    if int(stride) != stride or not 1 <= stride <= 64 or (fw // stride) * (fh // stride) > 1 << 28:
-        raise NmError("link refinement: stride %r outside [1, 64] or a lattice beyond 2^28 pixels" % (stride,))
+def _link_refine_check(grayAs, grayBs, mask, model, stride, iterations, min_pixels, max_step):
+    fw, fh = _planes_check("link refinement", list(grayAs) + list(grayBs), mask)
+    _lattice_check("link refinement", fw, fh, stride)
     if model not in (LINK_REFINE_TRANSLATION, LINK_REFINE_AFFINE, LINK_REFINE_HOMOGRAPHY):
         raise NmError("link refinement: model %r is none of LINK_REFINE_TRANSLATION, _AFFINE, _HOMOGRAPHY" % (model,))
     if int(iterations) != iterations or not 1 <= iterations <= LINK_REFINE_MAX_ITERATIONS:
@@ -1160,6 +1269,7 @@ def _link_refine_check(fw, fh, model, stride, iterations, min_pixels, max_step):
         raise NmError("link refinement: min_pixels %r must be an integer >= 1" % (min_pixels,))
     if not math.isfinite(max_step) or not max_step > 0:
         raise NmError("link refinement: max_step %r must be finite and > 0" % (max_step,))
+    return fw, fh
 
 
 def link_refine_batch_dev(grayAs, grayBs, H, status=None, mask=None, model=LINK_REFINE_HOMOGRAPHY, stride=4, iterations=4,
@@ -1172,20 +1282,16 @@ def link_refine_batch_dev(grayAs, grayBs, H, status=None, mask=None, model=LINK_
     link_verify_batch_dev, mosaic_plan and the guided matchers as they are."""
     torch = _torch()
     n = _pair_count(grayAs, grayBs)
-    if any(t.ndim != 2 or t.shape != grayAs[0].shape for t in list(grayAs) + list(grayBs) + ([mask] if mask is not None else [])):
-        raise NmError("link refinement: planes of one (height, width) shape expected")
-    fh, fw = grayAs[0].shape
-    _link_refine_check(fw, fh, model, stride, iterations, min_pixels, max_step)
+    fw, fh = _link_refine_check(grayAs, grayBs, mask, model, stride, iterations, min_pixels, max_step)
     _pair_model_shape(n, H.numel(), None if status is None else status.numel())
     device = _pair_device(list(grayAs) + list(grayBs) + [H, status, mask, workspace.buf if workspace is not None else None], [])
     workspace = _pair_workspace(LinkRefineWorkspace, workspace, device, n)
     H_out = torch.empty((n, 9), dtype=torch.float32, device=device)
     st = torch.empty(n, dtype=torch.int32, device=device)
     stats = torch.empty((n, len(LINK_REFINE_STATS)), dtype=torch.float64, device=device)
-    opt = lambda t, dt: _dev(t, dt) if t is not None else None
     _check(lib().nm_link_refine_batch_dev_f32(n, _pair_dev_table(grayAs, torch.float32), _pair_dev_table(grayBs, torch.float32),
-                                              fw, fh, opt(mask, torch.float32), _dev(H, torch.float32),
-                                              opt(status, torch.int32), int(model), int(stride), int(iterations),
+                                              fw, fh, _opt(mask, torch.float32), _dev(H, torch.float32),
+                                              _opt(status, torch.int32), int(model), int(stride), int(iterations),
                                               int(min_pixels), max_step, _dev(H_out), _dev(st), _dev(stats),
                                               _dev(workspace.buf), _stream()), "nm_link_refine_batch_dev_f32")
     return H_out, st, stats
@@ -1200,10 +1306,7 @@ def link_refine_host(grayAs, grayBs, H, status=None, mask=None, model=LINK_REFIN
     n = _pair_count(grayAs, grayBs)
     grayAs, grayBs = (_pair_host_arrays(vs, np.float32, flat=False) for vs in (grayAs, grayBs))
     mask = None if mask is None else np.ascontiguousarray(mask, dtype=np.float32)
-    if any(a.ndim != 2 or a.shape != grayAs[0].shape for a in grayAs + grayBs + ([mask] if mask is not None else [])):
-        raise NmError("link refinement: planes of one (height, width) shape expected")
-    fh, fw = grayAs[0].shape
-    _link_refine_check(fw, fh, model, stride, iterations, min_pixels, max_step)
+    fw, fh = _link_refine_check(grayAs, grayBs, mask, model, stride, iterations, min_pixels, max_step)
     H, status = _pair_host_model(n, H, status)
     H_out = np.zeros((n, 9), np.float32)
     st = np.zeros(n, np.int32)
@@ -1714,16 +1817,15 @@ def sift_match_guided_u8_host(As, axs, ays, nAs, Bs, bxs, bys, nBs, H, status=No
                         ambiguity, max_distance, capA, capB, want_distance)
 
 
-MOSAIC_MAX_BATCH = 64
-_MOSAIC_SIZE_LIMIT = 32767
+MOSAIC_MAX_BATCH = _FRAMES_MAX_BATCH
 _MOSAIC_OFFSET_LIMIT = 1 << 20
 
 
 def _mosaic_check_geometry(n, fw, fh, cw, ch, ox, oy):
     if not 0 < n <= MOSAIC_MAX_BATCH:
         raise NmError("mosaic: %d frames (1 .. %d)" % (n, MOSAIC_MAX_BATCH))
-    if any(not 1 <= int(v) <= _MOSAIC_SIZE_LIMIT for v in (fw, fh, cw, ch)):
-        raise NmError("mosaic: frame %dx%d / canvas %dx%d outside [1, %d]" % (fw, fh, cw, ch, _MOSAIC_SIZE_LIMIT))
+    _size_check("mosaic", "frame", int(fw), int(fh))
+    _size_check("mosaic", "canvas", int(cw), int(ch))
     if any(abs(int(v)) >= _MOSAIC_OFFSET_LIMIT for v in (ox, oy)):
         raise NmError("mosaic: |ox|, |oy| must be below 2^20")
 
@@ -1740,10 +1842,7 @@ def mosaic_plan(H, status, fw, fh, cw, ch, ox, oy, M_first=None):
     _mosaic_check_geometry(n, fw, fh, cw, ch, ox, oy)
     if H.numel() != 9 * (n - 1):
         raise NmError("mosaic_plan: H must hold (n-1) x 9 floats")
-    tensors = [H] + ([status] if status is not None else []) + ([M_first] if M_first is not None else [])
-    device = H.device
-    if any(t.device != device for t in tensors) or device.type != "cuda" or torch.cuda.current_device() != device.index:
-        raise NmError("mosaic_plan: all tensors must live on the current device")
+    device = _on_current_device([H, status, M_first], "mosaic_plan")
     if status is not None and status.numel() != n - 1:
         raise NmError("mosaic_plan: status must hold n-1 values")
     if M_first is not None and M_first.numel() != 9:
@@ -1751,10 +1850,9 @@ def mosaic_plan(H, status, fw, fh, cw, ch, ox, oy, M_first=None):
     records = torch.empty((n, 16), dtype=torch.int32, device=device)
     chain = torch.empty((n, 9), dtype=torch.float32, device=device)
     extent = torch.empty(4, dtype=torch.float32, device=device)
-    _check(lib().nm_mosaic_plan_f32(n, _dev(H, torch.float32) if n > 1 else None,
-                                    _dev(status, torch.int32) if status is not None else None, fw, fh, cw, ch, ox, oy,
-                                    _dev(M_first, torch.float32) if M_first is not None else None, _dev(records),
-                                    _dev(chain), _dev(extent), _stream()), "nm_mosaic_plan_f32")
+    _check(lib().nm_mosaic_plan_f32(n, _dev(H, torch.float32) if n > 1 else None, _opt(status, torch.int32), fw, fh, cw, ch,
+                                    ox, oy, _opt(M_first, torch.float32), _dev(records), _dev(chain), _dev(extent), _stream()),
+           "nm_mosaic_plan_f32")
     return records, chain, extent
 
 
@@ -1775,7 +1873,7 @@ def mosaic_plan_host(H, status, fw, fh, cw, ch, ox, oy, M_first=None):
     records = np.zeros((n, 16), np.int32)
     chain = np.zeros((n, 9), np.float32)
     extent = np.zeros(4, np.float32)
-    ptr = lambda a: a.ctypes.data if a is not None else None
+    ptr = _pair_host_ptr
     _check(lib().nm_mosaic_plan_host_f32(n, ptr(H) if n > 1 else None, ptr(status), fw, fh, cw, ch, ox, oy, ptr(M_first),
                                          ptr(records), ptr(chain), ptr(extent)), "nm_mosaic_plan_host_f32")
     return records, chain, extent
@@ -1796,42 +1894,19 @@ def transform_blend_batch_gain(canvas, canvas_wts, frames, masks, wts, records, 
     torch = _torch()
     if gains is not None and (tuple(gains.shape) != (len(frames), 3) or gains.device != canvas.device):
         raise NmError("transform_blend_batch_gain: gains must be float32 (n, 3) on the canvas' device")
-    _blend_batch("nm_transform_blend_batch_gain", canvas, canvas_wts, frames, masks, wts, records,
-                 (_dev(gains, torch.float32) if gains is not None else None,))
+    _blend_batch("nm_transform_blend_batch_gain", canvas, canvas_wts, frames, masks, wts, records, (_opt(gains, torch.float32),))
 
 
 def _blend_batch(entry, canvas, canvas_wts, frames, masks, wts, records, extra):
-    torch = _torch()
-    n = len(frames)
-    if not 0 < n <= MOSAIC_MAX_BATCH:
-        raise NmError("transform_blend_batch: %d frames (1 .. %d)" % (n, MOSAIC_MAX_BATCH))
-    masks = list(masks) if isinstance(masks, (list, tuple)) else [masks] * n
-    wts = list(wts) if isinstance(wts, (list, tuple)) else [wts] * n
-    if len(masks) != n or len(wts) != n:
-        raise NmError("transform_blend_batch: %d frames, %d masks, %d weight planes" % (n, len(masks), len(wts)))
-    if canvas.dim() != 3 or canvas.shape[2] != 4 or tuple(canvas_wts.shape) != tuple(canvas.shape[:2]):
-        raise NmError("transform_blend_batch: canvas must be (ch, cw, 4) uint8 with (ch, cw) float32 weights")
-    ch, cw = canvas.shape[0], canvas.shape[1]
-    if not (1 <= cw <= _MOSAIC_SIZE_LIMIT and 1 <= ch <= _MOSAIC_SIZE_LIMIT):
-        raise NmError("transform_blend_batch: canvas %dx%d outside [1, %d]" % (cw, ch, _MOSAIC_SIZE_LIMIT))
-    fh, fw = frames[0].shape[0], frames[0].shape[1]
-    if any(f.dim() != 3 or tuple(f.shape) != (fh, fw, 4) for f in frames) or fw < 1 or fh < 1:
-        raise NmError("transform_blend_batch: frames must all be (fh, fw, 4) uint8")
-    if any(tuple(t.shape) != (fh, fw) for t in masks + wts):
-        raise NmError("transform_blend_batch: masks and weights must be (fh, fw) planes")
-    mfmt, wfmt = _tex_format(masks[0]), _tex_format(wts[0])
-    if any(_tex_format(t) != mfmt for t in masks) or any(_tex_format(t) != wfmt for t in wts):
-        raise NmError("transform_blend_batch: one mask format and one weight format per call")
-    if tuple(records.shape) != (n, 16) or records.dtype != torch.int32:
-        raise NmError("transform_blend_batch: records must be int32 (n, 16)")
-    device = canvas.device
-    tensors = [canvas, canvas_wts, records] + list(frames) + masks + wts
-    if any(t.device != device for t in tensors) or device.type != "cuda" or torch.cuda.current_device() != device.index:
-        raise NmError("transform_blend_batch: all tensors must live on the current device")
-    arr = lambda vals: (C.c_void_p * n)(*vals)
+    torch, what = _torch(), "transform_blend_batch"
+    n, fw, fh = _frames_check(what, frames)
+    masks, wts, mfmt, wfmt = _scalar_planes(what, n, fw, fh, masks, wts)
+    cw, ch = _canvas_check(what, canvas, canvas_wts)
+    _records_check(what, records, n)
+    _on_current_device([canvas, canvas_wts, records] + list(frames) + masks + wts, what)
     _check(getattr(lib(), entry)(_dev(canvas, torch.uint8), cw, ch, _dev(canvas_wts, torch.float32), n,
-                                 arr([_dev(f, torch.uint8) for f in frames]), fw, fh, arr([_dev(t) for t in masks]), mfmt,
-                                 arr([_dev(t) for t in wts]), wfmt, _dev(records, torch.int32), *extra, _stream()), entry)
+                                 _pair_dev_table(frames, torch.uint8), fw, fh, _pair_dev_table(masks, masks[0].dtype), mfmt,
+                                 _pair_dev_table(wts, wts[0].dtype), wfmt, _dev(records, torch.int32), *extra, _stream()), entry)
 
 
 def mosaic_place(chain, fw, fh, cw, ch, ox, oy, frame_status=None):
@@ -1844,12 +1919,11 @@ def mosaic_place(chain, fw, fh, cw, ch, ox, oy, frame_status=None):
     _mosaic_check_geometry(n, fw, fh, cw, ch, ox, oy)
     if chain.numel() != 9 * n or (frame_status is not None and frame_status.numel() != n):
         raise NmError("mosaic_place: chain must hold n x 9 floats and frame_status n values")
-    device = _on_current_device([chain] + ([frame_status] if frame_status is not None else []), "mosaic_place")
+    device = _on_current_device([chain, frame_status], "mosaic_place")
     records = torch.empty((n, 16), dtype=torch.int32, device=device)
     extent = torch.empty(4, dtype=torch.float32, device=device)
-    _check(lib().nm_mosaic_place_f32(n, _dev(chain, torch.float32),
-                                     _dev(frame_status, torch.int32) if frame_status is not None else None, fw, fh, cw, ch,
-                                     ox, oy, _dev(records), _dev(extent), _stream()), "nm_mosaic_place_f32")
+    _check(lib().nm_mosaic_place_f32(n, _dev(chain, torch.float32), _opt(frame_status, torch.int32), fw, fh, cw, ch, ox, oy,
+                                     _dev(records), _dev(extent), _stream()), "nm_mosaic_place_f32")
     return records, extent
 
 
@@ -1895,8 +1969,7 @@ def _mosaic_adjust_check(n, lists, link_a, link_b, anchor, fw, fh, iterations, m
         raise NmError("mosaic adjustment: a link joins two different frames in [0, n)")
     if not 0 <= int(anchor) < n:
         raise NmError("mosaic adjustment: anchor %r outside [0, n)" % (anchor,))
-    if not (1 <= fw <= _MOSAIC_SIZE_LIMIT and 1 <= fh <= _MOSAIC_SIZE_LIMIT):
-        raise NmError("mosaic adjustment: frame %r x %r outside [1, %d]" % (fw, fh, _MOSAIC_SIZE_LIMIT))
+    _size_check("mosaic adjustment", "frame", fw, fh)
     if int(iterations) != iterations or not 1 <= iterations <= MOSAIC_ADJUST_MAX_ITERATIONS:
         raise NmError("mosaic adjustment: iterations %r outside [1, %d]" % (iterations, MOSAIC_ADJUST_MAX_ITERATIONS))
     if int(min_rows) != min_rows or min_rows < 4:
@@ -1931,9 +2004,8 @@ def mosaic_adjust(link_a, link_b, src_xs, src_ys, d_nAs, dst_xs, dst_ys, matches
     rms = torch.empty((L, 2), dtype=torch.float64, device=device)
     stats = torch.empty(len(MOSAIC_ADJUST_STATS), dtype=torch.float64, device=device)
     tables = _point_tables_dev(*lists)
-    opt = lambda t, dt: _dev(t, dt) if t is not None else None
-    _check(lib().nm_mosaic_adjust_dev_f32(n, L, la, lb, *tables[:3], capA, *tables[3:], opt(mask, torch.uint8),
-                                          opt(link_status, torch.int32), _dev(chain, torch.float32), int(anchor), fw, fh,
+    _check(lib().nm_mosaic_adjust_dev_f32(n, L, la, lb, *tables[:3], capA, *tables[3:], _opt(mask, torch.uint8),
+                                          _opt(link_status, torch.int32), _dev(chain, torch.float32), int(anchor), fw, fh,
                                           int(iterations), int(min_rows), damping, max_step, _dev(chain_out), _dev(fstat),
                                           _dev(rms), _dev(stats), _dev(workspace.buf), _stream()), "nm_mosaic_adjust_dev_f32")
     return chain_out, fstat, rms, stats
@@ -2013,13 +2085,13 @@ def _exposure_links(n, link_a, link_b):
     return L, (C.c_int * L)(*[int(a) for a in link_a]), (C.c_int * L)(*[int(b) for b in link_b])
 
 
-def _exposure_sums_check(n, link_a, link_b, fw, fh, stride, lo, hi):
+def _exposure_sums_check(frames, link_a, link_b, stride, lo, hi):
+    n, fw, fh = _frames_check("mosaic exposure", frames)
     L, la, lb = _exposure_links(n, link_a, link_b)
-    if not (1 <= fw <= _MOSAIC_SIZE_LIMIT and 1 <= fh <= _MOSAIC_SIZE_LIMIT):
-        raise NmError("mosaic exposure: frame %r x %r outside [1, %d]" % (fw, fh, _MOSAIC_SIZE_LIMIT))
-    if any(int(v) != v for v in (stride, lo, hi)) or not 1 <= stride <= 64 or not 0 <= lo <= hi <= 255:
-        raise NmError("mosaic exposure: stride in [1, 64] and bytes 0 <= lo <= hi <= 255 expected")
-    return L, la, lb
+    _lattice_check("mosaic exposure", fw, fh, stride)
+    if any(int(v) != v for v in (lo, hi)) or not 0 <= lo <= hi <= 255:
+        raise NmError("mosaic exposure: bytes 0 <= lo <= hi <= 255 expected")
+    return n, fw, fh, L, la, lb
 
 
 def _exposure_gains_check(n, link_a, link_b, min_pixels, sigma_n, sigma_g, g_min, g_max, mode):
@@ -2037,17 +2109,13 @@ def _exposure_gains_check(n, link_a, link_b, min_pixels, sigma_n, sigma_g, g_min
 
 def mosaic_exposure_sums(frames, link_a, link_b, H, link_status=None, mask=None, stride=4, lo=5, hi=250, sums=None):
     """Per-link, per-channel overlap sums of n = len(frames) <= 64 BGRA frames over L = len(link_a) <= 256 links
-    (nm_mosaic_exposure_sums_dev): one memset node and one launch on the current stream, no host read. frames: uint8 device
-    (fh, fw, 4), tensors may repeat; link_a, link_b: host ints; H float32 device (L, 9) or (L, 3, 3), H_l mapping frame
+    (nm_mosaic_exposure_sums_dev): two launches on the current stream (the first zeroes the sums), no host read. frames:
+    uint8 device (fh, fw, 4), tensors may repeat; link_a, link_b: host ints; H float32 device (L, 9) or (L, 3, 3), H_l mapping frame
     link_a[l] to frame link_b[l]; link_status int32 device (L,) or None; mask float32 device (fh, fw) or None; a pixel counts
     when its three bytes and the twelve tap bytes lie in [lo, hi]. sums: an int64 device tensor of L x 7 to write into
     (default: new). Returns it as (L, 7): N, Sa_B, Sa_G, Sa_R, Sb_B, Sb_G, Sb_R (unsigned 64-bit values below 2^63)."""
     torch = _torch()
-    n = len(frames)
-    fh, fw = (frames[0].shape[0], frames[0].shape[1]) if n else (0, 0)
-    L, la, lb = _exposure_sums_check(n, link_a, link_b, fw, fh, stride, lo, hi)
-    if any(f.dim() != 3 or tuple(f.shape) != (fh, fw, 4) for f in frames):
-        raise NmError("mosaic exposure: frames must all be (fh, fw, 4) uint8")
+    n, fw, fh, L, la, lb = _exposure_sums_check(frames, link_a, link_b, stride, lo, hi)
     if H.numel() != 9 * L or (link_status is not None and link_status.numel() != L) or \
             (mask is not None and tuple(mask.shape) != (fh, fw)):
         raise NmError("mosaic exposure: H L x 9, link_status L values and mask (fh, fw) expected")
@@ -2055,10 +2123,9 @@ def mosaic_exposure_sums(frames, link_a, link_b, H, link_status=None, mask=None,
         sums = torch.empty((L, EXPOSURE_SUMS), dtype=torch.int64, device=frames[0].device)
     if sums.numel() != L * EXPOSURE_SUMS:
         raise NmError("mosaic exposure: sums must hold L x 7 values")
-    _on_current_device(list(frames) + [H, sums] + [t for t in (link_status, mask) if t is not None], "mosaic_exposure_sums")
-    opt = lambda t, dt: _dev(t, dt) if t is not None else None
-    _check(lib().nm_mosaic_exposure_sums_dev(n, L, (C.c_void_p * n)(*[_dev(f, torch.uint8) for f in frames]), la, lb, fw, fh,
-                                             opt(mask, torch.float32), _dev(H, torch.float32), opt(link_status, torch.int32),
+    _on_current_device(list(frames) + [H, sums, link_status, mask], "mosaic_exposure_sums")
+    _check(lib().nm_mosaic_exposure_sums_dev(n, L, _pair_dev_table(frames, torch.uint8), la, lb, fw, fh,
+                                             _opt(mask, torch.float32), _dev(H, torch.float32), _opt(link_status, torch.int32),
                                              int(stride), int(lo), int(hi), _dev(sums, torch.int64), _stream()),
            "nm_mosaic_exposure_sums_dev")
     return sums.view(L, EXPOSURE_SUMS)
@@ -2068,12 +2135,8 @@ def mosaic_exposure_sums_host(frames, link_a, link_b, H, link_status=None, mask=
     """mosaic_exposure_sums on the host (nm_mosaic_exposure_sums_host, the same functions): numpy in and out, identical
     results. Returns uint64 (L, 7)."""
     import numpy as np
-    frames = [np.ascontiguousarray(f, dtype=np.uint8) for f in frames]
-    n = len(frames)
-    fh, fw = (frames[0].shape[0], frames[0].shape[1]) if n else (0, 0)
-    L, la, lb = _exposure_sums_check(n, link_a, link_b, fw, fh, stride, lo, hi)
-    if any(f.shape != (fh, fw, 4) for f in frames):
-        raise NmError("mosaic exposure: frames must all be (fh, fw, 4) uint8")
+    frames = _pair_host_arrays(frames, np.uint8, flat=False)
+    n, fw, fh, L, la, lb = _exposure_sums_check(frames, link_a, link_b, stride, lo, hi)
     H = np.ascontiguousarray(H, dtype=np.float32).reshape(-1)
     link_status = None if link_status is None else np.ascontiguousarray(link_status, dtype=np.int32).reshape(-1)
     mask = None if mask is None else np.ascontiguousarray(mask, dtype=np.float32)
@@ -2104,9 +2167,8 @@ def mosaic_gains(n, link_a, link_b, sums, link_status=None, min_pixels=64, sigma
         stats = torch.empty(len(EXPOSURE_STATS), dtype=torch.float64, device=sums.device)
     if gains.numel() != 3 * n or stats.numel() != len(EXPOSURE_STATS):
         raise NmError("mosaic exposure: gains must hold n x 3 values and stats %d" % len(EXPOSURE_STATS))
-    _on_current_device([sums, gains, stats] + ([link_status] if link_status is not None else []), "mosaic_gains")
-    _check(lib().nm_mosaic_gains_dev(n, L, la, lb, _dev(sums, torch.int64),
-                                     _dev(link_status, torch.int32) if link_status is not None else None, int(min_pixels),
+    _on_current_device([sums, gains, stats, link_status], "mosaic_gains")
+    _check(lib().nm_mosaic_gains_dev(n, L, la, lb, _dev(sums, torch.int64), _opt(link_status, torch.int32), int(min_pixels),
                                      float(sigma_n), float(sigma_g), float(g_min), float(g_max), int(mode),
                                      _dev(gains, torch.float32), _dev(stats, torch.float64), _stream()), "nm_mosaic_gains_dev")
     return gains.view(n, 3), stats
@@ -2134,8 +2196,8 @@ def mosaic_gains_host(n, link_a, link_b, sums, link_status=None, min_pixels=64, 
 def mosaic_exposure(frames, link_a, link_b, H, link_status=None, mask=None, stride=4, lo=5, hi=250, min_pixels=64,
                     sigma_n=10.0, sigma_g=0.1, g_min=0.25, g_max=4.0, mode=EXPOSURE_PER_CHANNEL, sums=None, gains=None,
                     stats=None):
-    """Exposure gains of a mosaic's frames: mosaic_exposure_sums, then mosaic_gains, one memset node and two launches on the
-    current stream and no host read. Returns (gains, stats, sums), all device tensors."""
+    """Exposure gains of a mosaic's frames: mosaic_exposure_sums, then mosaic_gains, three launches on the current stream
+    and no host read. Returns (gains, stats, sums), all device tensors."""
     _exposure_gains_check(len(frames), link_a, link_b, min_pixels, sigma_n, sigma_g, g_min, g_max, mode)
     sums = mosaic_exposure_sums(frames, link_a, link_b, H, link_status=link_status, mask=mask, stride=stride, lo=lo, hi=hi,
                                 sums=sums)
@@ -2156,13 +2218,11 @@ class MosaicBandsWorkspace(_PairWorkspace):
         self._alloc(device, n=n, tile_cap=tile_cap, cw=cw, ch=ch)
 
 
-def _bands_check(n, tile_cap, cw, ch, R, sigma):
+def _bands_check(n, tile_cap, R=0, sigma=1.0):
     if not 0 < n <= MOSAIC_MAX_BATCH:
         raise NmError("mosaic bands: %d frames (1 .. %d)" % (n, MOSAIC_MAX_BATCH))
     if int(tile_cap) != tile_cap or not 1 <= tile_cap <= _BANDS_MAX_TILE_CAP:
         raise NmError("mosaic bands: tile_cap %r outside [1, 2^30]" % (tile_cap,))
-    if not (1 <= cw <= _MOSAIC_SIZE_LIMIT and 1 <= ch <= _MOSAIC_SIZE_LIMIT):
-        raise NmError("mosaic bands: canvas %dx%d outside [1, %d]" % (cw, ch, _MOSAIC_SIZE_LIMIT))
     if int(R) != R or not 0 <= R <= BANDS_MAX_RADIUS:
         raise NmError("mosaic bands: radius %r outside [0, %d]" % (R, BANDS_MAX_RADIUS))
     if R > 0 and not (math.isfinite(sigma) and sigma > 0):
@@ -2172,7 +2232,7 @@ def _bands_check(n, tile_cap, cw, ch, R, sigma):
 def mosaic_bands_taps(R, sigma):
     """The low band's taps g[0..R] (float32 numpy) as nm_mosaic_bands_dev / _host compute them on the host."""
     import numpy as np
-    _bands_check(1, 1, 1, 1, R, sigma)
+    _bands_check(1, 1, R, sigma)
     g = np.zeros(int(R) + 1, np.float32)
     _check(lib().nm_mosaic_bands_taps(int(R), float(sigma), g.ctypes.data), "nm_mosaic_bands_taps")
     return g
@@ -2184,24 +2244,13 @@ def mosaic_warp_tiles(frames, masks, wts, records, gains=None, tile_cap=None, ti
     slot (default fh * fw * 2); a frame whose nw * nh exceeds it is skipped. tiles / stats: float32 (n, tile_cap, 4) / int32
     (2,) device tensors to write into (default: new, tiles uninitialised). Returns (tiles, stats): frame k's pixel (x, y) is
     tiles[k, y * nw_k + x] = (C_B, C_G, C_R, w); stats in the order of BANDS_STATS."""
-    torch = _torch()
-    n = len(frames)
-    if not 0 < n <= MOSAIC_MAX_BATCH:
-        raise NmError("mosaic_warp_tiles: %d frames (1 .. %d)" % (n, MOSAIC_MAX_BATCH))
-    masks = list(masks) if isinstance(masks, (list, tuple)) else [masks] * n
-    wts = list(wts) if isinstance(wts, (list, tuple)) else [wts] * n
-    fh, fw = frames[0].shape[0], frames[0].shape[1]
+    torch, what = _torch(), "mosaic_warp_tiles"
+    n, fw, fh = _frames_check(what, frames)
+    masks, wts, mfmt, wfmt = _scalar_planes(what, n, fw, fh, masks, wts)
+    _records_check(what, records, n)
     if tile_cap is None:
         tile_cap = 2 * fh * fw
-    _bands_check(n, tile_cap, 1, 1, 0, 1.0)
-    if len(masks) != n or len(wts) != n or any(f.dim() != 3 or tuple(f.shape) != (fh, fw, 4) for f in frames) or \
-            any(tuple(t.shape) != (fh, fw) for t in masks + wts) or not (1 <= fw <= _MOSAIC_SIZE_LIMIT and 1 <= fh <= _MOSAIC_SIZE_LIMIT):
-        raise NmError("mosaic_warp_tiles: n frames (fh, fw, 4) uint8 with (fh, fw) masks and weights expected")
-    mfmt, wfmt = _tex_format(masks[0]), _tex_format(wts[0])
-    if any(_tex_format(t) != mfmt for t in masks) or any(_tex_format(t) != wfmt for t in wts):
-        raise NmError("mosaic_warp_tiles: one mask format and one weight format per call")
-    if tuple(records.shape) != (n, 16) or records.dtype != torch.int32:
-        raise NmError("mosaic_warp_tiles: records must be int32 (n, 16)")
+    _bands_check(n, tile_cap)
     if gains is not None and tuple(gains.shape) != (n, 3):
         raise NmError("mosaic_warp_tiles: gains must be float32 (n, 3)")
     device = frames[0].device
@@ -2211,20 +2260,12 @@ def mosaic_warp_tiles(frames, masks, wts, records, gains=None, tile_cap=None, ti
         stats = torch.empty(len(BANDS_STATS), dtype=torch.int32, device=device)
     if tiles.numel() != n * int(tile_cap) * 4 or stats.numel() != len(BANDS_STATS):
         raise NmError("mosaic_warp_tiles: tiles must hold n x tile_cap x 4 floats and stats %d ints" % len(BANDS_STATS))
-    _on_current_device(list(frames) + masks + wts + [records, tiles, stats] + ([gains] if gains is not None else []),
-                       "mosaic_warp_tiles")
-    arr = lambda vals: (C.c_void_p * n)(*vals)
-    _check(lib().nm_mosaic_warp_tiles(n, arr([_dev(f, torch.uint8) for f in frames]), fw, fh, arr([_dev(t) for t in masks]),
-                                      mfmt, arr([_dev(t) for t in wts]), wfmt, _dev(records, torch.int32),
-                                      _dev(gains, torch.float32) if gains is not None else None, _dev(tiles, torch.float32),
-                                      int(tile_cap), _dev(stats, torch.int32), _stream()), "nm_mosaic_warp_tiles")
+    _on_current_device(list(frames) + masks + wts + [records, tiles, stats, gains], what)
+    _check(lib().nm_mosaic_warp_tiles(n, _pair_dev_table(frames, torch.uint8), fw, fh, _pair_dev_table(masks, masks[0].dtype),
+                                      mfmt, _pair_dev_table(wts, wts[0].dtype), wfmt, _dev(records, torch.int32),
+                                      _opt(gains, torch.float32), _dev(tiles, torch.float32), int(tile_cap),
+                                      _dev(stats, torch.int32), _stream()), what)
     return tiles.view(n, int(tile_cap), 4), stats
-
-
-def _bands_canvas_shape(canvas_shape, wts_shape):
-    if len(canvas_shape) != 3 or canvas_shape[2] != 4 or (wts_shape is not None and tuple(wts_shape) != tuple(canvas_shape[:2])):
-        raise NmError("mosaic bands: canvas must be (ch, cw, 4) uint8 with (ch, cw) float32 weights or None")
-    return canvas_shape[1], canvas_shape[0]
 
 
 def mosaic_bands(canvas, canvas_wts, tiles, records, R=16, sigma=None, workspace=None):
@@ -2233,21 +2274,15 @@ def mosaic_bands(canvas, canvas_wts, tiles, records, R=16, sigma=None, workspace
     canvas_wts float32 (ch, cw) or None; tiles float32 (n, tile_cap, 4); records int32 (n, 16); R in [0, 32], sigma default
     R / 2. A labelled pixel is overwritten, every other keeps its bytes and weight. Returns the workspace used."""
     torch = _torch()
-    if tiles.dim() != 3 or tiles.shape[2] != 4:
-        raise NmError("mosaic_bands: tiles must be float32 (n, tile_cap, 4)")
-    n, tile_cap = tiles.shape[0], tiles.shape[1]
-    cw, ch = _bands_canvas_shape(tuple(canvas.shape), None if canvas_wts is None else tuple(canvas_wts.shape))
+    n, tile_cap, cw, ch = _composite_head("mosaic_bands", canvas, canvas_wts, tiles, records)
     sigma = (max(R, 1) / 2.0) if sigma is None else sigma
-    _bands_check(n, tile_cap, cw, ch, R, sigma)
-    if tuple(records.shape) != (n, 16) or records.dtype != torch.int32:
-        raise NmError("mosaic_bands: records must be int32 (n, 16)")
-    device = _on_current_device([canvas, tiles, records] + ([canvas_wts] if canvas_wts is not None else []) +
-                                ([workspace.buf] if workspace is not None else []), "mosaic_bands")
+    _bands_check(n, tile_cap, R, sigma)
+    device = _on_current_device([canvas, tiles, records, canvas_wts, workspace.buf if workspace is not None else None],
+                                "mosaic_bands")
     workspace = _pair_workspace(MosaicBandsWorkspace, workspace, device, n, tile_cap, cw, ch)
     _check(lib().nm_mosaic_bands_dev(n, _dev(tiles, torch.float32), tile_cap, _dev(records, torch.int32),
-                                     _dev(canvas, torch.uint8), cw, ch,
-                                     _dev(canvas_wts, torch.float32) if canvas_wts is not None else None, int(R),
-                                     float(sigma), _dev(workspace.buf), _stream()), "nm_mosaic_bands_dev")
+                                     _dev(canvas, torch.uint8), cw, ch, _opt(canvas_wts, torch.float32), int(R), float(sigma),
+                                     _dev(workspace.buf), _stream()), "nm_mosaic_bands_dev")
     return workspace
 
 
@@ -2255,28 +2290,13 @@ def mosaic_bands_host(canvas, canvas_wts, tiles, records, R=16, sigma=None):
     """mosaic_bands on the host (nm_mosaic_bands_host, the same functions): numpy arrays, canvas (ch, cw, 4) uint8 and
     canvas_wts (ch, cw) float32 or None written IN PLACE, bit-identical to the device."""
     import numpy as np
-    tiles, records = np.ascontiguousarray(tiles, dtype=np.float32), np.ascontiguousarray(records, dtype=np.int32)
-    if tiles.ndim != 3 or tiles.shape[2] != 4 or records.shape != (tiles.shape[0], 16):
-        raise NmError("mosaic_bands_host: tiles float32 (n, tile_cap, 4) and records int32 (n, 16) expected")
-    n, tile_cap = tiles.shape[0], tiles.shape[1]
-    for a, dt in ((canvas, np.uint8), (canvas_wts, np.float32)):
-        if a is not None and (a.dtype != dt or not a.flags.c_contiguous or not a.flags.writeable):
-            raise NmError("mosaic_bands_host: canvas uint8 and canvas_wts float32, contiguous and writeable")
-    cw, ch = _bands_canvas_shape(canvas.shape, None if canvas_wts is None else canvas_wts.shape)
+    n, tile_cap, cw, ch, tiles, records = _composite_head_host("mosaic_bands_host", canvas, canvas_wts, tiles, records)
     sigma = (max(R, 1) / 2.0) if sigma is None else sigma
-    _bands_check(n, tile_cap, cw, ch, R, sigma)
-    nbytes = lib().nm_mosaic_bands_workspace_bytes(n, tile_cap, cw, ch)
-    ws, tl = _aligned_host(nbytes, np), _aligned_host(tiles.nbytes, np)
-    tl[:] = tiles.reshape(-1).view(np.uint8)
-    _check(lib().nm_mosaic_bands_host(n, tl.ctypes.data, tile_cap, records.ctypes.data, canvas.ctypes.data, cw, ch,
-                                      _pair_host_ptr(canvas_wts), int(R), float(sigma), ws.ctypes.data),
-           "nm_mosaic_bands_host")
-
-
-def _aligned_host(nbytes, np, align=16):
-    raw = np.empty(nbytes + align, np.uint8)
-    off = (-raw.ctypes.data) % align
-    return raw[off:off + nbytes]
+    _bands_check(n, tile_cap, R, sigma)
+    ws = _aligned_host(lib().nm_mosaic_bands_workspace_bytes(n, tile_cap, cw, ch), np)
+    ptr = _pair_host_ptr
+    _check(lib().nm_mosaic_bands_host(n, ptr(tiles), tile_cap, ptr(records), ptr(canvas), cw, ch, ptr(canvas_wts), int(R),
+                                      float(sigma), ptr(ws)), "nm_mosaic_bands_host")
 
 
 def mosaic_blend_bands(canvas, canvas_wts, frames, masks, wts, records, gains=None, R=16, sigma=None, tile_cap=None,
@@ -2294,8 +2314,8 @@ MEDIAN_SELECT, MEDIAN_MEAN = 0, 1
 MEDIAN_TAU = 0.05
 
 
-def _median_check(n, tile_cap, cw, ch, mode, w_min, tau):
-    _bands_check(n, tile_cap, cw, ch, 0, 1.0)
+def _median_check(n, tile_cap, mode, w_min, tau):
+    _bands_check(n, tile_cap)
     if mode not in (MEDIAN_SELECT, MEDIAN_MEAN):
         raise NmError("mosaic median: unknown mode %r" % (mode,))
     if not (math.isfinite(w_min) and w_min >= 0):
@@ -2315,23 +2335,16 @@ def mosaic_median(canvas, canvas_wts, tiles, records, mode=MEDIAN_SELECT, w_min=
     pixel with a valid frame is overwritten, every other keeps its contents. The default tau was chosen on synthetic views
     (MEDIAN_TAU); tune it on real footage. Returns counts."""
     torch = _torch()
-    if tiles.dim() != 3 or tiles.shape[2] != 4:
-        raise NmError("mosaic_median: tiles must be float32 (n, tile_cap, 4)")
-    n, tile_cap = tiles.shape[0], tiles.shape[1]
-    cw, ch = _bands_canvas_shape(tuple(canvas.shape), None if canvas_wts is None else tuple(canvas_wts.shape))
-    _median_check(n, tile_cap, cw, ch, mode, w_min, tau)
-    if tuple(records.shape) != (n, 16) or records.dtype != torch.int32:
-        raise NmError("mosaic_median: records must be int32 (n, 16)")
+    n, tile_cap, cw, ch = _composite_head("mosaic_median", canvas, canvas_wts, tiles, records)
+    _median_check(n, tile_cap, mode, w_min, tau)
     if any(p is not None and tuple(p.shape) != (ch, cw) for p in (support, label)) or \
             (counts is not None and counts.numel() != 2 * n):
         raise NmError("mosaic_median: support and label must be uint8 (ch, cw) and counts int64 (n, 2)")
-    _on_current_device([canvas, tiles, records] + [t for t in (canvas_wts, support, label, counts) if t is not None],
-                       "mosaic_median")
-    opt = lambda t, dtype: _dev(t, dtype) if t is not None else None
+    _on_current_device([canvas, tiles, records, canvas_wts, support, label, counts], "mosaic_median")
     _check(lib().nm_mosaic_median_dev(n, _dev(tiles, torch.float32), tile_cap, _dev(records, torch.int32),
-                                      _dev(canvas, torch.uint8), cw, ch, opt(canvas_wts, torch.float32), int(mode),
-                                      float(w_min), float(tau), opt(support, torch.uint8), opt(label, torch.uint8),
-                                      opt(counts, torch.int64), _stream()), "nm_mosaic_median_dev")
+                                      _dev(canvas, torch.uint8), cw, ch, _opt(canvas_wts, torch.float32), int(mode),
+                                      float(w_min), float(tau), _opt(support, torch.uint8), _opt(label, torch.uint8),
+                                      _opt(counts, torch.int64), _stream()), "nm_mosaic_median_dev")
     return counts
 
 
@@ -2341,23 +2354,14 @@ def mosaic_median_host(canvas, canvas_wts, tiles, records, mode=MEDIAN_SELECT, w
     (ch, cw, 4) uint8, canvas_wts (ch, cw) float32 or None, support / label (ch, cw) uint8 or None, counts (n, 2) uint64 or
     None; bit-identical to the device."""
     import numpy as np
-    tiles, records = np.ascontiguousarray(tiles, dtype=np.float32), np.ascontiguousarray(records, dtype=np.int32)
-    if tiles.ndim != 3 or tiles.shape[2] != 4 or records.shape != (tiles.shape[0], 16):
-        raise NmError("mosaic_median_host: tiles float32 (n, tile_cap, 4) and records int32 (n, 16) expected")
-    n, tile_cap = tiles.shape[0], tiles.shape[1]
-    for a, dt in ((canvas, np.uint8), (canvas_wts, np.float32), (support, np.uint8), (label, np.uint8), (counts, np.uint64)):
-        if a is not None and (a.dtype != dt or not a.flags.c_contiguous or not a.flags.writeable):
-            raise NmError("mosaic_median_host: outputs must be contiguous, writeable and of their documented types")
-    cw, ch = _bands_canvas_shape(canvas.shape, None if canvas_wts is None else canvas_wts.shape)
-    _median_check(n, tile_cap, cw, ch, mode, w_min, tau)
+    n, tile_cap, cw, ch, tiles, records = _composite_head_host(
+        "mosaic_median_host", canvas, canvas_wts, tiles, records, ((support, np.uint8), (label, np.uint8), (counts, np.uint64)))
+    _median_check(n, tile_cap, mode, w_min, tau)
     if any(p is not None and p.shape != (ch, cw) for p in (support, label)) or (counts is not None and counts.size != 2 * n):
         raise NmError("mosaic_median_host: support and label must be (ch, cw) and counts (n, 2)")
-    tl = _aligned_host(tiles.nbytes, np)
-    tl[:] = tiles.reshape(-1).view(np.uint8)
     ptr = _pair_host_ptr
-    _check(lib().nm_mosaic_median_host(n, tl.ctypes.data, tile_cap, records.ctypes.data, canvas.ctypes.data, cw, ch,
-                                       ptr(canvas_wts), int(mode), float(w_min), float(tau), ptr(support), ptr(label),
-                                       ptr(counts)), "nm_mosaic_median_host")
+    _check(lib().nm_mosaic_median_host(n, ptr(tiles), tile_cap, ptr(records), ptr(canvas), cw, ch, ptr(canvas_wts), int(mode),
+                                       float(w_min), float(tau), ptr(support), ptr(label), ptr(counts)), "nm_mosaic_median_host")
 
 
 def mosaic_blend_median(canvas, canvas_wts, frames, masks, wts, records, gains=None, mode=MEDIAN_SELECT, w_min=0.0,
@@ -2484,16 +2488,7 @@ def link_propose(descs_u8, d_counts, ambiguity=0.8, min_votes=16, min_gap=2, per
     return la, lb, ls, cnt, votes
 
 
-INGEST_MAX_BATCH = 64
-_INGEST_SIZE_LIMIT = 32767
-
-
-def _on_current_device(tensors, what):
-    torch = _torch()
-    device = tensors[0].device
-    if any(t.device != device for t in tensors) or device.type != "cuda" or torch.cuda.current_device() != device.index:
-        raise NmError("%s: all tensors must live on the current device" % what)
-    return device
+INGEST_MAX_BATCH = _FRAMES_MAX_BATCH
 
 
 def _ingest_map(u, v, what):
@@ -2501,8 +2496,7 @@ def _ingest_map(u, v, what):
     if u.dim() != 2 or tuple(v.shape) != tuple(u.shape) or u.dtype != torch.float32 or v.dtype != torch.float32:
         raise NmError("%s: the map must be two float32 (rows, cols) planes of one shape" % what)
     rows, cols = u.shape
-    if not (1 <= cols <= _INGEST_SIZE_LIMIT and 1 <= rows <= _INGEST_SIZE_LIMIT):
-        raise NmError("%s: map %dx%d outside [1, %d]" % (what, cols, rows, _INGEST_SIZE_LIMIT))
+    _size_check(what, "map", cols, rows)
     return cols, rows
 
 
@@ -2510,11 +2504,7 @@ def resample_map_u8x4(tex, x, y):
     """resample_2D<uchar4> on a caller's map (nm_resample_map_u8x4): tex uint8 (fh, fw, 4) BGRA sampled at (x + 0.5,
     y + 0.5) of the float32 (rows, cols) planes x, y. Returns uint8 (rows, cols, 4)."""
     torch = _torch()
-    if tex.dim() != 3 or tex.shape[2] != 4 or tex.dtype != torch.uint8:
-        raise NmError("resample_map_u8x4: tex must be (fh, fw, 4) uint8")
-    fh, fw = tex.shape[0], tex.shape[1]
-    if not (1 <= fw <= _INGEST_SIZE_LIMIT and 1 <= fh <= _INGEST_SIZE_LIMIT):
-        raise NmError("resample_map_u8x4: frame %dx%d outside [1, %d]" % (fw, fh, _INGEST_SIZE_LIMIT))
+    _, fw, fh = _frames_check("resample_map_u8x4", [tex])
     cols, rows = _ingest_map(x, y, "resample_map_u8x4")
     device = _on_current_device([tex, x, y], "resample_map_u8x4")
     out = torch.empty((rows, cols, 4), dtype=torch.uint8, device=device)
@@ -2531,34 +2521,19 @@ def ingest_batch(frames, u=None, v=None, undistorted=False):
     also the list of uint8 (rows, cols, 4) undistorted frames."""
     torch = _torch()
     frames = list(frames)
-    n = len(frames)
-    if not 0 < n <= INGEST_MAX_BATCH:
-        raise NmError("ingest_batch: %d frames (1 .. %d)" % (n, INGEST_MAX_BATCH))
-    if any(f.dim() != 3 or f.shape[2] != 4 or f.dtype != torch.uint8 for f in frames):
-        raise NmError("ingest_batch: frames must be (fh, fw, 4) uint8")
-    fh, fw = frames[0].shape[0], frames[0].shape[1]
-    if any(tuple(f.shape) != (fh, fw, 4) for f in frames):
-        raise NmError("ingest_batch: all frames must have one shape")
-    if not (1 <= fw <= _INGEST_SIZE_LIMIT and 1 <= fh <= _INGEST_SIZE_LIMIT):
-        raise NmError("ingest_batch: frame %dx%d outside [1, %d]" % (fw, fh, _INGEST_SIZE_LIMIT))
+    n, fw, fh = _frames_check("ingest_batch", frames)
     if (u is None) != (v is None):
         raise NmError("ingest_batch: give both map planes or neither")
     if u is None:
         if undistorted:
             raise NmError("ingest_batch: undistorted frames need a map")
-        cols, rows = fw, fh
-        device = _on_current_device(frames, "ingest_batch")
-    else:
-        cols, rows = _ingest_map(u, v, "ingest_batch")
-        device = _on_current_device(frames + [u, v], "ingest_batch")
+    cols, rows = (fw, fh) if u is None else _ingest_map(u, v, "ingest_batch")
+    device = _on_current_device(frames + [u, v], "ingest_batch")
     gray = [torch.empty((rows, cols), dtype=torch.float32, device=device) for _ in range(n)]
     und = [torch.empty((rows, cols, 4), dtype=torch.uint8, device=device) for _ in range(n)] if undistorted else None
-    arr = lambda vals: (C.c_void_p * n)(*vals)
-    _check(lib().nm_frame_ingest_batch_f32(n, arr([_dev(f, torch.uint8) for f in frames]), fw, fh,
-                                           _dev(u, torch.float32) if u is not None else None,
-                                           _dev(v, torch.float32) if v is not None else None, cols, rows,
-                                           arr([_dev(g) for g in gray]), arr([_dev(t) for t in und]) if und else None,
-                                           _stream()), "nm_frame_ingest_batch_f32")
+    _check(lib().nm_frame_ingest_batch_f32(n, _pair_dev_table(frames, torch.uint8), fw, fh, _opt(u, torch.float32),
+                                           _opt(v, torch.float32), cols, rows, _pair_dev_table(gray, torch.float32),
+                                           _pair_dev_table(und, torch.uint8), _stream()), "nm_frame_ingest_batch_f32")
     return (gray, und) if undistorted else gray
 
 
@@ -2574,11 +2549,7 @@ class FrameWeightsWorkspace(_PairWorkspace):
         self._alloc(device, n=n, fw=fw, fh=fh)
 
 
-def _frame_weights_check(n, fw, fh, lo, hi, R, margin, min_count, mask_format, want, counts):
-    if not 0 < n <= FRAME_WEIGHTS_MAX_BATCH:
-        raise NmError("frame weights: %d frames (1 .. %d)" % (n, FRAME_WEIGHTS_MAX_BATCH))
-    if not (1 <= fw <= _INGEST_SIZE_LIMIT and 1 <= fh <= _INGEST_SIZE_LIMIT):
-        raise NmError("frame weights: frame %dx%d outside [1, %d]" % (fw, fh, _INGEST_SIZE_LIMIT))
+def _frame_weights_check(lo, hi, R, margin, min_count, mask_format, want, counts):
     if any(int(v) != v for v in (lo, hi, R, margin, min_count)):
         raise NmError("frame weights: lo, hi, R, margin and min_count are integers")
     if not (0 <= lo <= 255 and 0 <= hi <= 255):
@@ -2614,29 +2585,20 @@ def frame_weights_batch(frames, lo=0, hi=255, R=32, margin=0, min_count=1, borde
     mosaic_warp_tiles and mosaic_blend_median. workspace: a FrameWeightsWorkspace (default: new)."""
     torch = _torch()
     frames = list(frames)
-    n = len(frames)
-    if not n or any(f.dim() != 3 or f.shape[2] != 4 or f.dtype != torch.uint8 for f in frames):
-        raise NmError("frame_weights_batch: frames must be (fh, fw, 4) uint8")
-    fh, fw = frames[0].shape[0], frames[0].shape[1]
-    if any(tuple(f.shape) != (fh, fw, 4) for f in frames):
-        raise NmError("frame_weights_batch: all frames must have one shape")
-    want = _frame_weights_check(n, fw, fh, lo, hi, R, margin, min_count, mask_format, want, counts)
+    n, fw, fh = _frames_check("frame_weights_batch", frames)
+    want = _frame_weights_check(lo, hi, R, margin, min_count, mask_format, want, counts)
     if base is not None and (tuple(base.shape) != (fh, fw) or base.dtype != torch.uint8):
         raise NmError("frame_weights_batch: base must be uint8 (fh, fw)")
-    device = _on_current_device(frames + ([base] if base is not None else []) +
-                                ([workspace.buf] if workspace is not None else []), "frame_weights_batch")
+    device = _on_current_device(frames + [base, workspace.buf if workspace is not None else None], "frame_weights_batch")
     workspace = _pair_workspace(FrameWeightsWorkspace, workspace, device, n, fw, fh)
     dtypes = {"mask": torch.uint8 if mask_format == TEX_U8N else torch.float32, "wts": torch.float32, "dist2": torch.int16}
     out = {w: torch.empty((n, fh, fw), dtype=dtypes[w], device=device) for w in want}
     cnt = torch.empty((n, 2), dtype=torch.int64, device=device) if counts else None
-    arr = lambda vals: (C.c_void_p * n)(*vals)
-    table = lambda w: arr([_dev(out[w][k]) for k in range(n)]) if w in out else None
-    _check(lib().nm_frame_weights_batch_dev(n, arr([_dev(f, torch.uint8) for f in frames]), fw, fh,
-                                            _dev(base, torch.uint8) if base is not None else None, int(lo), int(hi),
-                                            int(min_count), 1 if border else 0, int(R), int(margin), table("mask"),
-                                            int(mask_format), table("wts"), table("dist2"),
-                                            _dev(cnt, torch.int64) if counts else None, _dev(workspace.buf), _stream()),
-           "nm_frame_weights_batch_dev")
+    table = lambda w: _pair_dev_table(list(out[w]), dtypes[w]) if w in out else None
+    _check(lib().nm_frame_weights_batch_dev(n, _pair_dev_table(frames, torch.uint8), fw, fh, _opt(base, torch.uint8), int(lo),
+                                            int(hi), int(min_count), 1 if border else 0, int(R), int(margin), table("mask"),
+                                            int(mask_format), table("wts"), table("dist2"), _opt(cnt, torch.int64),
+                                            _dev(workspace.buf), _stream()), "nm_frame_weights_batch_dev")
     res = tuple(out[w] for w in want) + ((cnt,) if counts else ())
     return res[0] if len(res) == 1 else res
 
@@ -2647,14 +2609,9 @@ def frame_weights_host(frames, lo=0, hi=255, R=32, margin=0, min_count=1, border
     base a uint8 (fh, fw) array or None. Returns numpy arrays in the same order: mask uint8 or float32, wts float32, dist2
     uint16, each (n, fh, fw), and counts uint64 (n, 2); bit-identical to the device."""
     import numpy as np
-    frames = [np.ascontiguousarray(f, dtype=np.uint8) for f in frames]
-    n = len(frames)
-    if not n or any(f.ndim != 3 or f.shape[2] != 4 for f in frames):
-        raise NmError("frame_weights_host: frames must be (fh, fw, 4) uint8")
-    fh, fw = frames[0].shape[0], frames[0].shape[1]
-    if any(f.shape != (fh, fw, 4) for f in frames):
-        raise NmError("frame_weights_host: all frames must have one shape")
-    want = _frame_weights_check(n, fw, fh, lo, hi, R, margin, min_count, mask_format, want, counts)
+    frames = _pair_host_arrays(frames, np.uint8, flat=False)
+    n, fw, fh = _frames_check("frame_weights_host", frames)
+    want = _frame_weights_check(lo, hi, R, margin, min_count, mask_format, want, counts)
     if base is not None:
         base = np.ascontiguousarray(base, dtype=np.uint8)
         if base.shape != (fh, fw):
@@ -2662,7 +2619,7 @@ def frame_weights_host(frames, lo=0, hi=255, R=32, margin=0, min_count=1, border
     dtypes = {"mask": np.uint8 if mask_format == TEX_U8N else np.float32, "wts": np.float32, "dist2": np.uint16}
     out = {w: np.empty((n, fh, fw), dtypes[w]) for w in want}
     cnt = np.empty((n, 2), np.uint64) if counts else None
-    table = lambda w: _pair_host_table([out[w][k] for k in range(n)]) if w in out else None
+    table = lambda w: _pair_host_table(list(out[w])) if w in out else None
     _check(lib().nm_frame_weights_host(n, _pair_host_table(frames), fw, fh, _pair_host_ptr(base), int(lo), int(hi),
                                        int(min_count), 1 if border else 0, int(R), int(margin), table("mask"),
                                        int(mask_format), table("wts"), table("dist2"), _pair_host_ptr(cnt)),

@@ -8,6 +8,7 @@
 #define NM_WAVE 64
 
 constexpr int NM_SIZE_LIMIT = 32767;    // frame, canvas and output extents of every stage lie in [1, NM_SIZE_LIMIT]
+static inline bool nm_size_ok(int v) { return v >= 1 && v <= NM_SIZE_LIMIT; }
 
 #define NM_RETURN_IF(expr)                                  \
     do {                                                    \
@@ -38,6 +39,12 @@ __host__ __device__ __forceinline__ unsigned char nm_u8_sat(float v)
 // 256 / 8 are assumed. XCDs are not a device property: 32 CUs per XCD on gfx950.
 int nm_cu_count();
 int nm_xcd_count();
+// The grid of a kernel whose workgroups stride over `units`: enough to fill the chip, never more than there are units
+static inline int nm_fill_grid(long long units, int blocks_per_cu)
+{
+    const long long fill = (long long)nm_cu_count() * blocks_per_cu;
+    return (int)(units < fill ? units : fill);
+}
 static inline hipStream_t nm_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 
 // ---- profiling hook (nm_profile_events / nm_profile_event_pairs) ----

@@ -30,6 +30,7 @@
 #include "../../include/nm_abi.h"
 #include "nm_common.hpp"
 #include "nm_frame_weights_math.hpp"
+#include "nm_pair_batch.hpp"
 
 namespace {
 
@@ -218,34 +219,23 @@ __global__ __launch_bounds__(THREADS) void frame_weights_col_kernel(const FwOut 
     if (COUNTS && cur >= 0) flush_counts<COUNTS>(s_cnt, counts, cur, n_seed, n_valid);
 }
 
-__global__ __launch_bounds__(2 * MAX_FRAMES) void frame_weights_zero_kernel(unsigned long long *__restrict__ counts, int n)
-{
-    if ((int)threadIdx.x < 2 * n) counts[threadIdx.x] = 0;
-}
-
-bool shape_ok(int n, int fw, int fh)
-{
-    return n >= 1 && n <= MAX_FRAMES && fw >= 1 && fw <= NM_SIZE_LIMIT && fh >= 1 && fh <= NM_SIZE_LIMIT;
-}
+bool shape_ok(int n, int fw, int fh) { return n >= 1 && n <= MAX_FRAMES && nm_size_ok(fw) && nm_size_ok(fh); }
 
 bool args_ok(int n, const unsigned char *const *frames, int fw, int fh, int lo, int hi, int min_count, int R, int margin,
              void *const *masks, int mask_format, float *const *wts, unsigned short *const *dist2,
              const unsigned long long *counts)
 {
     if (!shape_ok(n, fw, fh) || lo < 0 || lo > 255 || hi < 0 || hi > 255 || min_count < 1 || min_count > 9 || R < 1 ||
-        R > MAX_RADIUS || margin < 0 || margin >= R || (mask_format != NM_TEX_U8N && mask_format != NM_TEX_F32) || !frames ||
+        R > MAX_RADIUS || margin < 0 || margin >= R || (mask_format != NM_TEX_U8N && mask_format != NM_TEX_F32) ||
         !(masks || wts || dist2 || counts))
         return false;
-    for (int k = 0; k < n; ++k)
-        if (!frames[k] || (masks && !masks[k]) || (wts && !wts[k]) || (dist2 && !dist2[k])) return false;
-    return true;
+    return nmp::tables_ok(n, {frames}, {masks, wts, dist2}, {});
 }
 
 int grid_of(long long units)
 {
-    const int cap = g_grid_cap.load();
-    const long long fill = cap > 0 ? cap : (long long)nm_cu_count() * BLOCKS_PER_CU;
-    return (int)(units < fill ? units : fill);
+    const int cap = g_grid_cap.load();                 // nm_frame_weights_set_grid_cap: tests make small grids walk far
+    return cap > 0 ? (int)(units < cap ? units : cap) : nm_fill_grid(units, BLOCKS_PER_CU);
 }
 
 }  // namespace
@@ -269,18 +259,11 @@ int nm_frame_weights_batch_dev(int n, const unsigned char *const *frames, int fw
         return (int)hipErrorInvalidValue;
     FwFrames a;
     FwOut o;
-    for (int k = 0; k < MAX_FRAMES; ++k) {
-        a.frames[k] = k < n ? reinterpret_cast<const uchar4 *>(frames[k]) : nullptr;
-        o.masks[k] = k < n && masks ? masks[k] : nullptr;
-        o.wts[k] = k < n && wts ? wts[k] : nullptr;
-        o.dist2[k] = k < n && dist2 ? dist2[k] : nullptr;
-    }
+    nmp::fill_slots_as(a.frames, frames, 0, n);
+    nmp::fill_slots(o.masks, masks, 0, n); nmp::fill_slots(o.wts, wts, 0, n); nmp::fill_slots(o.dist2, dist2, 0, n);
     unsigned char *g = reinterpret_cast<unsigned char *>((reinterpret_cast<size_t>(workspace) + WS_ALIGN - 1) & ~(WS_ALIGN - 1));
     const hipStream_t st = nm_stream(stream);
-    if (counts) {
-        hipLaunchKernelGGL(frame_weights_zero_kernel, dim3(1), dim3(2 * MAX_FRAMES), 0, st, counts, n);
-        NM_LAUNCH_CHECK();
-    }
+    if (counts) NM_RETURN_IF(nmp::launch_zero_u64(counts, 2 * (size_t)n, st));
     const int nblk = nm_divup(fw, 64);
     const int strips = nm_divup(fh, ROW_SR), chunks = nm_divup(nblk, ROW_CB);
     const auto row = min_count > 1 ? frame_weights_row_kernel<true> : frame_weights_row_kernel<false>;

@@ -9,6 +9,7 @@
 // neighbouring texels), then each frame's filter, uchar4 rounding and gray (nm_gray.hpp) run from registers and write
 // one uchar4 and one float. Per call the map is read once, each frame's texels about once, each output written once.
 #include "nm_gray.hpp"
+#include "nm_pair_batch.hpp"
 #include "nm_warp_math.hpp"
 
 namespace {
@@ -104,19 +105,14 @@ int nm_frame_ingest_batch_f32(int n, const unsigned char *const *frames, int fw,
                               const float *map_y, int cols, int rows, float *const *gray,
                               unsigned char *const *undistorted, void *stream)
 {
-    const auto size_ok = [](int v) { return v >= 1 && v <= NM_SIZE_LIMIT; };
-    if (n < 1 || n > NM_INGEST_MAX_BATCH || !size_ok(fw) || !size_ok(fh) || !size_ok(cols) || !size_ok(rows))
+    if (n < 1 || n > NM_INGEST_MAX_BATCH || !nm_size_ok(fw) || !nm_size_ok(fh) || !nm_size_ok(cols) || !nm_size_ok(rows))
         return (int)hipErrorInvalidValue;
-    if (!frames || !gray || (!map_x) != (!map_y)) return (int)hipErrorInvalidValue;
+    if (!nmp::tables_ok(n, {frames, gray}, {undistorted}, {}) || (!map_x) != (!map_y)) return (int)hipErrorInvalidValue;
     const bool map = map_x != nullptr;
     if (!map && (undistorted || cols != fw || rows != fh)) return (int)hipErrorInvalidValue;
     IgArgs a;
-    for (int k = 0; k < NM_INGEST_MAX_BATCH; ++k) {
-        if (k < n && (!frames[k] || !gray[k] || (undistorted && !undistorted[k]))) return (int)hipErrorInvalidValue;
-        a.frames[k] = k < n ? reinterpret_cast<const uchar4 *>(frames[k]) : nullptr;
-        a.gray[k] = k < n ? gray[k] : nullptr;
-        a.undistorted[k] = k < n && undistorted ? reinterpret_cast<uchar4 *>(undistorted[k]) : nullptr;
-    }
+    nmp::fill_slots_as(a.frames, frames, 0, n); nmp::fill_slots(a.gray, gray, 0, n);
+    nmp::fill_slots_as(a.undistorted, undistorted, 0, n);
     const hipStream_t st = nm_stream(stream);
     if (!map) launch<false, false>(a, n, cols, rows, fw, fh, nullptr, nullptr, st);
     else if (undistorted) launch<true, true>(a, n, cols, rows, fw, fh, map_x, map_y, st);

@@ -20,7 +20,7 @@ inline Lattice lattice_of(int fw, int fh, int stride)
 }
 inline bool lattice_ok(int fw, int fh, int stride)
 {
-    if (fw < 1 || fw > NM_SIZE_LIMIT || fh < 1 || fh > NM_SIZE_LIMIT || stride < 1 || stride > MAX_STRIDE) return false;
+    if (!nm_size_ok(fw) || !nm_size_ok(fh) || stride < 1 || stride > MAX_STRIDE) return false;
     return (long long)(fw / stride) * (long long)(fh / stride) <= MAX_LATTICE;
 }
 struct FrameTables {                        // a link stage's gray planes: 2 x 64 pointers, 1 KB of kernel arguments

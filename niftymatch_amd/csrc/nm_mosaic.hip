@@ -128,8 +128,7 @@ __host__ __device__ __forceinline__ int mp_given(const float *M, int status)
 
 inline bool mp_sizes_ok(int n, int fw, int fh, int cw, int ch, int ox, int oy, const void *records)
 {
-    const auto size_ok = [](int v) { return v >= 1 && v <= NM_SIZE_LIMIT; };
-    return n >= 1 && n <= NM_MOSAIC_MAX_BATCH && size_ok(fw) && size_ok(fh) && size_ok(cw) && size_ok(ch) &&
+    return n >= 1 && n <= NM_MOSAIC_MAX_BATCH && nm_size_ok(fw) && nm_size_ok(fh) && nm_size_ok(cw) && nm_size_ok(ch) &&
            ox > -MP_OFFSET_LIMIT && ox < MP_OFFSET_LIMIT && oy > -MP_OFFSET_LIMIT && oy < MP_OFFSET_LIMIT && records;
 }
 
@@ -356,17 +355,15 @@ int nm_transform_blend_batch_gain(unsigned char *canvas, int cw, int ch, float *
                                   int mask_format, const void *const *wts, int wts_format, const nm_mosaic_record *records,
                                   const float *gains, void *stream)
 {
-    if (n < 1 || n > NM_MOSAIC_MAX_BATCH || cw < 1 || cw > NM_SIZE_LIMIT || ch < 1 || ch > NM_SIZE_LIMIT || fw < 1 || fh < 1 ||
-        !scalar_fmt(mask_format) || !scalar_fmt(wts_format))
+    if (n < 1 || n > NM_MOSAIC_MAX_BATCH || !nm_size_ok(cw) || !nm_size_ok(ch) || fw < 1 || fh < 1 || !scalar_fmt(mask_format) ||
+        !scalar_fmt(wts_format))
         return (int)hipErrorInvalidValue;
     if (!canvas || !canvas_wts || !records) return (int)hipErrorInvalidValue;
     FrameArgs a;
     if (!fill_frame_args(a, n, frames, masks, wts)) return (int)hipErrorInvalidValue;
     // The grid is fixed here, before the rectangles exist: enough workgroups to fill the chip, never more than the
     // canvas has tiles. A workgroup whose tiles lie outside every rectangle returns after staging the records.
-    const long long canvas_tiles = (long long)nm_divup(cw, CANVAS_TILE_W) * nm_divup(ch, CANVAS_TILE_H);
-    const long long fill = (long long)nm_cu_count() * MB_BLOCKS_PER_CU;
-    const int grid = (int)(canvas_tiles < fill ? canvas_tiles : fill);
+    const int grid = nm_fill_grid((long long)nm_divup(cw, CANVAS_TILE_W) * nm_divup(ch, CANVAS_TILE_H), MB_BLOCKS_PER_CU);
     const auto kernel = gains ? transform_blend_batch_kernel<true> : transform_blend_batch_kernel<false>;
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(CANVAS_THREADS), 0, nm_stream(stream), a, n,
                        reinterpret_cast<uchar4 *>(canvas), cw, ch, canvas_wts, fw, fh, mask_format, wts_format, records, gains);

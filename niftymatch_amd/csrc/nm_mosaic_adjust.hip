@@ -216,7 +216,7 @@ bool host_solve(const Params &P, const LinkIdx &X, const double *rows, std::vect
 
 bool sizes_ok(int capA, int fw, int fh)
 {
-    return nmp::cap_ok(capA) && fw >= 1 && fw <= NM_SIZE_LIMIT && fh >= 1 && fh <= NM_SIZE_LIMIT;
+    return nmp::cap_ok(capA) && nm_size_ok(fw) && nm_size_ok(fh);
 }
 
 bool ma_args_ok(int n, int L, const int *link_a, const int *link_b, const float *const *src_x, const float *const *src_y,

@@ -287,12 +287,12 @@ bool tile_cap_ok(long long tile_cap) { return tile_cap >= 1 && tile_cap <= MAX_T
 bool bands_args_ok(int n, const void *tiles, long long tile_cap, const void *records, const void *canvas, int cw, int ch,
                    int R, double sigma, const void *workspace)
 {
-    return n >= 1 && n <= MAX_FRAMES && tile_cap_ok(tile_cap) && cw >= 1 && cw <= NM_SIZE_LIMIT && ch >= 1 && ch <= NM_SIZE_LIMIT &&
-           R >= 0 && R <= MAX_R && (R == 0 || (std::isfinite(sigma) && sigma > 0.0)) && tiles && records && canvas &&
-           workspace && ((reinterpret_cast<size_t>(workspace) | reinterpret_cast<size_t>(tiles)) & 15) == 0;
+    return n >= 1 && n <= MAX_FRAMES && tile_cap_ok(tile_cap) && nm_size_ok(cw) && nm_size_ok(ch) && R >= 0 && R <= MAX_R &&
+           (R == 0 || (std::isfinite(sigma) && sigma > 0.0)) && tiles && records && canvas && workspace && ((reinterpret_cast<size_t>(workspace) | reinterpret_cast<size_t>(tiles)) & 15) == 0;
 }
 
-int fill_grid() { return nm_cu_count() * BLOCKS_PER_CU; }
+// the grid of the kernels that stride over the frames' own tiles, whose number only the device knows: the whole fill
+int fill_grid() { return nm_fill_grid(LLONG_MAX, BLOCKS_PER_CU); }
 
 // ---- the host twin's pieces: the same functions, walked serially ----
 void host_blur(const Taps &T, int R, bool vert, const int4 &b, int k, int cw, int ch, const float4 *tile,
@@ -328,7 +328,7 @@ extern "C" {
 
 size_t nm_mosaic_bands_workspace_bytes(int n, long long tile_cap, int cw, int ch)
 {
-    if (n < 1 || n > MAX_FRAMES || !tile_cap_ok(tile_cap) || cw < 1 || cw > NM_SIZE_LIMIT || ch < 1 || ch > NM_SIZE_LIMIT) return 0;
+    if (n < 1 || n > MAX_FRAMES || !tile_cap_ok(tile_cap) || !nm_size_ok(cw) || !nm_size_ok(ch)) return 0;
     return workspace_bytes(n, tile_cap, cw, ch);
 }
 
@@ -345,8 +345,8 @@ int nm_mosaic_warp_tiles(int n, const unsigned char *const *frames, int fw, int 
                          int mask_format, const void *const *wts, int wts_format, const nm_mosaic_record *records,
                          const float *gains, float *tiles, long long tile_cap, int *stats, void *stream)
 {
-    if (n < 1 || n > MAX_FRAMES || fw < 1 || fw > NM_SIZE_LIMIT || fh < 1 || fh > NM_SIZE_LIMIT || !scalar_fmt(mask_format) ||
-        !scalar_fmt(wts_format) || !tile_cap_ok(tile_cap))
+    if (n < 1 || n > MAX_FRAMES || !nm_size_ok(fw) || !nm_size_ok(fh) || !scalar_fmt(mask_format) || !scalar_fmt(wts_format) ||
+        !tile_cap_ok(tile_cap))
         return (int)hipErrorInvalidValue;
     if (!records || !tiles || !stats || (reinterpret_cast<size_t>(tiles) & 15)) return (int)hipErrorInvalidValue;
     FrameArgs a;
@@ -369,8 +369,8 @@ int nm_mosaic_bands_dev(int n, const float *tiles, long long tile_cap, const nm_
     const Workspace W = carve(workspace, n, tile_cap, cw, ch);
     const float4 *t4 = reinterpret_cast<const float4 *>(tiles);
     uchar4 *cv = reinterpret_cast<uchar4 *>(canvas);
-    const long long canvas_tiles = (long long)nm_divup(cw, CANVAS_TILE_W) * nm_divup(ch, CANVAS_TILE_H);
-    const int fill = fill_grid(), cgrid = (int)(canvas_tiles < fill ? canvas_tiles : fill);
+    const int fill = fill_grid();
+    const int cgrid = nm_fill_grid((long long)nm_divup(cw, CANVAS_TILE_W) * nm_divup(ch, CANVAS_TILE_H), BLOCKS_PER_CU);
     hipStream_t st = nm_stream(stream);
     hipLaunchKernelGGL(mosaic_bands_canvas_kernel<false>, dim3(cgrid), dim3(THREADS), 0, st, n, records, tile_cap, t4, cw, ch,
                        W.label, (const float4 *)nullptr, (const float *)nullptr, (uchar4 *)nullptr, (float *)nullptr);
@@ -403,10 +403,7 @@ int nm_mosaic_bands_host(int n, const float *tiles, long long tile_cap, const nm
         box[k] = rect[k] = make_int4(0, 0, 0, 0);
         if (!frame_used(rec.placed, rec.nw, rec.nh, tile_cap)) continue;
         box[k] = make_int4(rec.tx, rec.ty, rec.nw, rec.nh);
-        const long long x0 = rec.tx > 0 ? rec.tx : 0, y0 = rec.ty > 0 ? rec.ty : 0;
-        const long long x1 = (long long)rec.tx + rec.nw < cw ? (long long)rec.tx + rec.nw : cw;
-        const long long y1 = (long long)rec.ty + rec.nh < ch ? (long long)rec.ty + rec.nh : ch;
-        if (x1 > x0 && y1 > y0) rect[k] = make_int4((int)x0, (int)y0, (int)x1, (int)y1);
+        rect[k] = clip_rect(rec.tx, rec.ty, rec.nw, rec.nh, cw, ch);
     }
     const auto slot_at = [&](int k, int px, int row) {
         return (size_t)k * (size_t)tile_cap + (size_t)(row - box[k].y) * box[k].z + (px - box[k].x);

@@ -2,8 +2,9 @@
 // frames, and the per-frame gains that level them (include/nm_abi.h has the written semantics). No reference counterpart.
 // The gained blend that applies the gains is nm_transform_blend_batch_gain (nm_mosaic.hip). On the caller's stream, no
 // allocation, no synchronisation, no host read, no workspace; no kernel waits for another workgroup:
-//   measure  ONE memset node (the L x 7 sums to zero) and ONE launch whatever L is: the 64 frame pointers (512 B) and the
-//            links' frame indices (2 x 256 B) travel as kernel arguments. Grid (parts, L): the lattice walk over frame a
+//   measure  TWO launches whatever L is, the first one workgroup that zeroes the L x 7 sums (nmp::launch_zero_u64, a
+//            kernel and not a memset node: see there). The 64 frame pointers (512 B) and the links' frame indices
+//            (2 x 256 B) travel as kernel arguments. Grid (parts, L): the lattice walk over frame a
 //            (one of three copies: nm_lattice.hpp), a link's tiles dealt to its `parts` workgroups of four waves (parts x
 //            L ~ 4096 workgroups when the lattice has that many tiles, so one link alone spreads over up to 256). A wave
 //            takes a lattice row, its lanes 64 neighbouring lattice columns: one uchar4 of frame a (at stride 1
@@ -53,7 +54,7 @@ __global__ __launch_bounds__(THREADS) void mosaic_exposure_sums_kernel(const Sum
     float Hl[9];
 #pragma unroll
     for (int q = 0; q < 9; ++q) Hl[q] = H[l * 9 + q];
-    if (!nml::usable(link_status ? link_status[l] : 1, Hl)) return;      // uniform: the memset's zeros stay
+    if (!nml::usable(link_status ? link_status[l] : 1, Hl)) return;      // uniform: the zeroing's zeros stay
     const Frames F{A.frames[A.X.a[l]], A.frames[A.X.b[l]], mask, fw, fh};
     u64 s[SUMS] = {0, 0, 0, 0, 0, 0, 0};
     for (int t = blockIdx.x; t < tiles; t += gridDim.x) {        // the lattice walk: one of three copies (nm_lattice.hpp)
@@ -153,14 +154,14 @@ extern "C" int nm_mosaic_exposure_sums_dev(int n, int L, const unsigned char *co
                                            void *stream)
 {
     if (!sums_args_ok(n, L, frames, link_a, link_b, fw, fh, H, stride, lo, hi, sums)) return (int)hipErrorInvalidValue;
-    NM_RETURN_IF(hipMemsetAsync(sums, 0, (size_t)L * SUMS * sizeof(u64), nm_stream(stream)));
+    NM_RETURN_IF(nmp::launch_zero_u64(sums, (size_t)L * SUMS, nm_stream(stream)));
     const Lattice T = lattice_of(fw, fh, stride);
     if (T.tiles == 0) return 0;                                    // a stride beyond the frame: an empty lattice, all sums 0
     int parts = nm_divup(GRID_TARGET, L);
     parts = parts > MAX_PARTS ? MAX_PARTS : parts;
     parts = parts > T.tiles ? T.tiles : parts;
     SumsArgs A;
-    for (int k = 0; k < MAX_FRAMES; ++k) A.frames[k] = k < n ? reinterpret_cast<const uchar4 *>(frames[k]) : nullptr;
+    nmp::fill_slots_as(A.frames, frames, 0, n);
     A.X = link_index(L, link_a, link_b);
     hipLaunchKernelGGL(mosaic_exposure_sums_kernel, dim3(parts, L), dim3(THREADS), 0, nm_stream(stream), A, fw, fh, mask, H,
                        link_status, stride, lo, hi, T.lw, T.lh, T.tiles_x, T.tiles, sums);

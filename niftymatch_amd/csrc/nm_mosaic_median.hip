@@ -35,15 +35,6 @@ using namespace nmmd;
 
 constexpr int WAVES = 2, THREADS = 64 * WAVES, TILE_W = 64, TILE_H = WAVES, BLOCKS_PER_CU = 8;
 
-// (x0, y0, x1, y1) of a used frame's rectangle on the canvas, clipped in 64-bit; (0, 0, 0, 0) when empty
-__host__ __device__ __forceinline__ int4 clip_rect(int tx, int ty, int nw, int nh, int cw, int ch)
-{
-    const long long x0 = tx > 0 ? tx : 0, y0 = ty > 0 ? ty : 0;
-    const long long x1 = (long long)tx + nw < cw ? (long long)tx + nw : cw;
-    const long long y1 = (long long)ty + nh < ch ? (long long)ty + nh : ch;
-    return x1 > x0 && y1 > y0 ? make_int4((int)x0, (int)y0, (int)x1, (int)y1) : make_int4(0, 0, 0, 0);
-}
-
 __host__ __device__ __forceinline__ size_t sample_at(int k, long long tile_cap, const int4 &b, int px, int row)
 {
     return (size_t)k * (size_t)tile_cap + (size_t)(row - b.y) * b.z + (px - b.x);
@@ -167,17 +158,12 @@ __global__ __launch_bounds__(THREADS) void mosaic_median_kernel(int n, const nm_
     }
 }
 
-__global__ __launch_bounds__(2 * MAX_FRAMES) void mosaic_median_zero_kernel(unsigned long long *__restrict__ counts, int n)
-{
-    if ((int)threadIdx.x < 2 * n) counts[threadIdx.x] = 0;
-}
-
 bool median_args_ok(int n, const void *tiles, long long tile_cap, const void *records, const void *canvas, int cw, int ch,
                     int mode, float w_min, float tau)
 {
-    return n >= 1 && n <= MAX_FRAMES && tile_cap >= 1 && tile_cap <= MAX_TILE_CAP && cw >= 1 && cw <= NM_SIZE_LIMIT && ch >= 1 &&
-           ch <= NM_SIZE_LIMIT && mode >= 0 && mode < MODES && std::isfinite(w_min) && w_min >= 0.f && tau >= 0.f && tiles &&
-           records && canvas && (reinterpret_cast<size_t>(tiles) & 15) == 0;
+    return n >= 1 && n <= MAX_FRAMES && tile_cap >= 1 && tile_cap <= MAX_TILE_CAP && nm_size_ok(cw) && nm_size_ok(ch) &&
+           mode >= 0 && mode < MODES && std::isfinite(w_min) && w_min >= 0.f && tau >= 0.f && tiles && records && canvas &&
+           (reinterpret_cast<size_t>(tiles) & 15) == 0;
 }
 
 }  // namespace
@@ -190,12 +176,8 @@ int nm_mosaic_median_dev(int n, const float *tiles, long long tile_cap, const nm
 {
     if (!median_args_ok(n, tiles, tile_cap, records, canvas, cw, ch, mode, w_min, tau)) return (int)hipErrorInvalidValue;
     hipStream_t st = nm_stream(stream);
-    if (counts) {
-        hipLaunchKernelGGL(mosaic_median_zero_kernel, dim3(1), dim3(2 * MAX_FRAMES), 0, st, counts, n);
-        NM_LAUNCH_CHECK();
-    }
-    const long long canvas_tiles = (long long)nm_divup(cw, TILE_W) * nm_divup(ch, TILE_H);
-    const int fill = nm_cu_count() * BLOCKS_PER_CU, grid = (int)(canvas_tiles < fill ? canvas_tiles : fill);
+    if (counts) NM_RETURN_IF(nmp::launch_zero_u64(counts, 2 * (size_t)n, st));
+    const int grid = nm_fill_grid((long long)nm_divup(cw, TILE_W) * nm_divup(ch, TILE_H), BLOCKS_PER_CU);
     const auto kernel = mode == NM_MEDIAN_MEAN
                             ? (counts ? mosaic_median_kernel<NM_MEDIAN_MEAN, true> : mosaic_median_kernel<NM_MEDIAN_MEAN, false>)
                             : (counts ? mosaic_median_kernel<NM_MEDIAN_SELECT, true> : mosaic_median_kernel<NM_MEDIAN_SELECT, false>);

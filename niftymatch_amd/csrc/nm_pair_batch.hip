@@ -1,4 +1,5 @@
-// nm_pair_batch.hip -- the one kernel the pair-batch stages share (nm_pair_batch.hpp): the counts of guided and mutual matching.
+// nm_pair_batch.hip -- the kernels the batched stages share (nm_pair_batch.hpp): the counts of guided and mutual matching, and
+// the zeroing of the 64-bit sums and counts that median, frame weights and exposure sums add into.
 #include "nm_common.hpp"
 #include "nm_pair_batch.hpp"
 
@@ -28,6 +29,12 @@ __global__ __launch_bounds__(TB) void pair_count_kernel(const CtArgs a, int capA
     }
 }
 
+// one workgroup, a stride loop: the callers zero at most a few thousand words
+__global__ __launch_bounds__(TB) void zero_u64_kernel(unsigned long long *__restrict__ p, size_t words)
+{
+    for (size_t i = threadIdx.x; i < words; i += TB) p[i] = 0;
+}
+
 }  // namespace
 
 int nmp::launch_pair_count(int n, int *const *result, int capA, int *count, hipStream_t stream)
@@ -37,4 +44,10 @@ int nmp::launch_pair_count(int n, int *const *result, int capA, int *count, hipS
     hipLaunchKernelGGL(pair_count_kernel, dim3(n), dim3(TB), 0, stream, c, capA, count);
     NM_LAUNCH_CHECK();
     return 0;
+}
+
+hipError_t nmp::launch_zero_u64(unsigned long long *p, size_t words, hipStream_t stream)
+{
+    hipLaunchKernelGGL(zero_u64_kernel, dim3(1), dim3(TB), 0, stream, p, words);
+    return hipGetLastError();
 }

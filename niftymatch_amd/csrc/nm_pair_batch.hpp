@@ -82,6 +82,12 @@ template <int N, class D, class S> inline void fill_slots(D *(&dst)[N], S *const
     for (int s = 0; s < N; ++s) dst[s] = (src && first + s < n) ? src[first + s] : nullptr;
 }
 
+// fill_slots for a table the kernel reads through another pointer type (BGRA bytes as uchar4)
+template <int N, class D, class S> inline void fill_slots_as(D *(&dst)[N], S *const *src, int first, int n)
+{
+    for (int s = 0; s < N; ++s) dst[s] = (src && first + s < n) ? reinterpret_cast<D *>(src[first + s]) : nullptr;
+}
+
 struct PointTables {                        // the point pairs of RANSAC and refit: 6 x 64 pointers, 3 KB of kernel arguments
     const float *sx[MAX_BATCH];
     const float *sy[MAX_BATCH];
@@ -99,5 +105,9 @@ struct PointTables {                        // the point pairs of RANSAC and ref
 
 // count[k] = entries >= 0 among the capA results of pair k, k < n (nm_pair_batch.hip): one launch, grid n, on `stream`
 int launch_pair_count(int n, int *const *result, int capA, int *count, hipStream_t stream);
+
+// p[0 .. words) = 0 (nm_pair_batch.hip): one launch of one workgroup on `stream`. A kernel and not hipMemsetAsync: a captured
+// memset node replayed correctly once and left other values from the second replay on ("Median composite")
+hipError_t launch_zero_u64(unsigned long long *p, size_t words, hipStream_t stream);
 
 }  // namespace nmp

@@ -267,7 +267,7 @@ def test_measure_solve_place_blend_on_the_loop_closure_views(nm, cuda):
     A = LC.view_maps()
     chain = np.stack([np.linalg.inv(np.linalg.inv(A[0]) @ a) for a in A])
     chain = (chain / chain[:, 2:, 2:]).astype(F32).reshape(K, 9)
-    scenes = [scaled_views(host_views(seed)) for seed in (91, 92)]
+    scenes = [scaled_views(host_views(seed)) for seed in (91, 93, 92)]
     frames = [_t(v, cuda) for v in scenes[0][0]]
     dH, dchain = _t(Hs, cuda), _t(chain, cuda)
     ones = torch.ones((LC.VH, LC.VW), dtype=torch.float32, device=cuda)
@@ -319,13 +319,14 @@ def test_measure_solve_place_blend_on_the_loop_closure_views(nm, cuda):
     g = torch.cuda.CUDAGraph()
     with torch.cuda.graph(g, stream=s):
         enqueue()
-    for f, v in zip(frames, scenes[1][0]):
-        f.copy_(_t(v, cuda))
-    torch.cuda.synchronize()
-    g.replay()
-    torch.cuda.synchronize()
-    replayed = host()
-    check(*scenes[1], replayed)
+    for views, t in scenes[1:]:                              # two replays, new frame contents each time
+        for f, v in zip(frames, views):
+            f.copy_(_t(v, cuda))
+        torch.cuda.synchronize()
+        g.replay()
+        torch.cuda.synchronize()
+        replayed = host()
+        check(views, t, replayed)
     with torch.cuda.stream(s):
         enqueue()
     s.synchronize()
