@@ -1539,6 +1539,107 @@ NM_API int nm_frame_weights_host(int n, const unsigned char *const *frames, int 
                                  unsigned long long *counts);
 NM_API int nm_frame_weights_set_grid_cap(int cap);
 
+/* ---- Frame quality and keyframe choice (no reference counterpart): which frames of a video go into a mosaic at all. Three
+ * entries and their host twins, each on `stream` with no allocation, no synchronisation and no host read, no workgroup
+ * waits for another: capturable into a HIP graph behind nm_frame_ingest_batch_f32, nm_frame_weights_batch_dev and
+ * nm_mosaic_plan_f32. Every table is a HOST table of device pointers, as in the stages above.
+ *
+ * nm_frame_quality_batch_dev: exact integer statistics per frame and per cell of a gx x gy grid. TWO launches whatever n is
+ * (a kernel that zeroes stats, then one walk over the pixels).
+ *   frames: n in [1, NM_FRAME_QUALITY_MAX_BATCH] device pointers to fw x fh uchar4 (BGRA) frames; pointers may repeat.
+ *   masks: optional table of n fw x fh planes in mask_format NM_TEX_U8N or NM_TEX_F32. lo, hi in [0, 255]. gx in
+ *   [1, min(NM_FRAME_QUALITY_MAX_GRID, fw)], gy in [1, min(NM_FRAME_QUALITY_MAX_GRID, fh)].
+ *   DEFINITION. For frame k and pixel p = (x, y):
+ *     mx = max(B, G, R); alpha is ignored. Y = (7 B + 72 G + 21 R + 50) / 100 in integer arithmetic, in [0, 255]: the
+ *     gray plane's weights as a rounded rational, this stage's own luminance.
+ *     ELIGIBLE: no masks, or the mask is valid at p under the `mask > 0.5` rule of the link stages: byte >= 128
+ *     (NM_TEX_U8N), value > 0.5f (NM_TEX_F32). DARK: eligible and mx < lo. BRIGHT: eligible and mx > hi. GOOD: eligible and
+ *     neither. MEASURED: p and its four edge neighbours lie inside the frame and all five are good.
+ *     On measured pixels L = Y(x-1,y) + Y(x+1,y) + Y(x,y-1) + Y(x,y+1) - 4 Y(x,y) and
+ *     G2 = (Y(x+1,y) - Y(x-1,y))^2 + (Y(x,y+1) - Y(x,y-1))^2.
+ *     Cell of p: ((x gx) / fw, (y gy) / fh), integer division.
+ *   stats: device, n x gy x gx x 8 unsigned 64-bit words, zeroed by the call. Per (frame, cell): [0] measured pixels,
+ *     [1] sum of Y, [2] of Y^2, [3] of L^2, [4] of G2 over the measured pixels, [5] dark, [6] bright, [7] eligible pixels.
+ *   BOUNDS. Per pixel L^2 <= 1020^2 = 1 040 400 and G2 <= 2 x 255^2 = 130 050 fit 32 bits; per frame every sum stays below
+ *     32767^2 x 1 040 400 < 2^51 < 2^53, so a double holds each word exactly. All words are exact integers: they do not
+ *     depend on scheduling, on n, on the slot a frame sits in or on the previous contents of stats.
+ *   Refused with hipErrorInvalidValue before any launch or device access: n outside [1, 64], fw or fh outside [1, 32767],
+ *     lo or hi outside [0, 255], gx or gy out of range, an unknown mask_format with masks given, a NULL frames or stats, a
+ *     NULL among the first n entries of a given table.
+ * nm_frame_quality_host: the same with every pointer in host memory (csrc/nm_frame_quality_math.hpp): identical words.
+ * nm_frame_quality_set_grid_cap (tuning and tests, process-wide): the walk launches min(units, cap) workgroups; cap >= 1
+ *   fixes the cap, any other value restores the default (8 per compute unit). Results are identical for every cap. Returns
+ *   the previous setting (0: the default).
+ *
+ * nm_keyframe_pick_dev: which frames to keep, ONE launch of one workgroup. Inputs on the device: stats with its gx, gy;
+ * chain (n x 9 fp32, row k = M_k mapping mosaic coordinates to frame-k pixels: the chain of nm_mosaic_plan_f32 or
+ * nm_mosaic_adjust_dev_f32); frame_status (optional, n ints). Host values: n, fw, fh, keep in [1, 64]; cell_min >= 1
+ * (suggested 64), min_pixels >= 0 (1024), max_bad in [0, 1] (0.25), rel in [0, 1] (0.6), w in [0, 8] (2),
+ * 0 <= d_min <= d_max finite, in pixels (32, 128), carry.
+ *   DEFINITION, every fp operation a single IEEE operation in the written order, no contraction:
+ *     Totals: the integer sums over a frame's cells of words [0], [1], [5], [6], [7].
+ *     Score: a cell QUALIFIES when its word [0] >= cell_min; its sharpness is (double)[3] / (double)[0]. The frame's score
+ *       is the LOWER median of the qualifying cells' sharpness ordered by (value, cell index), 0 without one. With
+ *       gx = gy = 1 it is the mean squared Laplacian.
+ *     Usable: frame_status is NULL or 1 and the nine chain values are finite and not all zero (else NM_KEYFRAME_STATUS); a
+ *       cell qualifies and the total measured count is >= min_pixels (else NM_KEYFRAME_FEW);
+ *       (double)(dark + bright) <= max_bad * (double)eligible (else NM_KEYFRAME_BAD).
+ *     Blurred: ref_k = the largest score of a usable frame j with |j - k| <= w (0 without one); a usable frame with
+ *       score_k < rel * ref_k is NM_KEYFRAME_BLURRED and not usable for the walk. rel = 0 turns the test off.
+ *     Motion: d(a, b) with W_a = invert3x3(M_a): for the corners c = (0,0), (fw-1,0), (0,fh-1), (fw-1,fh-1) of frame a,
+ *       q = project(M_b, project(W_a, c)) with the functions of the mosaic plan (csrc/nm_warp_math.hpp); d is the largest
+ *       |q.x - c.x| or |q.y - c.y| in fp32, +inf when a denominator is <= 0 or a value is not finite.
+ *     Walk: the first keyframe is frame 0 when carry != 0, whatever its flags (the previous chunk's last keyframe: a long
+ *       video is walked 63 new frames at a time), else the first usable frame. From keyframe `last`, the window closes at the
+ *       first usable j > last with d(last, j) > d_max; the candidates are the usable j > last before the closing frame with
+ *       d(last, j) >= d_min; the next keyframe is the candidate of the largest score, the lowest index on a tie; with no
+ *       candidate and a closing frame it is the closing frame, flagged NM_KEYFRAME_JUMP; with neither the walk ends. It
+ *       also ends after keep keyframes; key_count[1] = 1 when another keyframe would have followed.
+ *   Outputs (device, every entry written; all but keys and key_count optional): keys[keep] the chosen indices ascending,
+ *     -1 beyond the count; key_count[2] = count, truncated; key_status[keep] 1 for a filled slot else 0 (frame_status of
+ *     nm_mosaic_place_f32); flags[n] of NM_KEYFRAME_* bits; scores[n x 4] doubles: score, sum Y / measured, (dark + bright)
+ *     / eligible (0 for a zero divisor), ref; H_keys[(keep-1) x 9], H_status[keep-1]: H_keys[i] maps keyframe i pixels to
+ *     keyframe i+1 pixels: p = M_b W_a with p[3r+c] = fmaf(M_b[3r+2], W_a[6+c], fmaf(M_b[3r+1], W_a[3+c], M_b[3r] W_a[c])),
+ *     divided by p[8]; status 1 when both slots are filled, every value is finite and p[8] != 0, else a zero row and 0:
+ *     the H and status of nm_mosaic_plan_f32 and the start maps of the link stages on the gathered frames.
+ *   Refused with hipErrorInvalidValue before the launch: a host value out of range, d_min > d_max or either not finite,
+ *     max_bad or rel outside [0, 1], a NULL stats, chain, keys or key_count.
+ * nm_keyframe_pick_host: the same with every pointer in host memory, from the same functions: identical outputs.
+ *
+ * nm_slots_gather_dev: dst[i], i in [0, keep), receives the `bytes` bytes of src[keys[i]] when keys[i] lies in [0, n), else
+ * `bytes` copies of the byte `fill`. src: n device pointers (may repeat), dst: keep device pointers (must not overlap
+ * anything), keys on the device. ONE launch; 16-byte words when every pointer and bytes are multiples of 16, bytes
+ * otherwise (a matter of speed, not of results). Serves frames, planes, masks, weights, descriptor and coordinate tables and
+ * single count words. Refused: n or keep outside [1, 64], bytes outside [1, 2^31), a NULL table or entry, a NULL keys.
+ * nm_slots_gather_host: the same with every pointer in host memory.                                                  */
+#define NM_FRAME_QUALITY_MAX_BATCH 64
+#define NM_FRAME_QUALITY_MAX_GRID 8
+#define NM_KEYFRAME_STATUS 1
+#define NM_KEYFRAME_FEW 2
+#define NM_KEYFRAME_BAD 4
+#define NM_KEYFRAME_BLURRED 8
+#define NM_KEYFRAME_KEY 16
+#define NM_KEYFRAME_JUMP 32
+NM_API int nm_frame_quality_batch_dev(int n, const unsigned char *const *frames, int fw, int fh, const void *const *masks,
+                                      int mask_format, int lo, int hi, int gx, int gy, unsigned long long *stats,
+                                      void *stream);
+NM_API int nm_frame_quality_host(int n, const unsigned char *const *frames, int fw, int fh, const void *const *masks,
+                                 int mask_format, int lo, int hi, int gx, int gy, unsigned long long *stats);
+NM_API int nm_frame_quality_set_grid_cap(int cap);
+NM_API int nm_keyframe_pick_dev(int n, const unsigned long long *stats, int gx, int gy, const float *chain,
+                                const int *frame_status, int fw, int fh, int keep, long long cell_min, long long min_pixels,
+                                double max_bad, double rel, int w, float d_min, float d_max, int carry, int *keys,
+                                int *key_count, int *key_status, int *flags, double *scores, float *H_keys, int *H_status,
+                                void *stream);
+NM_API int nm_keyframe_pick_host(int n, const unsigned long long *stats, int gx, int gy, const float *chain,
+                                 const int *frame_status, int fw, int fh, int keep, long long cell_min, long long min_pixels,
+                                 double max_bad, double rel, int w, float d_min, float d_max, int carry, int *keys,
+                                 int *key_count, int *key_status, int *flags, double *scores, float *H_keys, int *H_status);
+NM_API int nm_slots_gather_dev(int n, const void *const *src, int keep, void *const *dst, const int *keys, long long bytes,
+                               int fill, void *stream);
+NM_API int nm_slots_gather_host(int n, const void *const *src, int keep, void *const *dst, const int *keys, long long bytes,
+                                int fill);
+
 /* ---- Link proposal: which frame pairs of a sequence to link at all (no reference counterpart). Two steps, both on
  * `stream` with no allocation, no synchronisation and no host read -- capturable into a HIP graph.
  * nm_link_votes_dev_u8: the u8 matcher's ratio test for ALL ordered pairs of n in [1, NM_LINK_PROPOSE_MAX_FRAMES] frames,

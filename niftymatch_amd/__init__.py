@@ -5,6 +5,7 @@ niftymatch_amd/nm/ that mirror the reference's API. This Python module is host p
 multi-GPU launcher: it binds the C ABI with ctypes and uses torch only for device memory, streams and
 torch.distributed. There is NO CPU fallback: if the library is missing, every entry point raises.
 """
+import collections
 import ctypes as C
 import math
 import os
@@ -167,6 +168,15 @@ _SIGNATURES = {
     "nm_frame_weights_batch_dev": (_I, [_I, _P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P]),
     "nm_frame_weights_host": (_I, [_I, _P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P]),
     "nm_frame_weights_set_grid_cap": (_I, [_I]),
+    "nm_frame_quality_batch_dev": (_I, [_I, _P, _I, _I, _P, _I, _I, _I, _I, _I, _P, _P]),
+    "nm_frame_quality_host": (_I, [_I, _P, _I, _I, _P, _I, _I, _I, _I, _I, _P]),
+    "nm_frame_quality_set_grid_cap": (_I, [_I]),
+    "nm_keyframe_pick_dev": (_I, [_I, _P, _I, _I, _P, _P, _I, _I, _I, C.c_longlong, C.c_longlong, C.c_double, C.c_double, _I, _F,
+                                  _F, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "nm_keyframe_pick_host": (_I, [_I, _P, _I, _I, _P, _P, _I, _I, _I, C.c_longlong, C.c_longlong, C.c_double, C.c_double, _I, _F,
+                                   _F, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "nm_slots_gather_dev": (_I, [_I, _P, _I, _P, _P, C.c_longlong, _I, _P]),
+    "nm_slots_gather_host": (_I, [_I, _P, _I, _P, _P, C.c_longlong, _I]),
     "nm_link_votes_workspace_bytes": (_SZ, [_I, _I]),
     "nm_link_votes_dev_u8": (_I, [_I, _P, _P, _I, _F, _P, _P, _P]),
     "nm_link_votes_host_u8": (_I, [_I, _P, _P, _I, _F, _P]),
@@ -2632,6 +2642,215 @@ def frame_weights_set_grid_cap(cap=0):
     """Tuning and tests: the most workgroups either pass of frame_weights_batch launches (nm_frame_weights_set_grid_cap); 0
     restores the default. Results do not depend on it. Returns the previous setting."""
     return lib().nm_frame_weights_set_grid_cap(int(cap))
+
+
+FRAME_QUALITY_MAX_BATCH, FRAME_QUALITY_MAX_GRID = 64, 8
+KEYFRAME_STATUS, KEYFRAME_FEW, KEYFRAME_BAD, KEYFRAME_BLURRED, KEYFRAME_KEY, KEYFRAME_JUMP = 1, 2, 4, 8, 16, 32
+KeyframePick = collections.namedtuple("KeyframePick", "keys key_count key_status flags scores H_keys H_status")
+
+
+def _frame_quality_check(what, n, fw, fh, masks, lo, hi, grid, stats):
+    """masks as a list of n planes (or None) with their format, and (gx, gy); shapes and dtypes only, torch or numpy."""
+    if any(int(v) != v for v in (lo, hi)) or not (0 <= lo <= 255 and 0 <= hi <= 255):
+        raise NmError("%s: lo %r and hi %r must be integers in [0, 255]" % (what, lo, hi))
+    gx, gy = grid
+    if int(gx) != gx or int(gy) != gy or not (1 <= gx <= min(FRAME_QUALITY_MAX_GRID, fw) and 1 <= gy <= min(FRAME_QUALITY_MAX_GRID, fh)):
+        raise NmError("%s: grid %r outside [1, min(%d, fw)] x [1, min(%d, fh)]" % (what, grid, FRAME_QUALITY_MAX_GRID,
+                                                                                  FRAME_QUALITY_MAX_GRID))
+    mfmt = TEX_U8N
+    if masks is not None:
+        masks = list(masks) if isinstance(masks, (list, tuple)) else [masks] * n
+        if len(masks) != n or any(tuple(m.shape) != (fh, fw) for m in masks):
+            raise NmError("%s: masks must be %d (fh, fw) planes" % (what, n))
+        kinds = {("uint8" if _is_dtype(m, "uint8") else "float32" if _is_dtype(m, "float32") else None) for m in masks}
+        if len(kinds) != 1 or None in kinds:
+            raise NmError("%s: masks must all be uint8 or all float32" % what)
+        mfmt = TEX_U8N if "uint8" in kinds else TEX_F32
+    if stats is not None and (tuple(stats.shape) != (n, int(gy), int(gx), 8) or
+                              not (_is_dtype(stats, "int64") or _is_dtype(stats, "uint64"))):
+        raise NmError("%s: stats must be 64-bit integers of shape (n, gy, gx, 8)" % what)
+    return masks, mfmt, int(gx), int(gy)
+
+
+def frame_quality_batch(frames, masks=None, lo=0, hi=255, grid=(4, 4), stats=None):
+    """Exact quality statistics of n = len(frames) <= FRAME_QUALITY_MAX_BATCH BGRA frames (uint8 device (fh, fw, 4)) per cell
+    of a grid = (gx, gy) <= (8, 8) (nm_frame_quality_batch_dev): two launches on the current stream whatever n is, no host
+    read. masks: None, one (fh, fw) plane for all frames or a list of n, uint8 (valid: >= 128) or float32 (> 0.5). A pixel
+    is dark when max(B, G, R) < lo and bright when > hi (the defaults 0 and 255 turn both off); it is measured when it and
+    its four edge neighbours are eligible and neither. Returns stats, int64 (n, gy, gx, 8) (given or new; zeroed by the
+    call): measured pixels, sum of Y, of Y^2, of the squared Laplacian, of the squared gradient, dark, bright and eligible
+    pixels, with Y = (7 B + 72 G + 21 R + 50) // 100. stats goes straight into keyframe_pick."""
+    torch = _torch()
+    frames = list(frames)
+    n, fw, fh = _frames_check("frame_quality_batch", frames)
+    masks, mfmt, gx, gy = _frame_quality_check("frame_quality_batch", n, fw, fh, masks, lo, hi, grid, stats)
+    if masks is not None:
+        masks, _, mfmt, _ = _scalar_planes("frame_quality_batch", n, fw, fh, masks, masks)
+    device = _on_current_device(frames + (masks or []) + [stats], "frame_quality_batch")
+    if stats is None:
+        stats = torch.empty((n, gy, gx, 8), dtype=torch.int64, device=device)
+    _check(lib().nm_frame_quality_batch_dev(n, _pair_dev_table(frames, torch.uint8), fw, fh,
+                                            _pair_dev_table(masks, masks[0].dtype if masks else None), mfmt, int(lo), int(hi),
+                                            gx, gy, _dev(stats, torch.int64), _stream()), "nm_frame_quality_batch_dev")
+    return stats
+
+
+def frame_quality_host(frames, masks=None, lo=0, hi=255, grid=(4, 4), stats=None):
+    """frame_quality_batch on the host (nm_frame_quality_host, the same functions): numpy frames and masks; returns (or
+    fills) uint64 (n, gy, gx, 8), identical to the device's."""
+    import numpy as np
+    frames = _pair_host_arrays(frames, np.uint8, flat=False)
+    n, fw, fh = _frames_check("frame_quality_host", frames)
+    if masks is not None:
+        masks = [np.asarray(m) for m in (masks if isinstance(masks, (list, tuple)) else [masks] * n)]
+    masks, mfmt, gx, gy = _frame_quality_check("frame_quality_host", n, fw, fh, masks, lo, hi, grid, stats)
+    if masks is not None:
+        masks = [np.ascontiguousarray(m) for m in masks]
+    if stats is None:
+        stats = np.empty((n, gy, gx, 8), np.uint64)
+    if not stats.flags["C_CONTIGUOUS"]:
+        raise NmError("frame_quality_host: stats must be contiguous")
+    _check(lib().nm_frame_quality_host(n, _pair_host_table(frames), fw, fh, _pair_host_table(masks), mfmt, int(lo), int(hi),
+                                       gx, gy, _pair_host_ptr(stats)), "nm_frame_quality_host")
+    return stats
+
+
+def frame_quality_set_grid_cap(cap=0):
+    """Tuning and tests: the most workgroups frame_quality_batch's walk launches (nm_frame_quality_set_grid_cap); 0 restores
+    the default. Results do not depend on it. Returns the previous setting."""
+    return lib().nm_frame_quality_set_grid_cap(int(cap))
+
+
+def _keyframe_check(what, stats, chain, fw, fh, keep, frame_status, cell_min, min_pixels, max_bad, rel, w, d_min, d_max):
+    import math
+    if len(stats.shape) != 4 or stats.shape[3] != 8 or not (_is_dtype(stats, "int64") or _is_dtype(stats, "uint64")):
+        raise NmError("%s: stats must be 64-bit integers of shape (n, gy, gx, 8)" % what)
+    n, gy, gx = (int(v) for v in stats.shape[:3])
+    if not (1 <= n <= FRAME_QUALITY_MAX_BATCH and 1 <= gx <= FRAME_QUALITY_MAX_GRID and 1 <= gy <= FRAME_QUALITY_MAX_GRID):
+        raise NmError("%s: %d frames on a %d x %d grid (1 .. %d frames, 1 .. %d cells a side)"
+                      % (what, n, gx, gy, FRAME_QUALITY_MAX_BATCH, FRAME_QUALITY_MAX_GRID))
+    _size_check(what, "frame", fw, fh)
+    if any(int(v) != v for v in (keep, w, cell_min, min_pixels)) or not (1 <= keep <= FRAME_QUALITY_MAX_BATCH and 0 <= w <= 8):
+        raise NmError("%s: keep %r outside [1, %d] or w %r outside [0, 8]" % (what, keep, FRAME_QUALITY_MAX_BATCH, w))
+    if not (1 <= cell_min < 1 << 62 and 0 <= min_pixels < 1 << 62):
+        raise NmError("%s: cell_min %r must be >= 1 and min_pixels %r >= 0" % (what, cell_min, min_pixels))
+    if not (0.0 <= max_bad <= 1.0 and 0.0 <= rel <= 1.0):
+        raise NmError("%s: max_bad %r and rel %r must lie in [0, 1]" % (what, max_bad, rel))
+    if not (math.isfinite(d_min) and math.isfinite(d_max) and 0.0 <= d_min <= d_max and d_max <= 3.0e38):
+        raise NmError("%s: 0 <= d_min %r <= d_max %r, both finite" % (what, d_min, d_max))
+    if _numel(chain) != 9 * n or not _is_dtype(chain, "float32"):
+        raise NmError("%s: chain must hold n x 9 float32" % what)
+    if frame_status is not None and (_numel(frame_status) != n or not _is_dtype(frame_status, "int32")):
+        raise NmError("%s: frame_status must hold n int32" % what)
+    return n, gx, gy
+
+
+def _numel(a):
+    v = 1
+    for d in a.shape:
+        v *= int(d)
+    return v
+
+
+def keyframe_pick(stats, chain, fw, fh, keep, frame_status=None, cell_min=64, min_pixels=1024, max_bad=0.25, rel=0.6, w=2,
+                  d_min=32.0, d_max=128.0, carry=False):
+    """Which of the n frames behind stats (frame_quality_batch's, int64 device (n, gy, gx, 8)) to keep, on the device
+    (nm_keyframe_pick_dev): one launch of one workgroup on the current stream, no host read. chain: float32 device (n, 9)
+    or (n, 3, 3), row k mapping mosaic coordinates to frame-k pixels (mosaic_plan's or mosaic_adjust's chain);
+    frame_status: int32 device (n,) or None. A cell qualifies with >= cell_min measured pixels; a frame's score is the lower
+    median of its qualifying cells' mean squared Laplacian; it is usable with status 1, a finite non-zero chain row, a
+    qualifying cell, >= min_pixels measured pixels and (dark + bright) <= max_bad * eligible, and unless its score is below
+    rel times the best usable score within w frames (blurred). The walk keeps the sharpest usable frame each time the
+    view's corners have moved between d_min and d_max pixels since the last keyframe, at most keep of them; carry=True makes
+    frame 0 the first keyframe whatever its flags (the last keyframe of the previous chunk of a long video). Returns
+    KeyframePick(keys int32 (keep,) ascending with -1 beyond the count, key_count int32 (2,) = count and truncated,
+    key_status int32 (keep,), flags int32 (n,) of KEYFRAME_* bits, scores float64 (n, 4) = score, mean Y, bad fraction and
+    ref, H_keys float32 (keep - 1, 9) and H_status int32 (keep - 1,): keyframe i -> keyframe i + 1, for mosaic_plan and the
+    link stages on the frames that slots_gather compacts by keys)."""
+    torch = _torch()
+    n, gx, gy = _keyframe_check("keyframe_pick", stats, chain, fw, fh, keep, frame_status, cell_min, min_pixels, max_bad, rel, w,
+                                d_min, d_max)
+    device = _on_current_device([stats, chain, frame_status], "keyframe_pick")
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=device)
+    out = KeyframePick(i32(keep), i32(2), i32(keep), i32(n), torch.empty((n, 4), dtype=torch.float64, device=device),
+                       torch.empty((keep - 1, 9), dtype=torch.float32, device=device), i32(keep - 1))
+    _check(lib().nm_keyframe_pick_dev(n, _dev(stats, torch.int64), gx, gy, _dev(chain, torch.float32),
+                                      _opt(frame_status, torch.int32), fw, fh, int(keep), int(cell_min), int(min_pixels),
+                                      float(max_bad), float(rel), int(w), float(d_min), float(d_max), 1 if carry else 0,
+                                      *[_dev(t) for t in out], _stream()), "nm_keyframe_pick_dev")
+    return out
+
+
+def keyframe_pick_host(stats, chain, fw, fh, keep, frame_status=None, cell_min=64, min_pixels=1024, max_bad=0.25, rel=0.6, w=2,
+                       d_min=32.0, d_max=128.0, carry=False):
+    """keyframe_pick on the host (nm_keyframe_pick_host, the same functions): numpy in and out, identical results."""
+    import numpy as np
+    stats, chain = np.asarray(stats), np.ascontiguousarray(chain, dtype=np.float32)
+    if frame_status is not None:
+        frame_status = np.ascontiguousarray(frame_status, dtype=np.int32)
+    n, gx, gy = _keyframe_check("keyframe_pick_host", stats, chain, fw, fh, keep, frame_status, cell_min, min_pixels, max_bad, rel,
+                                w, d_min, d_max)
+    stats = np.ascontiguousarray(stats)
+    i32 = lambda *shape: np.empty(shape, np.int32)
+    out = KeyframePick(i32(keep), i32(2), i32(keep), i32(n), np.empty((n, 4), np.float64), np.empty((keep - 1, 9), np.float32),
+                       i32(keep - 1))
+    ptr = _pair_host_ptr
+    _check(lib().nm_keyframe_pick_host(n, ptr(stats), gx, gy, ptr(chain), ptr(frame_status), fw, fh, int(keep), int(cell_min),
+                                       int(min_pixels), float(max_bad), float(rel), int(w), float(d_min), float(d_max),
+                                       1 if carry else 0, *[ptr(a) for a in out]), "nm_keyframe_pick_host")
+    return out
+
+
+def _slots_gather_check(what, keys, src, dst, fill):
+    """(n, keep, bytes per slot) of a gather: src and dst are lists of equally shaped, equally typed arrays."""
+    src = list(src)
+    n, keep = len(src), _numel(keys)
+    if not (1 <= n <= FRAME_QUALITY_MAX_BATCH and 1 <= keep <= FRAME_QUALITY_MAX_BATCH) or not _is_dtype(keys, "int32"):
+        raise NmError("%s: %d sources and %d int32 keys (1 .. %d each)" % (what, n, keep, FRAME_QUALITY_MAX_BATCH))
+    if int(fill) != fill or not 0 <= fill <= 255:
+        raise NmError("%s: fill %r is a byte" % (what, fill))
+    shape, dtype = tuple(src[0].shape), src[0].dtype
+    if any(tuple(t.shape) != shape or t.dtype != dtype for t in src):
+        raise NmError("%s: sources of one shape and dtype expected" % what)
+    if dst is not None:
+        dst = list(dst)
+        if len(dst) != keep or any(tuple(t.shape) != shape or t.dtype != dtype for t in dst):
+            raise NmError("%s: dst must be %d arrays shaped and typed like the sources" % (what, keep))
+    size = _numel(src[0]) * (src[0].element_size() if hasattr(src[0], "element_size") else src[0].itemsize)
+    if not 1 <= size < 1 << 31:
+        raise NmError("%s: %d bytes per slot outside [1, 2^31)" % (what, size))
+    return src, dst, n, keep, size
+
+
+def slots_gather(keys, src, dst=None, fill=0):
+    """Compact any per-frame table by the device's choice (nm_slots_gather_dev), one launch on the current stream, no host
+    read: dst[i] = src[keys[i]] where keys[i] (int32 device (keep,), keyframe_pick's) lies in [0, len(src)), else every byte
+    of dst[i] is `fill`. src: a list of n <= 64 contiguous device tensors of one shape and dtype (BGRA frames, gray planes,
+    masks, weights, descriptor or coordinate tables, single count words); entries may repeat. dst: keep such tensors that
+    overlap nothing (default: the slices of one new (keep, ...) allocation). Returns dst as a list."""
+    torch = _torch()
+    src, dst, n, keep, size = _slots_gather_check("slots_gather", keys, src, dst, fill)
+    device = _on_current_device([keys] + src + (dst or []), "slots_gather")
+    if dst is None:
+        dst = list(torch.empty((keep,) + tuple(src[0].shape), dtype=src[0].dtype, device=device))
+    _check(lib().nm_slots_gather_dev(n, _pair_dev_table(src, src[0].dtype), keep, _pair_dev_table(dst, src[0].dtype),
+                                     _dev(keys, torch.int32), size, int(fill), _stream()), "nm_slots_gather_dev")
+    return dst
+
+
+def slots_gather_host(keys, src, dst=None, fill=0):
+    """slots_gather on the host (nm_slots_gather_host): numpy arrays; dst entries must be contiguous."""
+    import numpy as np
+    keys = np.ascontiguousarray(keys, dtype=np.int32)
+    src = [np.ascontiguousarray(a) for a in src]
+    src, dst, n, keep, size = _slots_gather_check("slots_gather_host", keys, src, dst, fill)
+    if dst is None:
+        dst = list(np.empty((keep,) + src[0].shape, src[0].dtype))
+    if any(not a.flags["C_CONTIGUOUS"] for a in dst):
+        raise NmError("slots_gather_host: dst entries must be contiguous")
+    _check(lib().nm_slots_gather_host(n, _pair_host_table(src), keep, _pair_host_table(dst), _pair_host_ptr(keys), size,
+                                      int(fill)), "nm_slots_gather_host")
+    return dst
 
 
 SIFT_MAX_BATCH = 64
