@@ -1640,6 +1640,134 @@ NM_API int nm_slots_gather_dev(int n, const void *const *src, int keep, void *co
 NM_API int nm_slots_gather_host(int n, const void *const *src, int keep, void *const *dst, const int *keys, long long bytes,
                                 int fill);
 
+/* ---- Gray pyramid and point tracking (no reference counterpart): a pyramidal Lucas-Kanade (KLT) tracker between the gray
+ * planes of frame pairs. Its output is the point tables of the stages behind the matcher (src_x / src_y / dst_x / dst_y,
+ * matches, a device count), made without descriptors: nm_ransac_batch_dev_f32, nm_ransac_refit_batch_dev_f32, the guided
+ * entries and nm_mosaic_adjust_dev_f32 take them as they stand. Two stages and their host twins, each on `stream` with no
+ * allocation, no synchronisation and no host read, no workgroup waits for another: capturable into one HIP graph from
+ * nm_frame_ingest_batch_f32 to the refit. Every table is a HOST table of device pointers; n in [1, NM_KLT_MAX_BATCH]; a
+ * pair's (a frame's) results depend on its own inputs alone, not on n, its slot, scheduling or what the outputs held.
+ *
+ * nm_gray_pyramid_batch_f32: gray[k] (fw x fh fp32, the ingest's planes) -> pyr[k], ONE block of `levels` planes per
+ * frame, so that a pair costs two pointers of the tracker's kernel arguments.
+ *   Sizes: w_0 = fw, w_(l+1) = (w_l + 1) >> 1, h alike. Level l starts nm_gray_pyramid_offset(fw, fh, l) floats into the
+ *     block: the running sum of w_j h_j over j < l, each term rounded up to a multiple of 4; the block holds
+ *     nm_gray_pyramid_floats(fw, fh, levels) floats (the offset of level `levels`; 0 for a refused shape). levels in
+ *     [1, NM_KLT_MAX_LEVELS]; refused when the coarsest level would be narrower or lower than 2.
+ *   Filter: level 0 is gray[k] bit for bit. With s(t) = the pixel at clamp(2X + t, 0, w_l - 1) of row y of level l,
+ *     h(X, y) = (((s(-2) + s(2)) + 4 (s(-1) + s(1))) + 6 s(0)) * 0.0625f, every operation one IEEE binary32 operation, no
+ *     contraction; pixel (X, Y) of level l + 1 is the same form over h(X, clamp(2Y + t, 0, h_l - 1)), t = -2 .. 2. Pixel
+ *     centres lie at integer coordinates at every level: a level-0 coordinate x is x / 2^l at level l.
+ *   Mask pyramid (mask and mask_pyr both given or both NULL; one for all frames): mask is the link stages' fw x fh fp32
+ *     plane, a pixel is seen where mask > 0.5. mask_pyr receives nm_gray_pyramid_floats BYTES, level l at the same offset
+ *     counted in bytes: level 0 is 1 (seen) or 0, a pixel of level l + 1 is 1 exactly when all 25 clamped taps of level l
+ *     are 1; the bytes between levels are 0.
+ *   Launches: max(levels - 1, 1) for all n frames (the first also stores level 0) plus one for the mask block.
+ *   Refused with hipErrorInvalidValue before any launch or device access: n outside [1, 64], fw or fh outside [1, 32767],
+ *     levels out of range or too many for the frame, a NULL gray or pyr or a NULL among their first n entries, exactly one
+ *     of mask / mask_pyr NULL. A block must not overlap any input or other block.
+ * nm_gray_pyramid_host_f32: the same with every pointer in host memory (csrc/nm_klt_math.hpp): identical bits.
+ *
+ * nm_klt_track_batch_dev_f32. Per pair k: pyrA[k], pyrB[k] pyramid blocks (pointers may repeat); src_x[k], src_y[k],
+ * d_nA[k], capA exactly as nm_ransac_batch_dev_f32 takes them (nA = clip(*d_nA[k], 0, capA), read on the device); mask_pyr
+ * (optional) the mask block; H_in (optional, n x 9 fp32 on the device) with status_in (optional, n ints, needs H_in)
+ * predicted maps A -> B. Host values: fw, fh, levels as for the pyramid; radius r in [1, NM_KLT_MAX_RADIUS]; iterations in
+ * [1, NM_KLT_MAX_ITERATIONS]; eps > 0, max_step > 0, min_eig >= 0, max_residual >= 0, fb_max >= 0, all finite.
+ *   DEFINITION. Whatever is summed is an integer, so host, device and any order of summation agree bit for bit; the fp64
+ *   steps are single IEEE operations in the written order, no contraction.
+ *     Level of a value: q = (int)rintf(v * 16.0f) when 0 <= v <= 255, else the pixel holds no level (a NaN holds none).
+ *     Window: a window has a centre c given in fp64; (cx, cy) = ((float)c.x, (float)c.y) is formed ONCE. The window is
+ *       outside when not (0 <= cx < w_l and 0 <= cy < h_l). i = floorf(cx), ax = (int)floorf((cx - i) * 256.0f + 0.5f) in
+ *       [0, 256], j and ay alike; the four integer weights (256 - ax)(256 - ay), ax (256 - ay), (256 - ax) ay, ax ay sum
+ *       to 65536 and are shared by every tap of the window (the verification's sampler, formed once per window).
+ *     Sample at tap (u, v), u and v whole numbers: from the pixels (i + u, j + v), (i + u + 1, j + v), (i + u, j + v + 1),
+ *       (i + u + 1, j + v + 1): (sum of weight x level + 32768) >> 16. A sample is valid when its four pixels lie inside
+ *       the plane, hold a level and, with a mask block, have byte 1 at that level.
+ *     Row i of pair k is tried when i < nA, src_x >= 0 and both coordinates are finite, else it is NM_KLT_ABSENT. State in
+ *       fp64: p = (src_x, src_y), displacement d.
+ *     Start: with H_in given, status_in NULL or status_in[k] == 1 and the nine values of H_k finite:
+ *       d = (double)project(H_k, p) - p with project and project_den of csrc/nm_warp_math.hpp on the fp32 coordinates; a
+ *       denominator that is not finite and > 0, or a projection that is not finite, loses the row (NM_KLT_START).
+ *       Otherwise d = 0.
+ *     Descent: d is multiplied by 2^-(levels-1), then for l = levels - 1 .. 0, with p_l = p 2^-l:
+ *       Template on plane l of A, window centre p_l: T(u, v) for |u|, |v| <= r, gx = T(u+1, v) - T(u-1, v),
+ *         gy = T(u, v+1) - T(u, v-1) (integers, no factor 1/2; the window has radius r + 1 and every sample of it
+ *         but the four corners, which enter no difference, must be valid); Gxx = sum gx^2, Gxy = sum gx gy,
+ *         Gyy = sum gy^2 over the (2r+1)^2 taps (< 2^34, held in 64 bits).
+ *       Texture gate, fp64: det = Gxx Gyy - Gxy Gxy; lam = ((Gxx + Gyy) - sqrt((Gxx - Gyy)^2 + 4 (Gxy Gxy))) / 2. The
+ *         window is flat when det is not finite and > 0, or lam / (1024 (2r+1)^2) < min_eig (gray^2 per tap; 1024 = 32^2).
+ *       Iteration: on plane l of B, window centre p_l + d: e = sample - T per tap, bx = sum e gx, by = sum e gy (64 bits);
+ *         sx = 2 (Gyy bx - Gxy by) / det, sy = 2 (Gxx by - Gxy bx) / det; a step with a non-finite component or
+ *         max(|sx|, |sy|) > max_step is refused; else d = d - s, and the level ends when max(|sx|, |sy|) < eps or after
+ *         `iterations` steps.
+ *       Failures: an invalid template sample or an outside template window, an invalid sample or outside window on B
+ *         (NM_KLT_BORDER), a flat window (NM_KLT_FLAT), a refused step (NM_KLT_STEP). At l > 0 the level is skipped: d
+ *         returns to its value on entry to the level. At l = 0 the row is lost with that code.
+ *       Between levels d is doubled.
+ *     Residual: one more evaluation on plane 0 of B at the final d against level 0's template: an invalid sample is
+ *       NM_KLT_BORDER; residual = (double)(sum |e|) / (16 (2r+1)^2) in gray values; with max_residual > 0 a residual above
+ *       it loses the row (NM_KLT_RESIDUAL).
+ *     Result: dst = ((float)(p.x + d.x), (float)(p.y + d.y)).
+ *     Forward-backward check (fb_max > 0): the same procedure, residual test included, from B to A with
+ *       p' = (double)dst and start displacement -d, ending at d'. The row is lost (NM_KLT_FB) when that track is lost or when
+ *       max(|(double)(float)(p'.x + d'.x) - src_x|, the same in y) > fb_max; that maximum, as fp32, is the fb_error.
+ *   Outputs (device): dst_x[k], dst_y[k]: capA floats each, ALL written, -1 for a lost or absent row; matches[k]: capA
+ *     ints, i for a tracked row i, else -1; count: n unsigned 64-bit words, the tracked rows per pair; optional tables
+ *     reason[k] (capA bytes, the NM_KLT_* code, 0 for a tracked row), residual[k] (capA floats, -1 where no residual was
+ *     formed) and fb_error[k] (capA floats, -1 where the backward track gave none).
+ *   Launches: the shared zeroing kernel on count (not a memset node: CHANGELOG.md, median composite), then one launch per
+ *     32 pair slots: ONE for n <= 32, two above (eleven tables of 64 pointers do not fit the 4 KB of kernel arguments).
+ *   Refused with hipErrorInvalidValue before any launch or device access: n outside [1, 64], capA outside [1, 2^22), the
+ *     pyramid's refusals for fw, fh, levels, radius or iterations out of range, a value that is not finite, eps <= 0,
+ *     max_step <= 0, a negative min_eig, max_residual or fb_max, status_in without H_in, a NULL count, a NULL required
+ *     table or a NULL among the first n entries of a table that is given.
+ * nm_klt_track_host_f32: the same with every pointer in host memory, from the same functions: identical outputs.
+ * nm_klt_sums_host (tests): the integer sums of one evaluation at `level`: template window centre (px, py) 2^-level on
+ *   pyrA, other window centre that + (dx, dy) on pyrB; sums[6] = Gxx, Gxy, Gyy, bx, by, sum |e|; *flags bit 0: the
+ *   template is outside or holds an invalid sample, bit 1: the same of the other window (sums of a flagged window are
+ *   not defined).
+ * nm_klt_set_grid_cap (tuning and tests, process-wide): the pyramid, mask and tracker launches use min(units, cap)
+ *   workgroups; cap >= 1 fixes the cap, any other value restores the default (8 per compute unit). Results are identical
+ *   for every cap. Returns the previous setting (0: the default).
+ * nm_klt_set_lanes (tuning and tests, process-wide): the lanes of a wave that share a point in the tracker's kernel: 8, 16
+ *   or 32 fixes them, any other value restores the default (16). Results are identical for every setting (the sums are
+ *   integers). Returns the previous setting (0: the default).                                                           */
+#define NM_KLT_MAX_BATCH 64
+#define NM_KLT_MAX_LEVELS 6
+#define NM_KLT_MAX_RADIUS 7
+#define NM_KLT_MAX_ITERATIONS 16
+#define NM_KLT_OK 0
+#define NM_KLT_ABSENT 1
+#define NM_KLT_START 2
+#define NM_KLT_BORDER 3
+#define NM_KLT_FLAT 4
+#define NM_KLT_STEP 5
+#define NM_KLT_RESIDUAL 6
+#define NM_KLT_FB 7
+NM_API size_t nm_gray_pyramid_floats(int fw, int fh, int levels);
+NM_API size_t nm_gray_pyramid_offset(int fw, int fh, int level);
+NM_API int nm_gray_pyramid_batch_f32(int n, const float *const *gray, int fw, int fh, int levels, float *const *pyr,
+                                     const float *mask, unsigned char *mask_pyr, void *stream);
+NM_API int nm_gray_pyramid_host_f32(int n, const float *const *gray, int fw, int fh, int levels, float *const *pyr,
+                                    const float *mask, unsigned char *mask_pyr);
+NM_API int nm_klt_track_batch_dev_f32(int n, const float *const *pyrA, const float *const *pyrB, int fw, int fh, int levels,
+                                      const unsigned char *mask_pyr, const float *const *src_x, const float *const *src_y,
+                                      const int *const *d_nA, int capA, const float *H_in, const int *status_in, int radius,
+                                      int iterations, float eps, float max_step, float min_eig, float max_residual,
+                                      float fb_max, float *const *dst_x, float *const *dst_y, int *const *matches,
+                                      unsigned long long *count, unsigned char *const *reason, float *const *residual,
+                                      float *const *fb_error, void *stream);
+NM_API int nm_klt_track_host_f32(int n, const float *const *pyrA, const float *const *pyrB, int fw, int fh, int levels,
+                                 const unsigned char *mask_pyr, const float *const *src_x, const float *const *src_y,
+                                 const int *const *nA, int capA, const float *H_in, const int *status_in, int radius,
+                                 int iterations, float eps, float max_step, float min_eig, float max_residual, float fb_max,
+                                 float *const *dst_x, float *const *dst_y, int *const *matches, unsigned long long *count,
+                                 unsigned char *const *reason, float *const *residual, float *const *fb_error);
+NM_API int nm_klt_sums_host(const float *pyrA, const float *pyrB, const unsigned char *mask_pyr, int fw, int fh, int levels,
+                            int level, int radius, double px, double py, double dx, double dy, long long *sums, int *flags);
+NM_API int nm_klt_set_grid_cap(int cap);
+NM_API int nm_klt_set_lanes(int lanes);
+
 /* ---- Link proposal: which frame pairs of a sequence to link at all (no reference counterpart). Two steps, both on
  * `stream` with no allocation, no synchronisation and no host read -- capturable into a HIP graph.
  * nm_link_votes_dev_u8: the u8 matcher's ratio test for ALL ordered pairs of n in [1, NM_LINK_PROPOSE_MAX_FRAMES] frames,

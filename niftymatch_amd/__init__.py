@@ -177,6 +177,17 @@ _SIGNATURES = {
                                    _F, _I, _P, _P, _P, _P, _P, _P, _P]),
     "nm_slots_gather_dev": (_I, [_I, _P, _I, _P, _P, C.c_longlong, _I, _P]),
     "nm_slots_gather_host": (_I, [_I, _P, _I, _P, _P, C.c_longlong, _I]),
+    "nm_gray_pyramid_floats": (_SZ, [_I, _I, _I]),
+    "nm_gray_pyramid_offset": (_SZ, [_I, _I, _I]),
+    "nm_gray_pyramid_batch_f32": (_I, [_I, _P, _I, _I, _I, _P, _P, _P, _P]),
+    "nm_gray_pyramid_host_f32": (_I, [_I, _P, _I, _I, _I, _P, _P, _P]),
+    "nm_klt_track_batch_dev_f32": (_I, [_I, _P, _P, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P, _I, _I, _F, _F, _F, _F, _F, _P, _P, _P,
+                                        _P, _P, _P, _P, _P]),
+    "nm_klt_track_host_f32": (_I, [_I, _P, _P, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P, _I, _I, _F, _F, _F, _F, _F, _P, _P, _P, _P,
+                                   _P, _P, _P]),
+    "nm_klt_sums_host": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, C.c_double, C.c_double, C.c_double, C.c_double, _P, _P]),
+    "nm_klt_set_grid_cap": (_I, [_I]),
+    "nm_klt_set_lanes": (_I, [_I]),
     "nm_link_votes_workspace_bytes": (_SZ, [_I, _I]),
     "nm_link_votes_dev_u8": (_I, [_I, _P, _P, _I, _F, _P, _P, _P]),
     "nm_link_votes_host_u8": (_I, [_I, _P, _P, _I, _F, _P]),
@@ -2851,6 +2862,210 @@ def slots_gather_host(keys, src, dst=None, fill=0):
     _check(lib().nm_slots_gather_host(n, _pair_host_table(src), keep, _pair_host_table(dst), _pair_host_ptr(keys), size,
                                       int(fill)), "nm_slots_gather_host")
     return dst
+
+
+# ---- gray pyramid and pyramidal KLT point tracking (include/nm_abi.h, "Gray pyramid and point tracking") ----
+KLT_MAX_BATCH, KLT_MAX_LEVELS, KLT_MAX_RADIUS, KLT_MAX_ITERATIONS = _PAIR_MAX_BATCH, 6, 7, 16
+KLT_OK, KLT_ABSENT, KLT_START, KLT_BORDER, KLT_FLAT, KLT_STEP, KLT_RESIDUAL, KLT_FB = range(8)
+KltTrack = collections.namedtuple("KltTrack", "dst_xs dst_ys matches count reason residual fb_error")
+
+
+def gray_pyramid_floats(fw, fh, levels):
+    """Floats of one frame's pyramid block (nm_gray_pyramid_floats); 0 for a shape the pyramid refuses."""
+    return int(lib().nm_gray_pyramid_floats(int(fw), int(fh), int(levels)))
+
+
+def gray_pyramid_offset(fw, fh, level):
+    """Floats (bytes of the mask block) from a block's start to its level `level` (nm_gray_pyramid_offset)."""
+    return int(lib().nm_gray_pyramid_offset(int(fw), int(fh), int(level)))
+
+
+def gray_pyramid_level(block, fw, fh, level):
+    """Level `level` of a pyramid or mask block as an (h_l, w_l) view; torch and numpy alike."""
+    w, h = fw, fh
+    for _ in range(level):
+        w, h = (w + 1) >> 1, (h + 1) >> 1
+    off = gray_pyramid_offset(fw, fh, level)
+    return block.reshape(-1)[off:off + w * h].reshape(h, w)
+
+
+def _pyramid_check(what, grays, levels, mask):
+    n = len(grays)
+    if not 0 < n <= KLT_MAX_BATCH:
+        raise NmError("%s: %d frames (1 .. %d)" % (what, n, KLT_MAX_BATCH))
+    fw, fh = _planes_check(what, list(grays), mask)
+    _size_check(what, "frame", fw, fh)
+    if any(not _is_dtype(g, "float32") for g in list(grays) + ([mask] if mask is not None else [])):
+        raise NmError("%s: float32 planes expected" % what)
+    if int(levels) != levels or not 1 <= levels <= KLT_MAX_LEVELS or gray_pyramid_floats(fw, fh, levels) == 0:
+        raise NmError("%s: levels %r outside [1, %d] or too many for a %d x %d frame" % (what, levels, KLT_MAX_LEVELS, fw, fh))
+    return n, fw, fh, gray_pyramid_floats(fw, fh, levels)
+
+
+def gray_pyramid_batch(grays, levels=4, mask=None, pyrs=None, mask_pyr=None):
+    """Gray pyramids of n = len(grays) <= KLT_MAX_BATCH float32 device planes of one (fh, fw) shape
+    (nm_gray_pyramid_batch_f32): max(levels - 1, 1) launches on the current stream whatever n is, no host read. A frame's
+    pyramid is one float32 tensor of gray_pyramid_floats(fw, fh, levels) values, level l at gray_pyramid_offset(fw, fh, l):
+    level 0 is the plane itself, level l + 1 the (1 4 6 4 1) / 16 binomial filter of level l at its even pixels. mask: the
+    link stages' float32 (fh, fw) plane (seen where > 0.5); its pyramid of bytes (1: every pixel below is seen) costs one
+    more launch and serves every frame. Returns (pyrs, mask_pyr or None); both may be given to be filled."""
+    torch = _torch()
+    grays = list(grays)
+    n, fw, fh, floats = _pyramid_check("gray_pyramid_batch", grays, levels, mask)
+    device = _on_current_device(grays + [mask, mask_pyr] + list(pyrs or []), "gray_pyramid_batch")
+    if pyrs is None:
+        pyrs = [torch.empty(floats, dtype=torch.float32, device=device) for _ in range(n)]
+    if len(pyrs) != n or any(p.numel() < floats for p in pyrs):
+        raise NmError("gray_pyramid_batch: %d blocks of at least %d floats expected" % (n, floats))
+    if mask is not None and mask_pyr is None:
+        mask_pyr = torch.empty(floats, dtype=torch.uint8, device=device)
+    if (mask is None) != (mask_pyr is None) or (mask_pyr is not None and mask_pyr.numel() < floats):
+        raise NmError("gray_pyramid_batch: mask_pyr needs a mask and %d bytes" % floats)
+    _check(lib().nm_gray_pyramid_batch_f32(n, _pair_dev_table(grays, torch.float32), fw, fh, int(levels),
+                                           _pair_dev_table(list(pyrs), torch.float32), _opt(mask, torch.float32),
+                                           _opt(mask_pyr, torch.uint8), _stream()), "nm_gray_pyramid_batch_f32")
+    return list(pyrs), mask_pyr
+
+
+def gray_pyramid_host(grays, levels=4, mask=None):
+    """gray_pyramid_batch on the host (nm_gray_pyramid_host_f32, the same functions): numpy planes in, (list of float32
+    blocks, uint8 mask block or None) out, identical bits."""
+    import numpy as np
+    grays = _pair_host_arrays(grays, np.float32, flat=False)
+    mask = None if mask is None else np.ascontiguousarray(mask, dtype=np.float32)
+    n, fw, fh, floats = _pyramid_check("gray_pyramid_host", grays, levels, mask)
+    pyrs = [np.zeros(floats, np.float32) for _ in range(n)]
+    mask_pyr = None if mask is None else np.zeros(floats, np.uint8)
+    _check(lib().nm_gray_pyramid_host_f32(n, _pair_host_table(grays), fw, fh, int(levels), _pair_host_table(pyrs),
+                                          _pair_host_ptr(mask), _pair_host_ptr(mask_pyr)), "nm_gray_pyramid_host_f32")
+    return pyrs, mask_pyr
+
+
+def _klt_check(what, n, fw, fh, levels, floats_of, H, status, radius, iterations, eps, max_step, min_eig, max_residual, fb_max):
+    """The tracker's host values; floats_of: the sizes of the pyramid blocks and, last, of the mask block or None."""
+    _size_check(what, "frame", fw, fh)
+    if int(levels) != levels or not 1 <= levels <= KLT_MAX_LEVELS or gray_pyramid_floats(fw, fh, levels) == 0:
+        raise NmError("%s: levels %r outside [1, %d] or too many for a %d x %d frame" % (what, levels, KLT_MAX_LEVELS, fw, fh))
+    if any(v is not None and v < gray_pyramid_floats(fw, fh, levels) for v in floats_of):
+        raise NmError("%s: a pyramid or mask block is smaller than %d" % (what, gray_pyramid_floats(fw, fh, levels)))
+    if int(radius) != radius or not 1 <= radius <= KLT_MAX_RADIUS or int(iterations) != iterations or \
+            not 1 <= iterations <= KLT_MAX_ITERATIONS:
+        raise NmError("%s: radius %r outside [1, %d] or iterations %r outside [1, %d]"
+                      % (what, radius, KLT_MAX_RADIUS, iterations, KLT_MAX_ITERATIONS))
+    if not all(math.isfinite(v) for v in (eps, max_step, min_eig, max_residual, fb_max)) or eps <= 0 or max_step <= 0 or \
+            min_eig < 0 or max_residual < 0 or fb_max < 0:
+        raise NmError("%s: eps and max_step must be > 0, min_eig, max_residual and fb_max >= 0, all finite" % what)
+    if H is None and status is not None:
+        raise NmError("%s: status needs H" % what)
+    if H is not None:
+        _pair_model_shape(n, _numel(H), None if status is None else _numel(status))
+
+
+def klt_track_batch_dev(pyrAs, pyrBs, fw, fh, src_xs, src_ys, d_nAs, levels=4, radius=7, iterations=10, eps=2.0 ** -6,
+                        max_step=16.0, min_eig=0.0, max_residual=0.0, fb_max=0.0, mask_pyr=None, H=None, status=None,
+                        capA=None, want_reason=False, want_residual=False, want_fb_error=False, out=None):
+    """Pyramidal Lucas-Kanade tracking of the points (src_xs[k], src_ys[k]) of n = len(pyrAs) <= KLT_MAX_BATCH frame pairs
+    from pyramid block pyrAs[k] into pyrBs[k] (gray_pyramid_batch; nm_klt_track_batch_dev_f32): the zeroing launch and one
+    launch per 32 pairs on the current stream, no host read. d_nAs are int32 DEVICE tensors; rows at and beyond
+    min(*d_nA, capA), rows with src_x < 0 and rows that are lost get -1. H (n, 9) float32 with status (n,) int32: predicted
+    maps A -> B as the start. min_eig: the smaller eigenvalue of the window's gradient matrix per tap, gray^2;
+    max_residual: mean absolute difference in gray values, 0 turns it off; fb_max: forward-backward distance in pixels, 0
+    turns the check off. Returns KltTrack(dst_xs, dst_ys, matches, count, reason, residual, fb_error): lists of n tensors of
+    capA float32 / float32 / int32 that go into ransac_batch_dev as they stand, count int64 (n,), and the optional per-row
+    uint8 KLT_* codes, residuals and forward-backward errors (None when not asked for). out: a KltTrack from an earlier
+    call of the same shape to be filled again."""
+    torch = _torch()
+    n = _pair_count(pyrAs, pyrBs, src_xs, src_ys, d_nAs)
+    _klt_check("klt_track_batch_dev", n, fw, fh, levels, [p.numel() for p in list(pyrAs) + list(pyrBs)] +
+               [None if mask_pyr is None else mask_pyr.numel()], H, status, radius, iterations, eps, max_step, min_eig,
+               max_residual, fb_max)
+    capA = _pair_cap(capA, list(src_xs) + list(src_ys))
+    device = _pair_device(list(pyrAs) + list(pyrBs) + list(src_xs) + list(src_ys) + list(d_nAs) + [mask_pyr, H, status], d_nAs)
+    if out is None:
+        new = lambda dt: [torch.empty(capA, dtype=dt, device=device) for _ in range(n)]
+        out = KltTrack(new(torch.float32), new(torch.float32), new(torch.int32), torch.empty(n, dtype=torch.int64, device=device),
+                       new(torch.uint8) if want_reason else None, new(torch.float32) if want_residual else None,
+                       new(torch.float32) if want_fb_error else None)
+    _pair_cap(capA, [t for ts in out[:3] + out[4:] if ts is not None for t in ts])
+    if len(out.dst_xs) != n or out.count.numel() != n:
+        raise NmError("klt_track_batch_dev: out is of another shape")
+    f, i32, tab = torch.float32, torch.int32, _pair_dev_table
+    _check(lib().nm_klt_track_batch_dev_f32(n, tab(list(pyrAs), f), tab(list(pyrBs), f), fw, fh, int(levels),
+                                            _opt(mask_pyr, torch.uint8), tab(list(src_xs), f), tab(list(src_ys), f),
+                                            tab(list(d_nAs), i32), capA, _opt(H, f), _opt(status, i32), int(radius),
+                                            int(iterations), eps, max_step, min_eig, max_residual, fb_max, tab(out.dst_xs, f),
+                                            tab(out.dst_ys, f), tab(out.matches, i32), _dev(out.count, torch.int64),
+                                            tab(out.reason, torch.uint8), tab(out.residual, f), tab(out.fb_error, f),
+                                            _stream()), "nm_klt_track_batch_dev_f32")
+    return out
+
+
+def klt_track_host(pyrAs, pyrBs, fw, fh, src_xs, src_ys, nAs, levels=4, radius=7, iterations=10, eps=2.0 ** -6, max_step=16.0,
+                   min_eig=0.0, max_residual=0.0, fb_max=0.0, mask_pyr=None, H=None, status=None, capA=None):
+    """klt_track_batch_dev on the host (nm_klt_track_host_f32, the same functions): numpy in and out, identical results;
+    nAs are host ints. Returns a KltTrack of (n, capA) arrays with count uint64 and every optional output."""
+    import numpy as np
+    n = _pair_count(pyrAs, pyrBs, src_xs, src_ys, nAs)
+    pyrAs, pyrBs, src_xs, src_ys = (_pair_host_arrays(vs, np.float32) for vs in (pyrAs, pyrBs, src_xs, src_ys))
+    mask_pyr = None if mask_pyr is None else np.ascontiguousarray(mask_pyr, dtype=np.uint8).reshape(-1)
+    if H is not None:
+        H = np.ascontiguousarray(H, dtype=np.float32).reshape(-1)
+        status = None if status is None else np.ascontiguousarray(status, dtype=np.int32).reshape(-1)
+    _klt_check("klt_track_host", n, fw, fh, levels, [p.size for p in pyrAs + pyrBs] + [None if mask_pyr is None else mask_pyr.size],
+               H, status, radius, iterations, eps, max_step, min_eig, max_residual, fb_max)
+    capA = _pair_cap(capA, src_xs + src_ys)
+    nA = _pair_host_sizes(nAs)
+    dst_x, dst_y, residual, fb = (np.zeros((n, capA), np.float32) for _ in range(4))
+    matches, reason, count = np.zeros((n, capA), np.int32), np.zeros((n, capA), np.uint8), np.zeros(n, np.uint64)
+    arr, ptr = _pair_host_table, _pair_host_ptr
+    _check(lib().nm_klt_track_host_f32(n, arr(pyrAs), arr(pyrBs), fw, fh, int(levels), ptr(mask_pyr), arr(src_xs), arr(src_ys),
+                                       arr(nA), capA, ptr(H), ptr(status), int(radius), int(iterations), eps, max_step, min_eig,
+                                       max_residual, fb_max, arr(list(dst_x)), arr(list(dst_y)), arr(list(matches)), ptr(count),
+                                       arr(list(reason)), arr(list(residual)), arr(list(fb))), "nm_klt_track_host_f32")
+    return KltTrack(dst_x, dst_y, matches, count, reason, residual, fb)
+
+
+def klt_sums_host(pyrA, pyrB, fw, fh, levels, level, radius, px, py, dx, dy, mask_pyr=None):
+    """The integer sums of one evaluation of the tracker (nm_klt_sums_host, for tests): (Gxx, Gxy, Gyy, bx, by, sum |e|) as
+    Python ints and the flags (1: template invalid, 2: the other window invalid)."""
+    import numpy as np
+    pyrA, pyrB = (np.ascontiguousarray(p, dtype=np.float32).reshape(-1) for p in (pyrA, pyrB))
+    mask_pyr = None if mask_pyr is None else np.ascontiguousarray(mask_pyr, dtype=np.uint8).reshape(-1)
+    sums, flags = np.zeros(6, np.int64), np.zeros(1, np.int32)
+    _check(lib().nm_klt_sums_host(_pair_host_ptr(pyrA), _pair_host_ptr(pyrB), _pair_host_ptr(mask_pyr), fw, fh, int(levels),
+                                  int(level), int(radius), float(px), float(py), float(dx), float(dy), _pair_host_ptr(sums),
+                                  _pair_host_ptr(flags)), "nm_klt_sums_host")
+    return tuple(int(v) for v in sums), int(flags[0])
+
+
+def klt_set_grid_cap(cap=0):
+    """Tuning and tests: the most workgroups a pyramid or tracker launch uses (nm_klt_set_grid_cap); 0 restores the default.
+    Results do not depend on it. Returns the previous setting."""
+    return lib().nm_klt_set_grid_cap(int(cap))
+
+
+def klt_set_lanes(lanes=0):
+    """Tuning and tests: the lanes of a wave that share a point in the tracker's kernel (nm_klt_set_lanes): 8, 16 or 32; 0
+    restores the default (16). Results do not depend on it. Returns the previous setting."""
+    return lib().nm_klt_set_lanes(int(lanes))
+
+
+def klt_grid_points(fw, fh, step, mask=None):
+    """A regular lattice as a point table, for frames without keypoints: the points (step // 2 + i step, step // 2 + j step)
+    inside the frame, row by row, as two float32 numpy arrays (x, y). mask: an (fh, fw) array; points where it is <= 0.5
+    are left out. Hand them to the device with torch.from_numpy(...).cuda()."""
+    import numpy as np
+    if int(step) != step or step < 1:
+        raise NmError("klt_grid_points: step %r must be a whole number >= 1" % (step,))
+    _size_check("klt_grid_points", "frame", fw, fh)
+    ys, xs = np.meshgrid(np.arange(step // 2, fh, step), np.arange(step // 2, fw, step), indexing="ij")
+    xs, ys = xs.reshape(-1), ys.reshape(-1)
+    if mask is not None:
+        if tuple(mask.shape) != (fh, fw):
+            raise NmError("klt_grid_points: mask must be (fh, fw)")
+        keep = np.asarray(mask)[ys, xs] > 0.5
+        xs, ys = xs[keep], ys[keep]
+    return xs.astype(np.float32), ys.astype(np.float32)
 
 
 SIFT_MAX_BATCH = 64
