@@ -16,20 +16,15 @@ Prints one JSON line. --trace runs a few calls of each instead (for a kernel tra
 """
 import argparse
 import ctypes as C
-import json
 import math
-import os
-import sys
 
 import numpy as np
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import torch  # noqa: E402
+import karms
+import torch
 
-import kexposure as KE  # noqa: E402
-import kmosaic_batch as KB  # noqa: E402
-import niftymatch_amd as nm  # noqa: E402
+import kmosaic_batch as KB
+import niftymatch_amd as nm
 
 FW, FH, N = KB.FW, KB.FH, 64
 HBM_PEAK_GBPS = 8000.0
@@ -38,9 +33,7 @@ HBM_PEAK_GBPS = 8000.0
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--radii", type=int, nargs="+", default=[4, 16, 32])
-    ap.add_argument("--rounds", type=int, default=12)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--trace", action="store_true")
+    karms.timing_args(ap, rounds=12, warmup=2, trace=True)
     a = ap.parse_args()
     assert torch.cuda.is_available(), "kbands.py measures on a GPU"
     assert a.rounds >= 10 or a.trace, "at least 10 rounds"
@@ -90,7 +83,8 @@ def main():
 
     runs = {"feather_blend": feather, "warp_tiles": warp}
     runs.update({"bands_R%d" % R: (lambda R=R: bands(R)) for R in a.radii})
-    t = KE.timed(runs, rounds, warmup, stream)
+    sp = karms.spread(karms.time_eager(runs, stream, rounds, warmup))
+    t = {k: {"median_us": sp["median_us"][k], "min_us": sp["min_max_us"][k][0], "max_us": sp["min_max_us"][k][1]} for k in runs}
     torch.cuda.synchronize()
     K = int((cwts["bands"] > 0).sum().item())
     # mosaic_plan clips every rectangle to the canvas, so every tile pixel is a canvas pixel: valid tile pixels per covered pixel
@@ -105,7 +99,7 @@ def main():
         us = t["bands_R%d" % R]["median_us"]
         out["bands_R%d" % R] = {"model_GBps": model["bands"] / us * 1e-3, "hbm_fraction": model["bands"] / us * 1e-3 / HBM_PEAK_GBPS,
                                 "warp_plus_bands_over_feather": (us + t["warp_tiles"]["median_us"]) / t["feather_blend"]["median_us"]}
-    print(json.dumps(out), flush=True)
+    karms.emit(out)
 
 
 if __name__ == "__main__":

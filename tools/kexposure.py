@@ -14,19 +14,15 @@ of each instead (for a kernel trace, with the program after `--`).
 """
 import argparse
 import ctypes as C
-import json
 import math
-import os
-import sys
 
 import numpy as np
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import torch  # noqa: E402
+import karms
+import torch
 
-import kmosaic_batch as KB  # noqa: E402
-import niftymatch_amd as nm  # noqa: E402
+import kmosaic_batch as KB
+import niftymatch_amd as nm
 
 FW, FH, N = KB.FW, KB.FH, 64
 
@@ -43,28 +39,16 @@ def link_maps(L):
 
 
 def timed(runs, rounds, warmup, stream):
-    ev = lambda: torch.cuda.Event(enable_timing=True)
-    times = {k: [] for k in runs}
-    with torch.cuda.stream(stream):
-        for r in range(warmup + rounds):
-            for name, fn in runs.items():
-                e0, e1 = ev(), ev()
-                e0.record(stream)
-                fn()
-                e1.record(stream)
-                e1.synchronize()
-                if r >= warmup:
-                    times[name].append(e0.elapsed_time(e1) * 1e3)
-    return {k: {"median_us": float(np.median(v)), "min_us": float(np.min(v)), "max_us": float(np.max(v))} for k, v in times.items()}
+    """This tool's record of the eager method: median, min and max per arm."""
+    sp = karms.spread(karms.time_eager(runs, stream, rounds, warmup))
+    return {k: {"median_us": sp["median_us"][k], "min_us": sp["min_max_us"][k][0], "max_us": sp["min_max_us"][k][1]} for k in runs}
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--links", type=int, nargs="+", default=[64, 256])
     ap.add_argument("--strides", type=int, nargs="+", default=[1, 2, 4])
-    ap.add_argument("--rounds", type=int, default=12)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--trace", action="store_true")
+    karms.timing_args(ap, rounds=12, warmup=2, trace=True)
     a = ap.parse_args()
     assert torch.cuda.is_available(), "kexposure.py measures on a GPU"
     assert a.rounds >= 10 or a.trace, "at least 10 rounds"
@@ -111,7 +95,7 @@ def main():
             lattice = L * (FW // s) * (FH // s)
             out["stride_%d" % s] = {"lattice_pixels": lattice, "counted_pixels": counted[s], "model_bytes": 20 * counted[s],
                                     "model_GBps": 20 * counted[s] / t["measure_stride_%d" % s]["median_us"] * 1e-3}
-        print(json.dumps(out), flush=True)
+        karms.emit(out)
 
     # the blend pair on the kmosaic_batch sequence
     n = N
@@ -142,8 +126,8 @@ def main():
     t = timed({"blend": plain, "blend_gain": gained}, rounds, warmup, stream)
     torch.cuda.synchronize()
     assert torch.equal(cwts["plain"].view(torch.int32), cwts["gained"].view(torch.int32))
-    print(json.dumps({"tool": "kexposure", "blend_frames": n, "canvas": [cw, ch], "rounds": rounds, "times": t,
-                      "gained_over_plain": t["blend_gain"]["median_us"] / t["blend"]["median_us"]}), flush=True)
+    karms.emit({"tool": "kexposure", "blend_frames": n, "canvas": [cw, ch], "rounds": rounds, "times": t,
+                "gained_over_plain": t["blend_gain"]["median_us"] / t["blend"]["median_us"]})
 
 
 if __name__ == "__main__":

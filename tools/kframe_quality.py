@@ -20,18 +20,14 @@ arm, untimed (for `rocprofv3 --kernel-trace --stats`, in a run of its own; the k
 keyframe_pick_kernel, slots_gather_kernel and the shared zero kernel).
 """
 import argparse
-import json
-import os
-import sys
 
 import numpy as np
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import torch  # noqa: E402
+import karms
+import torch
 
-import niftymatch_amd as nm  # noqa: E402
-from kframe_weights import FH, FW, make_frames  # noqa: E402
+import niftymatch_amd as nm
+from kframe_weights import FH, FW, make_frames
 
 PARAMS = dict(lo=30, hi=240)
 PICK = dict(keep=16, d_min=40.0, d_max=120.0)
@@ -41,11 +37,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=64)
     ap.add_argument("--grids", type=int, nargs="+", default=[1, 4, 8])
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--seconds", type=float, default=1.0, help="work per arm, over all rounds")
-    ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--copy-tbps", type=float, default=4.86, help="what tools/hbm_probe.py reports as the d2d copy rate")
-    ap.add_argument("--trace", action="store_true")
+    karms.timing_args(ap, rounds=5, warmup=2, seconds=1.0, trace=True)
     a = ap.parse_args()
     assert torch.cuda.is_available(), "kframe_quality.py measures on a GPU"
     assert 1 <= a.frames <= nm.FRAME_QUALITY_MAX_BATCH and all(1 <= g <= nm.FRAME_QUALITY_MAX_GRID for g in a.grids)
@@ -89,48 +82,21 @@ def main():
                 for fn in arms.values():
                     fn()
             torch.cuda.synchronize()
-            print(json.dumps({"tool": "kframe_quality", "frames": n, "trace_calls": 3}), flush=True)
+            karms.emit({"tool": "kframe_quality", "frames": n, "trace_calls": 3})
             return
-        for fn in arms.values():
-            fn()
-    torch.cuda.synchronize()
-    graphs, keep = {}, {}
-    for name, fn in arms.items():
-        graphs[name] = torch.cuda.CUDAGraph()
-        with torch.cuda.stream(stream):
-            with torch.cuda.graph(graphs[name], stream=stream):
-                keep[name] = fn()
-    ev = lambda: torch.cuda.Event(enable_timing=True)
-
-    def timed(graph, reps):
-        e0, e1 = ev(), ev()
-        e0.record(stream)
-        for _ in range(reps):
-            graph.replay()
-        e1.record(stream)
-        e1.synchronize()
-        return e0.elapsed_time(e1) * 1e3 / reps
-
-    with torch.cuda.stream(stream):
-        for _ in range(a.warmup):
-            for gr in graphs.values():
-                gr.replay()
-        reps = {name: max(1, int(round(a.seconds / a.rounds / (timed(gr, 1) * 1e-6)))) for name, gr in graphs.items()}
-        times = {name: [] for name in graphs}
-        for _ in range(a.rounds):
-            for name, gr in graphs.items():
-                times[name].append(timed(gr, reps[name]))
-    med = {k: float(np.median(t)) for k, t in times.items()}
+    graphs, kept = karms.capture(arms, stream)
+    reps, times = karms.time_replays(graphs, stream, a.rounds, a.seconds, a.warmup)
+    sp = karms.spread(times)
+    med = sp["median_us"]
     per_pixel = lambda k: 8 if k.endswith("_f32") else (5 if k.endswith("_u8") else 4)
     filled = int((h_pick.keys >= 0).sum())
     model = {k: (2 * n * 4 * P if k == "ingest" else 4 * P * (filled + PICK["keep"]) if k == "gather" else
                  n * 16 * 8 * 8 if k == "pick" else n * per_pixel(k) * P) for k in graphs}
     bw = {k: model[k] / (med[k] * 1e-6) / 1e12 for k in graphs}
-    print(json.dumps({"tool": "kframe_quality", "frames": n, "frame": [FW, FH], "params": PARAMS, "pick": PICK,
-                      "keys": h_pick.keys.tolist(), "rounds": a.rounds, "reps_per_round": reps, "median_us": med,
-                      "min_max_us": {k: [float(min(t)), float(max(t))] for k, t in times.items()}, "model_bytes": model,
-                      "model_TBps": bw, "fraction_of_copy_rate": {k: b / a.copy_tbps for k, b in bw.items()},
-                      "copy_TBps": a.copy_tbps}), flush=True)
+    karms.emit({"tool": "kframe_quality", "frames": n, "frame": [FW, FH], "params": PARAMS, "pick": PICK,
+                "keys": h_pick.keys.tolist(), "rounds": a.rounds, "reps_per_round": reps, **sp, "model_bytes": model,
+                "model_TBps": bw, "fraction_of_copy_rate": {k: b / a.copy_tbps for k, b in bw.items()},
+                "copy_TBps": a.copy_tbps})
 
 
 if __name__ == "__main__":

@@ -19,16 +19,13 @@ times come from a kernel trace only: --trace runs 3 eager calls of each arm, unt
 the kernels are frame_weights_row_kernel, frame_weights_col_kernel and frame_weights_zero_kernel).
 """
 import argparse
-import json
-import os
-import sys
 
 import numpy as np
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import torch  # noqa: E402
+import karms
+import torch
 
-import niftymatch_amd as nm  # noqa: E402
+import niftymatch_amd as nm
 
 FW, FH = 1920, 1080
 PARAMS = dict(lo=30, hi=240, margin=2, min_count=4, border=True)
@@ -54,11 +51,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=64)
     ap.add_argument("--radii", type=int, nargs="+", default=[8, 32, 64])
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--seconds", type=float, default=1.0, help="work per arm, over all rounds")
-    ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--copy-tbps", type=float, default=4.86, help="what tools/hbm_probe.py reports as the d2d copy rate")
-    ap.add_argument("--trace", action="store_true")
+    karms.timing_args(ap, rounds=5, warmup=2, seconds=1.0, trace=True)
     a = ap.parse_args()
     assert torch.cuda.is_available(), "kframe_weights.py measures on a GPU"
     assert 1 <= a.frames <= nm.FRAME_WEIGHTS_MAX_BATCH and all(3 <= R <= nm.FRAME_WEIGHTS_MAX_RADIUS for R in a.radii)
@@ -86,48 +80,20 @@ def main():
                 for fn in arms.values():
                     fn()
             torch.cuda.synchronize()
-            print(json.dumps({"tool": "kframe_weights", "frames": n, "trace_calls": 3}), flush=True)
+            karms.emit({"tool": "kframe_weights", "frames": n, "trace_calls": 3})
             return
-        for fn in arms.values():
-            fn()
-    torch.cuda.synchronize()
-    graphs, keep = {}, {}
-    for name, fn in arms.items():
-        graphs[name] = torch.cuda.CUDAGraph()
-        with torch.cuda.stream(stream):
-            with torch.cuda.graph(graphs[name], stream=stream):
-                keep[name] = fn()
-    ev = lambda: torch.cuda.Event(enable_timing=True)
-
-    def timed(graph, reps):
-        e0, e1 = ev(), ev()
-        e0.record(stream)
-        for _ in range(reps):
-            graph.replay()
-        e1.record(stream)
-        e1.synchronize()
-        return e0.elapsed_time(e1) * 1e3 / reps
-
-    with torch.cuda.stream(stream):
-        for _ in range(a.warmup):
-            for gr in graphs.values():
-                gr.replay()
-        reps = {name: max(1, int(round(a.seconds / a.rounds / (timed(gr, 1) * 1e-6)))) for name, gr in graphs.items()}
-        times = {name: [] for name in graphs}
-        for _ in range(a.rounds):
-            for name, gr in graphs.items():
-                times[name].append(timed(gr, reps[name]))
-    med = {k: float(np.median(t)) for k, t in times.items()}
+    graphs, kept = karms.capture(arms, stream)
+    reps, times = karms.time_replays(graphs, stream, a.rounds, a.seconds, a.warmup)
+    sp = karms.spread(times)
+    med = sp["median_us"]
     pitch = (FW + 63) // 64 * 64
     row_bytes = n * (4 * P + pitch * FH)
     col_bytes = {"all": n * (pitch * FH + P * (1 + 4 + 2)), "mw": n * (pitch * FH + P * (1 + 4))}
     model = {k: (2 * n * 4 * P if k == "ingest" else row_bytes + col_bytes[k.split("_")[0]]) for k in graphs}
     bw = {k: model[k] / (med[k] * 1e-6) / 1e12 for k in graphs}
-    print(json.dumps({"tool": "kframe_weights", "frames": n, "frame": [FW, FH], "params": PARAMS, "rounds": a.rounds,
-                      "reps_per_round": reps, "median_us": med,
-                      "min_max_us": {k: [float(min(t)), float(max(t))] for k, t in times.items()},
-                      "row_pass_bytes": row_bytes, "col_pass_bytes": col_bytes, "model_bytes": model, "model_TBps": bw,
-                      "fraction_of_copy_rate": {k: b / a.copy_tbps for k, b in bw.items()}, "copy_TBps": a.copy_tbps}), flush=True)
+    karms.emit({"tool": "kframe_weights", "frames": n, "frame": [FW, FH], "params": PARAMS, "rounds": a.rounds,
+                "reps_per_round": reps, **sp, "row_pass_bytes": row_bytes, "col_pass_bytes": col_bytes, "model_bytes": model,
+                "model_TBps": bw, "fraction_of_copy_rate": {k: b / a.copy_tbps for k, b in bw.items()}, "copy_TBps": a.copy_tbps})
 
 
 if __name__ == "__main__":

@@ -10,16 +10,14 @@ The guided call's outputs are checked against its host twin before timing. Print
 their ratio. --trace runs only a few match + guided calls (for `rocprofv3 --kernel-trace --stats`: launches, kernel times).
 """
 import argparse
-import json
 import os
-import sys
 
 import numpy as np
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import torch  # noqa: E402
+import karms
+import torch
 
-import niftymatch_amd as nm  # noqa: E402
+import niftymatch_amd as nm
 
 TRUE_H = np.array([[0.995, 0.02, 9.0], [-0.015, 1.005, -6.0], [1.5e-5, -1e-5, 1.0]], np.float64)
 
@@ -43,10 +41,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pairs", type=int, default=16)
     ap.add_argument("--rows", type=int, default=12000)
-    ap.add_argument("--rounds", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--radius2", type=float, default=9.0)
-    ap.add_argument("--trace", action="store_true")
+    karms.timing_args(ap, rounds=20, warmup=3, trace=True)
     a = ap.parse_args()
     assert torch.cuda.is_available(), "kguided.py measures on a GPU"
     dev = torch.device("cuda:0")
@@ -81,7 +77,7 @@ def main():
                 match()
                 guided()
         torch.cuda.synchronize()
-        print(json.dumps({"tool": "kguided", "trace_calls": 5, "pairs": n, "rows": cap}))
+        karms.emit({"tool": "kguided", "trace_calls": 5, "pairs": n, "rows": cap})
         return
 
     with torch.cuda.stream(stream):
@@ -96,26 +92,12 @@ def main():
         assert np.array_equal(gbest[k].cpu().numpy().view(np.uint32), hbest[k].view(np.uint32)), "best distance, pair %d" % k
     assert np.array_equal(gcnt.cpu().numpy(), hcnt), "device and host twin differ (count)"
 
-    ev = lambda: torch.cuda.Event(enable_timing=True)
-    runs = {"match": match, "guided": guided}
-    times = {k: [] for k in runs}
-    with torch.cuda.stream(stream):
-        for r in range(a.warmup + a.rounds):
-            for name, fn in runs.items():
-                e0, e1 = ev(), ev()
-                e0.record(stream)
-                fn()
-                e1.record(stream)
-                e1.synchronize()
-                if r >= a.warmup:
-                    times[name].append(e0.elapsed_time(e1) * 1e3)
-    med = {k: float(np.median(v)) for k, v in times.items()}
-    spread = {k: [float(np.min(v)), float(np.max(v))] for k, v in times.items()}
-    print(json.dumps({"tool": "kguided", "pairs": n, "rows": cap, "radius2": a.radius2, "rounds": a.rounds, "median_us": med,
-                      "min_max_us": spread, "guided_over_match": med["guided"] / med["match"],
-                      "library": os.path.basename(nm.LIB_PATH),
-                      "blind_matches": [int((b >= 0).sum()) for b in blind[:4]],
-                      "guided_matches": [int(x) for x in hcnt[:4]], "status": [int(x) for x in st.cpu().tolist()][:4]}))
+    sp = karms.spread(karms.time_eager({"match": match, "guided": guided}, stream, a.rounds, a.warmup))
+    med = sp["median_us"]
+    karms.emit({"tool": "kguided", "pairs": n, "rows": cap, "radius2": a.radius2, "rounds": a.rounds, **sp,
+                "guided_over_match": med["guided"] / med["match"], "library": os.path.basename(nm.LIB_PATH),
+                "blind_matches": [int((b >= 0).sum()) for b in blind[:4]],
+                "guided_matches": [int(x) for x in hcnt[:4]], "status": [int(x) for x in st.cpu().tolist()][:4]})
 
 
 if __name__ == "__main__":

@@ -13,28 +13,24 @@ the u8 host twin. Prints one JSON line: medians with min-max, their ratio, and w
 `rocprofv3 --kernel-trace --stats`: launches, kernel times).
 """
 import argparse
-import json
 import os
-import sys
 
 import numpy as np
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import torch  # noqa: E402
+import karms
+import torch
 
-import niftymatch_amd as nm  # noqa: E402
-from kguided import make_pair  # noqa: E402
+import niftymatch_amd as nm
+from kguided import make_pair
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pairs", type=int, default=16)
     ap.add_argument("--rows", type=int, default=12000)
-    ap.add_argument("--rounds", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--radius2", type=float, default=9.0)
     ap.add_argument("--trace", choices=("a", "b"))
+    karms.timing_args(ap, rounds=20, warmup=3)
     a = ap.parse_args()
     assert torch.cuda.is_available(), "kguided_u8.py measures on a GPU"
     dev = torch.device("cuda:0")
@@ -66,7 +62,7 @@ def main():
             for _ in range(5):
                 arms[a.trace]()
         torch.cuda.synchronize()
-        print(json.dumps({"tool": "kguided_u8", "trace_arm": a.trace, "trace_calls": 5, "pairs": n, "rows": cap}))
+        karms.emit({"tool": "kguided_u8", "trace_arm": a.trace, "trace_calls": 5, "pairs": n, "rows": cap})
         return
 
     with torch.cuda.stream(stream):
@@ -87,26 +83,14 @@ def main():
         assert np.array_equal(u32(best_b[k]), hbest[k].view(np.uint32)), "device and host twin differ (best, pair %d)" % k
     assert np.array_equal(cnt_b.cpu().numpy(), hcnt), "device and host twin differ (count)"
 
-    ev = lambda: torch.cuda.Event(enable_timing=True)
-    times = {k: [] for k in arms}
-    with torch.cuda.stream(stream):
-        for r in range(a.warmup + a.rounds):
-            for name, fn in arms.items():
-                e0, e1 = ev(), ev()
-                e0.record(stream)
-                fn()
-                e1.record(stream)
-                e1.synchronize()
-                if r >= a.warmup:
-                    times[name].append(e0.elapsed_time(e1) * 1e3)
-    med = {k: float(np.median(v)) for k, v in times.items()}
-    spread = {k: [float(np.min(v)), float(np.max(v))] for k, v in times.items()}
-    bar = med["a"] + spread["a"][1] - spread["a"][0]
-    print(json.dumps({"tool": "kguided_u8", "pairs": n, "rows": cap, "radius2": a.radius2, "rounds": a.rounds,
-                      "arms": {"a": "fp32 guided on float copies", "b": "u8 guided"}, "median_us": med, "min_max_us": spread,
-                      "u8_over_fp32": med["b"] / med["a"], "bar_us": bar, "inside_spread": med["b"] <= bar,
-                      "library": os.path.basename(nm.LIB_PATH), "blind_matches": [int((b >= 0).sum()) for b in blind[:4]],
-                      "guided_matches": [int(x) for x in hcnt[:4]], "status": [int(x) for x in st.cpu().tolist()][:4]}))
+    sp = karms.spread(karms.time_eager(arms, stream, a.rounds, a.warmup))
+    med, (lo, hi) = sp["median_us"], sp["min_max_us"]["a"]
+    bar = med["a"] + hi - lo
+    karms.emit({"tool": "kguided_u8", "pairs": n, "rows": cap, "radius2": a.radius2, "rounds": a.rounds,
+                "arms": {"a": "fp32 guided on float copies", "b": "u8 guided"}, **sp,
+                "u8_over_fp32": med["b"] / med["a"], "bar_us": bar, "inside_spread": med["b"] <= bar,
+                "library": os.path.basename(nm.LIB_PATH), "blind_matches": [int((b >= 0).sum()) for b in blind[:4]],
+                "guided_matches": [int(x) for x in hcnt[:4]], "status": [int(x) for x in st.cpu().tolist()][:4]})
 
 
 if __name__ == "__main__":

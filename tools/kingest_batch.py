@@ -17,16 +17,11 @@ this device, tools/hbm_probe.py). --trace runs 3 calls of each arm, untimed (for
 """
 import argparse
 import ctypes as C
-import json
-import os
-import sys
 
-import numpy as np
+import karms
+import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import torch  # noqa: E402
-
-import niftymatch_amd as nm  # noqa: E402
+import niftymatch_amd as nm
 
 FW, FH = 1920, 1080
 COPY_TBPS = 6.29
@@ -99,37 +94,15 @@ def measure(n, rounds, seconds, warmup, trace, dev, frames_all, u, v):
         for s in ("A", "B", "C_gray"):
             assert torch.equal(i32(grays[s][k]), i32(grays["C"][k])), (s, k)
         assert torch.equal(i32(grays["I"][k]), i32(grays["G"][k])), k
-    ev = lambda: torch.cuda.Event(enable_timing=True)
-
-    def timed(fn, reps):
-        e0, e1 = ev(), ev()
-        e0.record(stream)
-        for _ in range(reps):
-            fn()
-        e1.record(stream)
-        e1.synchronize()
-        return e0.elapsed_time(e1) * 1e3 / reps
-
-    with torch.cuda.stream(stream):
-        for _ in range(warmup):
-            for fn in arms.values():
-                fn()
-        reps = {}
-        for name, fn in arms.items():
-            one = timed(fn, 1)
-            reps[name] = max(1, int(round(seconds / rounds / (one * 1e-6))))
-        times = {k: [] for k in arms}
-        for _ in range(rounds):
-            for name, fn in arms.items():
-                times[name].append(timed(fn, reps[name]))
-    med = {k: float(np.median(t)) for k, t in times.items()}
+    reps, times = karms.time_replays(arms, stream, rounds, seconds, warmup)
+    sp = karms.spread(times)
+    med = sp["median_us"]
     bytes_map = 8 * P
     model = {"A": None, "B": None, "C": bytes_map + n * (4 * P + 4 * P + 4 * P), "C_gray": bytes_map + n * (4 * P + 4 * P),
              "I": n * (4 * P + 4 * P), "G": n * (4 * P + 4 * P)}
     model["A"] = model["B"] = model["C"]
     bw = {k: model[k] / (med[k] * 1e-6) / 1e12 for k in arms}
-    return {"tool": "kingest_batch", "frames": n, "frame": [FW, FH], "rounds": rounds, "reps_per_round": reps,
-            "median_us": med, "min_max_us": {k: [float(min(t)), float(max(t))] for k, t in times.items()},
+    return {"tool": "kingest_batch", "frames": n, "frame": [FW, FH], "rounds": rounds, "reps_per_round": reps, **sp,
             "launches_per_call": {"A": 13 * n, "B": 2 * n, "C": 1, "C_gray": 1, "I": 1, "G": n},
             "speedup_C_over_A": med["A"] / med["C"], "speedup_C_over_B": med["B"] / med["C"],
             "speedup_I_over_G": med["G"] / med["I"],
@@ -140,10 +113,7 @@ def measure(n, rounds, seconds, warmup, trace, dev, frames_all, u, v):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, nargs="+", default=[16, 64])
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--seconds", type=float, default=1.0, help="work per arm, over all rounds")
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--trace", action="store_true")
+    karms.timing_args(ap, rounds=5, warmup=2, seconds=1.0, trace=True)
     a = ap.parse_args()
     assert torch.cuda.is_available(), "kingest_batch.py measures on a GPU"
     assert all(1 <= n <= nm.INGEST_MAX_BATCH for n in a.frames)
@@ -157,7 +127,7 @@ def main():
     u, v = nm.undistort_map(xx.contiguous(), yy.contiguous(), cam, dist)
     torch.cuda.synchronize()
     for n in a.frames:
-        print(json.dumps(measure(n, a.rounds, a.seconds, a.warmup, a.trace, dev, frames, u, v)), flush=True)
+        karms.emit(measure(n, a.rounds, a.seconds, a.warmup, a.trace, dev, frames, u, v))
 
 
 if __name__ == "__main__":

@@ -19,16 +19,14 @@ warm-up; a round replays an arm enough times for --seconds / --rounds of work. P
 and appends it to --out (default profiles/kklt_mi355x.jsonl): the median and min / max per arm over the rounds.
 """
 import argparse
-import json
 import os
-import sys
 
 import numpy as np
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import torch  # noqa: E402
+import karms
+import torch
 
-import niftymatch_amd as nm  # noqa: E402
+import niftymatch_amd as nm
 
 FW, FH, LEVELS = 1920, 1080, 4
 
@@ -60,11 +58,7 @@ def main():
     ap.add_argument("--pairs", type=int, nargs="+", default=[16, 64])
     ap.add_argument("--points", type=int, nargs="+", default=[4096, 12288])
     ap.add_argument("--radii", type=int, nargs="+", default=[3, 7])
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--seconds", type=float, default=1.0, help="work per arm, over all rounds")
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                                                  "kklt_mi355x.jsonl"))
+    karms.timing_args(ap, rounds=5, warmup=2, seconds=1.0, out=os.path.join(karms.ROOT, "profiles", "kklt_mi355x.jsonl"))
     a = ap.parse_args()
     assert torch.cuda.is_available(), "kklt.py measures on a GPU"
     dev = torch.device("cuda:0")
@@ -122,42 +116,11 @@ def main():
                     assert np.array_equal(o.dst_xs[0].cpu().numpy().view(np.uint32), h.dst_xs[0].view(np.uint32)), name
                     assert int(o.count[0]) == int(h.count[0])
                     tracked[name] = float(o.count.sum()) / (n * points)
-            torch.cuda.synchronize()
-            graphs = {}
-            for name, fn in arms.items():
-                graphs[name] = torch.cuda.CUDAGraph()
-                with torch.cuda.stream(stream):
-                    with torch.cuda.graph(graphs[name], stream=stream):
-                        fn()
-            ev = lambda: torch.cuda.Event(enable_timing=True)
-
-            def timed(graph, reps):
-                e0, e1 = ev(), ev()
-                e0.record(stream)
-                for _ in range(reps):
-                    graph.replay()
-                e1.record(stream)
-                e1.synchronize()
-                return e0.elapsed_time(e1) * 1e3 / reps
-
-            with torch.cuda.stream(stream):
-                for _ in range(a.warmup):
-                    for gr in graphs.values():
-                        gr.replay()
-                reps = {name: max(1, int(round(a.seconds / a.rounds / (timed(gr, 1) * 1e-6)))) for name, gr in graphs.items()}
-                times = {name: [] for name in graphs}
-                for _ in range(a.rounds):
-                    for name, gr in graphs.items():
-                        times[name].append(timed(gr, reps[name]))
-            line = json.dumps({"tool": "kklt", "pairs": n, "frames": nf, "points": points, "frame": [FW, FH], "levels": LEVELS, "rounds": a.rounds,
-                               "reps_per_round": reps, "median_us": {k: float(np.median(t)) for k, t in times.items()},
-                               "min_max_us": {k: [float(min(t)), float(max(t))] for k, t in times.items()},
-                               "tracked_share": tracked})
-            print(line, flush=True)
-            os.makedirs(os.path.dirname(a.out), exist_ok=True)
-            with open(a.out, "a") as f:
-                f.write(line + "\n")
-            del graphs
+            graphs, kept = karms.capture(arms, stream)
+            reps, times = karms.time_replays(graphs, stream, a.rounds, a.seconds, a.warmup)
+            karms.emit({"tool": "kklt", "pairs": n, "frames": nf, "points": points, "frame": [FW, FH], "levels": LEVELS,
+                        "rounds": a.rounds, "reps_per_round": reps, **karms.spread(times), "tracked_share": tracked}, a.out)
+            del graphs, kept
 
 
 if __name__ == "__main__":

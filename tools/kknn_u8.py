@@ -15,16 +15,14 @@ a kernel trace in a run of its own; the arms are match_scan_u8_kernel<2, RatioOu
 """
 import argparse
 import json
-import os
-import sys
 
 import numpy as np
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import torch  # noqa: E402
+import karms
+import torch
 
-import niftymatch_amd as nm  # noqa: E402
-from niftymatch_amd import synth  # noqa: E402
+import niftymatch_amd as nm
+from niftymatch_amd import synth
 
 W, H, CAP = 1920, 1080, 16384
 KS = (1, 2, 4, 8)
@@ -33,11 +31,9 @@ KS = (1, 2, 4, 8)
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pairs", type=int, default=16)
-    ap.add_argument("--rounds", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--rows", type=int, default=0, help="use at most this many rows of every frame (0: all)")
-    ap.add_argument("--trace", action="store_true")
-    ap.add_argument("--out", default=None)
+    ap.add_argument("--out", default=None, help="a file of its own for the record, indented (written anew)")
+    karms.timing_args(ap, rounds=20, warmup=3, trace=True)
     a = ap.parse_args()
     assert torch.cuda.is_available(), "kknn_u8.py measures on a GPU"
     assert 1 <= a.pairs <= nm.MATCH_MAX_BATCH
@@ -81,7 +77,7 @@ def main():
                 for fn in arms.values():
                     fn()
         torch.cuda.synchronize()
-        print(json.dumps({"tool": "kknn_u8", "trace_calls": 5, "pairs": n}))
+        karms.emit({"tool": "kknn_u8", "trace_calls": 5, "pairs": n})
         return
 
     with torch.cuda.stream(stream):
@@ -102,25 +98,13 @@ def main():
         want = torch.where(d2[:, 1] > 0, want, res[p][:rows[2 * p]])
         assert torch.equal(want, res[p][:rows[2 * p]]), "k = 2 lists and the matcher differ (pair %d)" % p
 
-    ev = lambda: torch.cuda.Event(enable_timing=True)
-    times = {k: [] for k in arms}
-    with torch.cuda.stream(stream):
-        for rd in range(a.warmup + a.rounds):
-            for name, fn in arms.items():
-                e0, e1 = ev(), ev()
-                e0.record(stream)
-                fn()
-                e1.record(stream)
-                e1.synchronize()
-                if rd >= a.warmup:
-                    times[name].append(e0.elapsed_time(e1) * 1e3)
-    med = {k: float(np.median(v)) for k, v in times.items()}
-    out = {"tool": "kknn_u8", "pairs": n, "rounds": a.rounds, "rows": rows[:4], "median_us": med,
-           "min_max_us": {k: [float(np.min(v)), float(np.max(v))] for k, v in times.items()},
+    sp = karms.spread(karms.time_eager(arms, stream, a.rounds, a.warmup))
+    med = sp["median_us"]
+    out = {"tool": "kknn_u8", "pairs": n, "rounds": a.rounds, "rows": rows[:4], **sp,
            "us_per_pair": {k: v / n for k, v in med.items()},
            "over_matcher": {k: v / med["match"] for k, v in med.items() if k != "match"}}
-    print(json.dumps(out))
-    if a.out:
+    karms.emit(out)
+    if a.out:                                            # not emit's appended line: profiles/ keeps this record indented
         with open(a.out, "w") as f:
             f.write(json.dumps(out, indent=1) + "\n")
     for x in arenas:

@@ -19,17 +19,15 @@ cap: medians with min-max in microseconds and b / a. --trace runs a few calls of
 run of its own, without counters).
 """
 import argparse
-import json
-import os
-import sys
+import statistics
 
 import numpy as np
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import torch  # noqa: E402
+import karms
+import torch
 
-import niftymatch_amd as nm  # noqa: E402
-from niftymatch_amd import synth  # noqa: E402
+import niftymatch_amd as nm
+from niftymatch_amd import synth
 
 W, H, CAP = 1920, 1080, 16384
 GROUP = 64
@@ -63,11 +61,9 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=64)
     ap.add_argument("--caps", default="512,1024,2048")
-    ap.add_argument("--rounds", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--splits", default="0,1")
     ap.add_argument("--related", action="store_true")
-    ap.add_argument("--trace", action="store_true")
+    karms.timing_args(ap, rounds=20, warmup=3, trace=True)
     a = ap.parse_args()
     assert torch.cuda.is_available(), "klink_propose.py measures on a GPU"
     n = a.frames
@@ -105,7 +101,7 @@ def main():
                     arm_a()
                     arm_b()
             torch.cuda.synchronize()
-            print(json.dumps({"tool": "klink_propose", "trace_calls": 3, "frames": n, "cap": cap, "related": a.related}))
+            karms.emit({"tool": "klink_propose", "trace_calls": 3, "frames": n, "cap": cap, "related": a.related})
             continue
 
         with torch.cuda.stream(stream):
@@ -124,32 +120,16 @@ def main():
 
         arms = {"a": arm_a, "b": arm_b}
         arms.update({"b_z%d" % z: (lambda z=z: arm_b(z)) for z in splits if z != 0})
-        graphs = {}
-        for name, fn in list(arms.items()):                           # the same arms as replays of a captured graph
-            graphs[name] = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graphs[name], stream=stream):
-                fn()
-            arms[name + "_graph"] = graphs[name].replay
-        times = {k: [] for k in arms}
-        ev = lambda: torch.cuda.Event(enable_timing=True)
-        with torch.cuda.stream(stream):
-            for r in range(a.warmup + a.rounds):
-                for name, fn in arms.items():
-                    e0, e1 = ev(), ev()
-                    e0.record(stream)
-                    fn()
-                    e1.record(stream)
-                    e1.synchronize()
-                    if r >= a.warmup:
-                        times[name].append(e0.elapsed_time(e1) * 1e3)
-        med = {k: float(np.median(v)) for k, v in times.items()}
+        graphs, kept = karms.capture(arms, stream)                    # the same arms as replays of a captured graph,
+        arms.update({name + "_graph": g.replay for name, g in graphs.items()})    # timed by the eager method beside them
+        sp = karms.spread(karms.time_eager(arms, stream, a.rounds, a.warmup))
+        med = sp["median_us"]
         rows = [min(int(c.item()), cap) for c in counts]
         off = want[~np.eye(n, dtype=bool)]
-        print(json.dumps({"tool": "klink_propose", "frames": n, "cap": cap, "related": a.related, "rows_min_max": [min(rows), max(rows)],
-                          "pairs": len(pairs), "votes_min_median_max": [int(off.min()), float(np.median(off)), int(off.max())],
-                          "launches": {"a_matcher": 2 * len(groups), "a_calls": len(groups), "b": 2}, "rounds": a.rounds,
-                          "median_us": med, "min_max_us": {k: [float(np.min(v)), float(np.max(v))] for k, v in times.items()},
-                          "b_over_a": med["b"] / med["a"], "b_graph_over_a_graph": med["b_graph"] / med["a_graph"]}))
+        karms.emit({"tool": "klink_propose", "frames": n, "cap": cap, "related": a.related, "rows_min_max": [min(rows), max(rows)],
+                    "pairs": len(pairs), "votes_min_median_max": [int(off.min()), float(statistics.median(off.tolist())), int(off.max())],
+                    "launches": {"a_matcher": 2 * len(groups), "a_calls": len(groups), "b": 2}, "rounds": a.rounds, **sp,
+                    "b_over_a": med["b"] / med["a"], "b_graph_over_a_graph": med["b_graph"] / med["a_graph"]})
 
 
 if __name__ == "__main__":

@@ -13,16 +13,13 @@ all of B) so that the time can be set against tools/hbm_probe.py's bandwidth. --
 `rocprofv3 --kernel-trace --stats`: launches per call, kernel times; no counters).
 """
 import argparse
-import json
-import os
-import sys
 
 import numpy as np
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import torch  # noqa: E402
+import karms
+import torch
 
-import niftymatch_amd as nm  # noqa: E402
+import niftymatch_amd as nm
 
 FW, FH = 1920, 1080
 
@@ -30,10 +27,8 @@ FW, FH = 1920, 1080
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pairs", type=int, default=16)
-    ap.add_argument("--rounds", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--iterations", type=int, default=4)
-    ap.add_argument("--trace", action="store_true")
+    karms.timing_args(ap, rounds=20, warmup=3, trace=True)
     a = ap.parse_args()
     assert torch.cuda.is_available(), "klink_refine.py measures on a GPU"
     dev = torch.device("cuda:0")
@@ -65,7 +60,7 @@ def main():
                 for s in strides:
                     refine(s)
         torch.cuda.synchronize()
-        print(json.dumps({"tool": "klink_refine", "trace_calls": 5 * len(strides), "pairs": n, "iterations": its}))
+        karms.emit({"tool": "klink_refine", "trace_calls": 5 * len(strides), "pairs": n, "iterations": its})
         return
 
     checks = {}
@@ -87,26 +82,12 @@ def main():
     for s in strides:
         runs["refine_stride%d" % s] = (lambda s=s: refine(s))
         runs["verify_stride%d" % s] = (lambda s=s: verify(s))
-    ev = lambda: torch.cuda.Event(enable_timing=True)
-    times = {k: [] for k in runs}
-    with torch.cuda.stream(stream):
-        for r in range(a.warmup + a.rounds):
-            for name, fn in runs.items():
-                e0, e1 = ev(), ev()
-                e0.record(stream)
-                fn()
-                e1.record(stream)
-                e1.synchronize()
-                if r >= a.warmup:
-                    times[name].append(e0.elapsed_time(e1) * 1e3)
-    med = {k: float(np.median(v)) for k, v in times.items()}
-    spread = {k: [float(np.min(v)), float(np.max(v))] for k, v in times.items()}
+    sp = karms.spread(karms.time_eager(runs, stream, a.rounds, a.warmup))
     must = {"refine_stride%d" % s: n * 4 * (5 * (FW // s) * (FH // s) + FW * FH) for s in strides}
-    per_it = {k: med[k] / its for k in must}
-    print(json.dumps({"tool": "klink_refine", "pairs": n, "frame": [FW, FH], "rounds": a.rounds, "iterations": its,
-                      "median_us": med, "min_max_us": spread, "per_iteration_us": per_it,
-                      "bytes_per_iteration": must, "gb_per_s": {k: must[k] / per_it[k] / 1e3 for k in must},
-                      "checks": checks}))
+    per_it = {k: sp["median_us"][k] / its for k in must}
+    karms.emit({"tool": "klink_refine", "pairs": n, "frame": [FW, FH], "rounds": a.rounds, "iterations": its, **sp,
+                "per_iteration_us": per_it, "bytes_per_iteration": must,
+                "gb_per_s": {k: must[k] / per_it[k] / 1e3 for k in must}, "checks": checks})
 
 
 if __name__ == "__main__":

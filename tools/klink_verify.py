@@ -11,18 +11,15 @@ the host twin before timing. Prints one JSON line: medians with min-max, and per
 (for `rocprofv3 --kernel-trace --stats`: launches per call, kernel times; no counters).
 """
 import argparse
-import json
-import os
-import sys
 
 import numpy as np
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import torch  # noqa: E402
+import karms
+import torch
 
-import niftymatch_amd as nm  # noqa: E402
+import niftymatch_amd as nm
 
-from kransac_refit import noisy_pair  # noqa: E402
+from kransac_refit import noisy_pair
 
 FW, FH = 1920, 1080
 
@@ -30,9 +27,7 @@ FW, FH = 1920, 1080
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pairs", type=int, default=16)
-    ap.add_argument("--rounds", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--trace", action="store_true")
+    karms.timing_args(ap, rounds=20, warmup=3, trace=True)
     a = ap.parse_args()
     assert torch.cuda.is_available(), "klink_verify.py measures on a GPU"
     dev = torch.device("cuda:0")
@@ -56,7 +51,7 @@ def main():
                 for s in strides:
                     verify(s)
         torch.cuda.synchronize()
-        print(json.dumps({"tool": "klink_verify", "trace_calls": 5 * len(strides), "pairs": n}))
+        karms.emit({"tool": "klink_verify", "trace_calls": 5 * len(strides), "pairs": n})
         return
 
     stats = {}
@@ -83,24 +78,11 @@ def main():
                                                        threshold=thr, capA=cap)}
     for s in strides:
         runs["verify_stride%d" % s] = (lambda s=s: verify(s))
-    ev = lambda: torch.cuda.Event(enable_timing=True)
-    times = {k: [] for k in runs}
-    with torch.cuda.stream(stream):
-        for r in range(a.warmup + a.rounds):
-            for name, fn in runs.items():
-                e0, e1 = ev(), ev()
-                e0.record(stream)
-                fn()
-                e1.record(stream)
-                e1.synchronize()
-                if r >= a.warmup:
-                    times[name].append(e0.elapsed_time(e1) * 1e3)
-    med = {k: float(np.median(v)) for k, v in times.items()}
-    spread = {k: [float(np.min(v)), float(np.max(v))] for k, v in times.items()}
+    sp = karms.spread(karms.time_eager(runs, stream, a.rounds, a.warmup))
+    med = sp["median_us"]
     must = {"verify_stride%d" % s: n * 4 * ((FW // s) * (FH // s) + FW * FH) for s in strides}
-    print(json.dumps({"tool": "klink_verify", "pairs": n, "frame": [FW, FH], "rounds": a.rounds, "median_us": med,
-                      "min_max_us": spread, "bytes_to_move": must,
-                      "gb_per_s": {k: must[k] / med[k] / 1e3 for k in must}, "checks": stats}))
+    karms.emit({"tool": "klink_verify", "pairs": n, "frame": [FW, FH], "rounds": a.rounds, **sp, "bytes_to_move": must,
+                "gb_per_s": {k: must[k] / med[k] / 1e3 for k in must}, "checks": stats})
 
 
 if __name__ == "__main__":

@@ -17,17 +17,14 @@ Prints one JSON line: medians with min-max, b / a, arm (b)'s share of the i8 mat
 match_scan_u8_kernel<2, RatioOut>).
 """
 import argparse
-import json
-import os
-import sys
 
 import numpy as np
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import torch  # noqa: E402
+import karms
+import torch
 
-import niftymatch_amd as nm  # noqa: E402
-from niftymatch_amd import synth  # noqa: E402
+import niftymatch_amd as nm
+from niftymatch_amd import synth
 
 W, H, CAP = 1920, 1080, 16384
 I8_PEAK_OPS = 5.0e15                           # twice the ~2.5 PF dense bf16 peak: the same cycles per MFMA at twice the K
@@ -36,10 +33,8 @@ I8_PEAK_OPS = 5.0e15                           # twice the ~2.5 PF dense bf16 pe
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pairs", type=int, default=16)
-    ap.add_argument("--rounds", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--rows", type=int, default=0, help="use at most this many rows of every frame (0: all)")
-    ap.add_argument("--trace", action="store_true")
+    karms.timing_args(ap, rounds=20, warmup=3, trace=True)
     a = ap.parse_args()
     assert torch.cuda.is_available(), "kmatch_u8.py measures on a GPU"
     assert 1 <= a.pairs <= nm.MATCH_MAX_BATCH
@@ -86,7 +81,7 @@ def main():
                 arm_b()
                 finish()
         torch.cuda.synchronize()
-        print(json.dumps({"tool": "kmatch_u8", "trace_calls": 5, "pairs": n}))
+        karms.emit({"tool": "kmatch_u8", "trace_calls": 5, "pairs": n})
         return
 
     with torch.cuda.stream(stream):
@@ -110,29 +105,16 @@ def main():
             f[:c].copy_(d[:c])
             s[:c].copy_(u[:c])
 
-    ev = lambda: torch.cuda.Event(enable_timing=True)
     arms = {"a_f32_matcher_on_float_copies": arm_a, "b_u8_matcher": arm_b, "finish": finish, "copy_same_bytes": copy}
-    times = {k: [] for k in arms}
-    with torch.cuda.stream(stream):
-        for rd in range(a.warmup + a.rounds):
-            for name, fn in arms.items():
-                e0, e1 = ev(), ev()
-                e0.record(stream)
-                fn()
-                e1.record(stream)
-                e1.synchronize()
-                if rd >= a.warmup:
-                    times[name].append(e0.elapsed_time(e1) * 1e3)
-    med = {k: float(np.median(v)) for k, v in times.items()}
+    sp = karms.spread(karms.time_eager(arms, stream, a.rounds, a.warmup))
+    med = sp["median_us"]
     ops = sum(2.0 * 128 * rows[2 * k] * rows[2 * k + 1] for k in range(n))
     moved = sum(rows) * (512 + 640)
-    out = {"tool": "kmatch_u8", "pairs": n, "rounds": a.rounds, "rows": rows[:4], "matches_pair0": int((rb[0] >= 0).sum()),
-           "median_us": med, "min_max_us": {k: [float(np.min(v)), float(np.max(v))] for k, v in times.items()},
-           "b_over_a": med["b_u8_matcher"] / med["a_f32_matcher_on_float_copies"],
-           "b_us_per_pair": med["b_u8_matcher"] / n,
-           "b_share_of_i8_peak": ops / (med["b_u8_matcher"] * 1e-6) / I8_PEAK_OPS,
-           "finish_bytes_per_s": moved / (med["finish"] * 1e-6), "finish_over_copy": med["finish"] / med["copy_same_bytes"]}
-    print(json.dumps(out))
+    karms.emit({"tool": "kmatch_u8", "pairs": n, "rounds": a.rounds, "rows": rows[:4], "matches_pair0": int((rb[0] >= 0).sum()), **sp,
+                "b_over_a": med["b_u8_matcher"] / med["a_f32_matcher_on_float_copies"],
+                "b_us_per_pair": med["b_u8_matcher"] / n,
+                "b_share_of_i8_peak": ops / (med["b_u8_matcher"] * 1e-6) / I8_PEAK_OPS,
+                "finish_bytes_per_s": moved / (med["finish"] * 1e-6), "finish_over_copy": med["finish"] / med["copy_same_bytes"]})
     for x in arenas:
         x.close()
 

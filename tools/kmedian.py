@@ -15,20 +15,15 @@ Prints one JSON line. --trace runs a few calls of each instead (for a kernel tra
 """
 import argparse
 import ctypes as C
-import json
 import math
-import os
-import sys
 
 import numpy as np
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import torch  # noqa: E402
+import karms
+import torch
 
-import kexposure as KE  # noqa: E402
-import kmosaic_batch as KB  # noqa: E402
-import niftymatch_amd as nm  # noqa: E402
+import kmosaic_batch as KB
+import niftymatch_amd as nm
 
 FW, FH, N = KB.FW, KB.FH, 64
 HBM_PEAK_GBPS = 8000.0
@@ -36,10 +31,8 @@ HBM_PEAK_GBPS = 8000.0
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--rounds", type=int, default=12)
-    ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--tau", type=float, default=nm.MEDIAN_TAU)
-    ap.add_argument("--trace", action="store_true")
+    karms.timing_args(ap, rounds=12, warmup=2, trace=True)
     a = ap.parse_args()
     assert torch.cuda.is_available(), "kmedian.py measures on a GPU"
     assert a.rounds >= 10 or a.trace, "at least 10 rounds"
@@ -103,7 +96,8 @@ def main():
             "median_mean": lambda: median("mean", nm.MEDIAN_MEAN, False),
             "median_select_all_outputs": lambda: median("select", nm.MEDIAN_SELECT, True),
             "median_mean_all_outputs": lambda: median("mean", nm.MEDIAN_MEAN, True)}
-    t = KE.timed(runs, rounds, warmup, stream)
+    sp = karms.spread(karms.time_eager(runs, stream, rounds, warmup))
+    t = {k: {"median_us": sp["median_us"][k], "min_us": sp["min_max_us"][k][0], "max_us": sp["min_max_us"][k][1]} for k in runs}
     torch.cuda.synchronize()
     K = int((support > 0).sum().item())
     c = float(counts[:, 0].sum().item()) / max(K, 1)
@@ -118,7 +112,7 @@ def main():
         us = t[name]["median_us"]
         out[name] = {"model_GBps": nbytes / us * 1e-3, "hbm_fraction": nbytes / us * 1e-3 / HBM_PEAK_GBPS,
                      "over_feather": us / t["feather_blend"]["median_us"], "over_bands_R0": us / t["bands_R0"]["median_us"]}
-    print(json.dumps(out), flush=True)
+    karms.emit(out)
 
 
 if __name__ == "__main__":

@@ -10,15 +10,14 @@ bit before timing. Prints one JSON line: medians with min-max per call, launches
 --trace runs only a few calls (for `rocprofv3 --kernel-trace --stats`: kernel times per launch; no counters).
 """
 import argparse
-import json
 import os
 import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+import karms
+
+sys.path.insert(0, os.path.join(karms.ROOT, "tests"))
 import torch  # noqa: E402
 
 import niftymatch_amd as nm  # noqa: E402
@@ -45,10 +44,8 @@ def problem(L, rng):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--rounds", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--iterations", type=int, default=5)
-    ap.add_argument("--trace", action="store_true")
+    karms.timing_args(ap, rounds=20, warmup=3, trace=True)
     a = ap.parse_args()
     assert torch.cuda.is_available(), "kmosaic_adjust.py measures on a GPU"
     dev = torch.device("cuda:0")
@@ -77,20 +74,11 @@ def main():
         host = nm.mosaic_adjust_host(la, lb, *tab, chain, R.FW, R.FH, mask=mask, **kw)
         for d, h in zip(got, host):
             assert np.array_equal(d.cpu().numpy().view(np.uint8), h.view(np.uint8)), "device and host twin differ"
-        times = []
-        with torch.cuda.stream(stream):
-            for r in range(a.warmup + a.rounds):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(stream)
-                call()
-                e1.record(stream)
-                e1.synchronize()
-                if r >= a.warmup:
-                    times.append(e0.elapsed_time(e1) * 1e3)
-        out["L%d" % L] = {"median_us": float(np.median(times)), "min_max_us": [float(min(times)), float(max(times))],
+        sp = karms.spread(karms.time_eager({"call": call}, stream, a.rounds, a.warmup))
+        out["L%d" % L] = {"median_us": sp["median_us"]["call"], "min_max_us": sp["min_max_us"]["call"],
                           "launches": (a.iterations + 1) * (-(-L // 64) + 1), "end": int(host[3][7]), "steps": int(host[3][5]),
                           "cost": [float(host[3][0]), float(host[3][1])], "unknown_frames": int(host[3][4])}
-    print(json.dumps(out))
+    karms.emit(out)
 
 
 if __name__ == "__main__":

@@ -14,17 +14,14 @@ timing. The plan launch is timed on its own. Prints one JSON line per n. --trace
 """
 import argparse
 import ctypes as C
-import json
 import math
-import os
-import sys
 
 import numpy as np
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import torch  # noqa: E402
+import karms
+import torch
 
-import niftymatch_amd as nm  # noqa: E402
+import niftymatch_amd as nm
 
 FW, FH = 1920, 1080
 
@@ -95,18 +92,7 @@ def measure(n, rounds, warmup, trace, dev, frames_all, mask, wts):
     torch.cuda.synchronize()
     assert torch.equal(canv["per_frame"], canv["batched"])
     assert torch.equal(cwts["per_frame"].view(torch.int32), cwts["batched"].view(torch.int32))
-    ev = lambda: torch.cuda.Event(enable_timing=True)
-    times = {k: [] for k in runs}
-    with torch.cuda.stream(stream):
-        for r in range(warmup + rounds):
-            for name, fn in runs.items():
-                e0, e1 = ev(), ev()
-                e0.record(stream)
-                fn()
-                e1.record(stream)
-                e1.synchronize()
-                if r >= warmup:
-                    times[name].append(e0.elapsed_time(e1) * 1e3)
+    sp = karms.spread(karms.time_eager(runs, stream, rounds, warmup))
     # bytes: per-frame calls read 8 B and write 8 B (uchar4 + weight) per covered pixel per covering frame; the batched
     # call does so once per pixel covered by any frame. Texels: each frame's planes (uchar4 + 1 B mask + 4 B weight).
     cover = np.zeros((ch, cw), np.uint8)
@@ -115,9 +101,8 @@ def measure(n, rounds, warmup, trace, dev, frames_all, mask, wts):
         cover[ty:ty + nh, tx:tx + nw] += 1
     rect_px = int(cover.sum(dtype=np.int64))
     union_px = int((cover > 0).sum())
-    med = {k: float(np.median(v)) for k, v in times.items()}
-    return {"tool": "kmosaic_batch", "frames": n, "frame": [FW, FH], "canvas": [cw, ch], "rounds": rounds,
-            "median_us": med, "min_max_us": {k: [float(np.min(v)), float(np.max(v))] for k, v in times.items()},
+    med = sp["median_us"]
+    return {"tool": "kmosaic_batch", "frames": n, "frame": [FW, FH], "canvas": [cw, ch], "rounds": rounds, **sp,
             "speedup": med["per_frame"] / med["batched"], "launches_per_call": {"per_frame": n, "batched": 1, "plan": 1},
             "rect_pixels": rect_px, "union_pixels": union_px,
             "canvas_bytes_per_call": {"per_frame": 16 * rect_px, "batched": 16 * union_px},
@@ -127,9 +112,7 @@ def measure(n, rounds, warmup, trace, dev, frames_all, mask, wts):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, nargs="+", default=[16, 64])
-    ap.add_argument("--rounds", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--trace", action="store_true")
+    karms.timing_args(ap, rounds=20, warmup=3, trace=True)
     a = ap.parse_args()
     assert torch.cuda.is_available(), "kmosaic_batch.py measures on a GPU"
     assert all(1 <= n <= nm.MOSAIC_MAX_BATCH for n in a.frames)
@@ -139,7 +122,7 @@ def main():
     mask = torch.full((FH, FW), 255, dtype=torch.uint8, device=dev)
     wts = torch.from_numpy(feather()).to(dev)
     for n in a.frames:
-        print(json.dumps(measure(n, a.rounds, a.warmup, a.trace, dev, frames, mask, wts)), flush=True)
+        karms.emit(measure(n, a.rounds, a.warmup, a.trace, dev, frames, mask, wts))
 
 
 if __name__ == "__main__":

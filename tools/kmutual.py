@@ -18,17 +18,15 @@ launches, kernel times). --stats reads the two counters a scratch build writes
 NM_HIP_LIB=tools/_variants/libnm_hip_mstats.so): (claim, row) pairs scanned and 16-dimension chunks walked.
 """
 import argparse
-import json
 import os
-import sys
 
 import numpy as np
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import torch  # noqa: E402
+import karms
+import torch
 
-import niftymatch_amd as nm  # noqa: E402
-from niftymatch_amd import synth  # noqa: E402
+import niftymatch_amd as nm
+from niftymatch_amd import synth
 
 W, H, CAP = 1920, 1080, 16384
 
@@ -51,11 +49,9 @@ def make_frames(dev, n, related):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pairs", type=int, default=16)
-    ap.add_argument("--rounds", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--related", action="store_true")
-    ap.add_argument("--trace", action="store_true")
     ap.add_argument("--stats", action="store_true")
+    karms.timing_args(ap, rounds=20, warmup=3, trace=True)
     a = ap.parse_args()
     assert torch.cuda.is_available(), "kmutual.py measures on a GPU"
     assert 1 <= a.pairs <= nm.MATCH_MAX_BATCH
@@ -90,7 +86,7 @@ def main():
                 match()
                 mutual()
         torch.cuda.synchronize()
-        print(json.dumps({"tool": "kmutual", "trace_calls": 5, "pairs": n, "related": a.related}))
+        karms.emit({"tool": "kmutual", "trace_calls": 5, "pairs": n, "related": a.related})
         return
 
     with torch.cuda.stream(stream):
@@ -109,7 +105,7 @@ def main():
         st = uws.buf[256:272].cpu().numpy().view(np.uint64)
         out["stats"] = {"claim_row_pairs": int(st[0]), "chunks": int(st[1]),
                         "mean_chunks_per_pair": float(st[1]) / max(float(st[0]), 1.0)}
-        print(json.dumps(out))
+        karms.emit(out)
         return
     hres, hcnt, hfwd = nm.sift_match_mutual_host([dA[0].cpu().numpy()], [rows[0]], [dB[0].cpu().numpy()], [int(nB[0].item())],
                                                  [fwd[0].cpu().numpy()], capA=CAP, capB=CAP, want_distance=True)
@@ -117,25 +113,13 @@ def main():
     assert np.array_equal(mfwd[0].cpu().numpy().view(np.uint32), hfwd[0].view(np.uint32)), "forward distance, pair 0"
     assert kept[0] == int(hcnt[0]), "device and host twin differ (count)"
 
-    ev = lambda: torch.cuda.Event(enable_timing=True)
     arms = {"a_match_then_swapped_match": lambda: (match(), swapped()), "b_match_then_mutual": lambda: (match(), mutual()),
             "match_alone": match, "swapped_match_alone": swapped, "mutual_alone": mutual}
-    times = {k: [] for k in arms}
-    with torch.cuda.stream(stream):
-        for r in range(a.warmup + a.rounds):
-            for name, fn in arms.items():
-                e0, e1 = ev(), ev()
-                e0.record(stream)
-                fn()
-                e1.record(stream)
-                e1.synchronize()
-                if r >= a.warmup:
-                    times[name].append(e0.elapsed_time(e1) * 1e3)
-    med = {k: float(np.median(v)) for k, v in times.items()}
-    out.update({"rounds": a.rounds, "median_us": med, "min_max_us": {k: [float(np.min(v)), float(np.max(v))] for k, v in times.items()},
-                "b_over_a": med["b_match_then_mutual"] / med["a_match_then_swapped_match"],
+    sp = karms.spread(karms.time_eager(arms, stream, a.rounds, a.warmup))
+    med = sp["median_us"]
+    out.update({"rounds": a.rounds, **sp, "b_over_a": med["b_match_then_mutual"] / med["a_match_then_swapped_match"],
                 "mutual_over_swapped_match": med["mutual_alone"] / med["swapped_match_alone"]})
-    print(json.dumps(out))
+    karms.emit(out)
     for x in arenas:
         x.close()
 

@@ -19,27 +19,22 @@ the share of claims the filter removes. --trace runs only a few calls of each ar
 without counters).
 """
 import argparse
-import json
-import os
-import sys
 
 import numpy as np
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import torch  # noqa: E402
+import karms
+import torch
 
-import niftymatch_amd as nm  # noqa: E402
+import niftymatch_amd as nm
 
-from kmutual import CAP, H, W, make_frames  # noqa: E402
+from kmutual import CAP, H, W, make_frames
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pairs", type=int, default=16)
-    ap.add_argument("--rounds", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--related", action="store_true")
-    ap.add_argument("--trace", action="store_true")
+    karms.timing_args(ap, rounds=20, warmup=3, trace=True)
     a = ap.parse_args()
     assert torch.cuda.is_available(), "kmutual_u8.py measures on a GPU"
     assert 1 <= a.pairs <= nm.MATCH_MAX_BATCH
@@ -89,7 +84,7 @@ def main():
                 match_f32()
                 mutual_f32()
         torch.cuda.synchronize()
-        print(json.dumps({"tool": "kmutual_u8", "trace_calls": 5, "pairs": n, "related": a.related}))
+        karms.emit({"tool": "kmutual_u8", "trace_calls": 5, "pairs": n, "related": a.related})
         return
 
     with torch.cuda.stream(stream):
@@ -115,28 +110,17 @@ def main():
            "claims": claims[:4], "kept": kept[:4], "claim_share_of_rows": sum(claims) / max(sum(rows), 1),
            "removed_share_of_claims": 1.0 - sum(kept) / max(sum(claims), 1)}
 
-    ev = lambda: torch.cuda.Event(enable_timing=True)
     arms = {"a_match_u8_then_swapped_match_u8": lambda: (match(), swapped()), "b_match_u8_then_mutual_u8": lambda: (match(), mutual()),
             "c_match_f32_then_mutual_f32": lambda: (match_f32(), mutual_f32()), "match_u8_alone": match,
             "swapped_match_u8_alone": swapped, "mutual_u8_alone": mutual}
-    times = {k: [] for k in arms}
-    with torch.cuda.stream(stream):
-        for r in range(a.warmup + a.rounds):
-            for name, fn in arms.items():
-                e0, e1 = ev(), ev()
-                e0.record(stream)
-                fn()
-                e1.record(stream)
-                e1.synchronize()
-                if r >= a.warmup:
-                    times[name].append(e0.elapsed_time(e1) * 1e3)
-    med = {k: float(np.median(v)) for k, v in times.items()}
-    out.update({"rounds": a.rounds, "median_us": med, "min_max_us": {k: [float(np.min(v)), float(np.max(v))] for k, v in times.items()},
+    sp = karms.spread(karms.time_eager(arms, stream, a.rounds, a.warmup))
+    med = sp["median_us"]
+    out.update({"rounds": a.rounds, **sp,
                 "b_over_a": med["b_match_u8_then_mutual_u8"] / med["a_match_u8_then_swapped_match_u8"],
                 "b_over_c": med["b_match_u8_then_mutual_u8"] / med["c_match_f32_then_mutual_f32"],
                 "mutual_u8_over_swapped_match_u8": med["mutual_u8_alone"] / med["swapped_match_u8_alone"],
                 "mutual_u8_us_per_pair": med["mutual_u8_alone"] / n})
-    print(json.dumps(out))
+    karms.emit(out)
     for x in arenas:
         x.close()
 

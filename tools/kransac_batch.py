@@ -10,16 +10,13 @@ JSON line. --trace runs only a few batched calls (for `rocprofv3 --kernel-trace 
 """
 import argparse
 import ctypes as C
-import json
-import os
-import sys
 
 import numpy as np
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import torch  # noqa: E402
+import karms
+import torch
 
-import niftymatch_amd as nm  # noqa: E402
+import niftymatch_amd as nm
 
 TRUE_H = np.array([[1.02, 0.03, 12.0], [-0.02, 0.98, -7.0], [1e-5, -2e-5, 1.0]])
 
@@ -53,10 +50,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pairs", type=int, default=16)
     ap.add_argument("--iterations", type=int, default=4096)
-    ap.add_argument("--rounds", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--threshold", type=float, default=4.0)
-    ap.add_argument("--trace", action="store_true")
+    karms.timing_args(ap, rounds=20, warmup=3, trace=True)
     a = ap.parse_args()
     assert torch.cuda.is_available(), "kransac_batch.py measures on a GPU"
     dev = torch.device("cuda:0")
@@ -79,7 +74,7 @@ def main():
             for _ in range(5):
                 batched()
         torch.cuda.synchronize()
-        print(json.dumps({"tool": "kransac_batch", "trace_calls": 5, "pairs": n, "iterations": it}))
+        karms.emit({"tool": "kransac_batch", "trace_calls": 5, "pairs": n, "iterations": it})
         return
 
     # the per-pair side: aligned rows (align_points semantics) and the batched entry's sample lists, on the device
@@ -113,26 +108,13 @@ def main():
         assert torch.equal(out[4][k].view(torch.int32), Ha[k].view(torch.int32)) and torch.equal(out[5][k], inl[k])
         assert torch.equal(out[0][k].view(torch.int32), Hb[k].view(torch.int32))
 
-    ev = lambda: torch.cuda.Event(enable_timing=True)
-    times = {"per_pair": [], "batched": [], "batched_all": []}
     runs = {"per_pair": per_pair, "batched": batched, "batched_all": lambda: batched(True)}
-    with torch.cuda.stream(stream):
-        for r in range(a.warmup + a.rounds):
-            for name, fn in runs.items():
-                e0, e1 = ev(), ev()
-                e0.record(stream)
-                fn()
-                e1.record(stream)
-                e1.synchronize()
-                if r >= a.warmup:
-                    times[name].append(e0.elapsed_time(e1) * 1e3)
-    med = {k: float(np.median(v)) for k, v in times.items()}
-    spread = {k: [float(np.min(v)), float(np.max(v))] for k, v in times.items()}
-    print(json.dumps({"tool": "kransac_batch", "pairs": n, "iterations": it, "rows": cap,
-                      "matched_rows": [int((p[4] >= 0).sum()) for p in pairs][:2], "rounds": a.rounds,
-                      "median_us": med, "min_max_us": spread, "speedup": med["per_pair"] / med["batched"],
-                      "speedup_with_all_outputs": med["per_pair"] / med["batched_all"],
-                      "best_inliers": [int(x) for x in out[1].cpu().tolist()][:4]}))
+    sp = karms.spread(karms.time_eager(runs, stream, a.rounds, a.warmup))
+    med = sp["median_us"]
+    karms.emit({"tool": "kransac_batch", "pairs": n, "iterations": it, "rows": cap,
+                "matched_rows": [int((p[4] >= 0).sum()) for p in pairs][:2], "rounds": a.rounds, **sp,
+                "speedup": med["per_pair"] / med["batched"], "speedup_with_all_outputs": med["per_pair"] / med["batched_all"],
+                "best_inliers": [int(x) for x in out[1].cpu().tolist()][:4]})
 
 
 if __name__ == "__main__":

@@ -10,18 +10,16 @@ Prints one JSON line: medians with min-max, and `added_us` = median(RANSAC + ref
 few RANSAC + refit calls (for `rocprofv3 --kernel-trace --stats`: launches per call, kernel times).
 """
 import argparse
-import json
-import os
-import sys
+import statistics
 
 import numpy as np
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import torch  # noqa: E402
+import karms
+import torch
 
-import niftymatch_amd as nm  # noqa: E402
+import niftymatch_amd as nm
 
-from kransac_batch import TRUE_H, make_pair  # noqa: E402
+from kransac_batch import TRUE_H, make_pair
 
 
 def noisy_pair(rng, sigma):
@@ -39,11 +37,9 @@ def main():
     ap.add_argument("--pairs", type=int, default=16)
     ap.add_argument("--iterations", type=int, default=4096)
     ap.add_argument("--refit-rounds", type=int, default=2)
-    ap.add_argument("--rounds", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--threshold", type=float, default=4.0)
     ap.add_argument("--noise", type=float, default=0.5)
-    ap.add_argument("--trace", action="store_true")
+    karms.timing_args(ap, rounds=20, warmup=3, trace=True)
     a = ap.parse_args()
     assert torch.cuda.is_available(), "kransac_refit.py measures on a GPU"
     dev = torch.device("cuda:0")
@@ -75,7 +71,7 @@ def main():
             for _ in range(5):
                 both()
         torch.cuda.synchronize()
-        print(json.dumps({"tool": "kransac_refit", "trace_calls": 5, "pairs": n, "iterations": it, "refit_rounds": rr}))
+        karms.emit({"tool": "kransac_refit", "trace_calls": 5, "pairs": n, "iterations": it, "refit_rounds": rr})
         return
 
     with torch.cuda.stream(stream):
@@ -97,29 +93,16 @@ def main():
     err_in = [corner(h) for h in Hb.cpu().numpy()]
     err_out = [corner(h) for h in out[0].cpu().numpy()]
 
-    ev = lambda: torch.cuda.Event(enable_timing=True)
     runs = {"ransac": ransac, "ransac_refit": both, "refit": lambda: refit(last["r"][0], last["r"][3]),
             "refit_mask_rms": lambda: refit(last["r"][0], last["r"][3], want_mask=True, want_rms=True)}
-    times = {k: [] for k in runs}
-    with torch.cuda.stream(stream):
-        for r in range(a.warmup + a.rounds):
-            for name, fn in runs.items():
-                e0, e1 = ev(), ev()
-                e0.record(stream)
-                fn()
-                e1.record(stream)
-                e1.synchronize()
-                if r >= a.warmup:
-                    times[name].append(e0.elapsed_time(e1) * 1e3)
-    med = {k: float(np.median(v)) for k, v in times.items()}
-    spread = {k: [float(np.min(v)), float(np.max(v))] for k, v in times.items()}
-    print(json.dumps({"tool": "kransac_refit", "pairs": n, "iterations": it, "rows": cap, "refit_rounds": rr,
-                      "rounds": a.rounds, "median_us": med, "min_max_us": spread,
-                      "added_us": med["ransac_refit"] - med["ransac"],
-                      "added_over_ransac": (med["ransac_refit"] - med["ransac"]) / med["ransac"],
-                      "rounds_done": [int(x) for x in out[3].cpu().tolist()],
-                      "inliers_in_out": [[int(x) for x in best.cpu().tolist()][:4], [int(x) for x in out[1].cpu().tolist()][:4]],
-                      "corner_error_px_in_out": [float(np.median(err_in)), float(np.median(err_out))]}))
+    sp = karms.spread(karms.time_eager(runs, stream, a.rounds, a.warmup))
+    med = sp["median_us"]
+    karms.emit({"tool": "kransac_refit", "pairs": n, "iterations": it, "rows": cap, "refit_rounds": rr, "rounds": a.rounds, **sp,
+                "added_us": med["ransac_refit"] - med["ransac"],
+                "added_over_ransac": (med["ransac_refit"] - med["ransac"]) / med["ransac"],
+                "rounds_done": [int(x) for x in out[3].cpu().tolist()],
+                "inliers_in_out": [[int(x) for x in best.cpu().tolist()][:4], [int(x) for x in out[1].cpu().tolist()][:4]],
+                "corner_error_px_in_out": [float(statistics.median(err_in)), float(statistics.median(err_out))]})
 
 
 if __name__ == "__main__":

@@ -17,17 +17,14 @@ select / copy and full / selected. Not measured here: RANSAC and refit on full, 
 --trace runs only a few calls of each arm (for a kernel trace in a run of its own).
 """
 import argparse
-import json
-import os
-import sys
 
 import numpy as np
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import torch  # noqa: E402
+import karms
+import torch
 
-import niftymatch_amd as nm  # noqa: E402
-from niftymatch_amd import synth  # noqa: E402
+import niftymatch_amd as nm
+from niftymatch_amd import synth
 
 W, H, CAP = 1920, 1080, 16384
 GX, GY = 16, 9
@@ -36,10 +33,8 @@ GX, GY = 16, 9
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pairs", type=int, default=16)
-    ap.add_argument("--rounds", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--keep", type=int, default=2048)
-    ap.add_argument("--trace", action="store_true")
+    karms.timing_args(ap, rounds=20, warmup=3, trace=True)
     a = ap.parse_args()
     assert torch.cuda.is_available(), "kselect.py measures on a GPU"
     assert 1 <= a.pairs <= 32
@@ -109,7 +104,7 @@ def main():
                 for fn in arms.values():
                     fn()
         torch.cuda.synchronize()
-        print(json.dumps({"tool": "kselect", "trace_calls": 5, "pairs": n}))
+        karms.emit({"tool": "kselect", "trace_calls": 5, "pairs": n})
         return
 
     x0 = arenas[0]
@@ -120,27 +115,14 @@ def main():
         "device and host twin differ (frame 0)"
     assert np.array_equal(cpu(held["s64"]["desc"][0])[:c0].view(np.uint32), host["desc"][0][:c0].view(np.uint32))
 
-    ev = lambda: torch.cuda.Event(enable_timing=True)
-    times = {k: [] for k in arms}
-    with torch.cuda.stream(stream):
-        for rd in range(a.warmup + a.rounds):
-            for name, fn in arms.items():
-                e0, e1 = ev(), ev()
-                e0.record(stream)
-                fn()
-                e1.record(stream)
-                e1.synchronize()
-                if rd >= a.warmup:
-                    times[name].append(e0.elapsed_time(e1) * 1e3)
-    med = {k: float(np.median(v)) for k, v in times.items()}
+    sp = karms.spread(karms.time_eager(arms, stream, a.rounds, a.warmup))
+    med = sp["median_us"]
     moved = sum(rows[k % (2 * n)] * 512 + min(keep, rows[k % (2 * n)]) * 2 * (512 + 32 + 4) for k in range(64))
-    out = {"tool": "kselect", "pairs": n, "rounds": a.rounds, "keep": keep, "grid": [GX, GY], "rows": rows[:4],
-           "median_us": med, "min_max_us": {k: [float(np.min(v)), float(np.max(v))] for k, v in times.items()},
-           "select_over_copy": med["select_64_frames"] / med["copy_same_bytes"],
-           "select_us_per_frame": med["select_64_frames"] / 64, "select_bytes_per_s": moved / (med["select_64_frames"] * 1e-6),
-           "full_over_selected": med["full_match"] / med["select_and_match"],
-           "matches_pair0": {"full": int((full_res[0] >= 0).sum()), "selected": int((sel_res[0] >= 0).sum())}}
-    print(json.dumps(out))
+    karms.emit({"tool": "kselect", "pairs": n, "rounds": a.rounds, "keep": keep, "grid": [GX, GY], "rows": rows[:4], **sp,
+                "select_over_copy": med["select_64_frames"] / med["copy_same_bytes"],
+                "select_us_per_frame": med["select_64_frames"] / 64, "select_bytes_per_s": moved / (med["select_64_frames"] * 1e-6),
+                "full_over_selected": med["full_match"] / med["select_and_match"],
+                "matches_pair0": {"full": int((full_res[0] >= 0).sum()), "selected": int((sel_res[0] >= 0).sum())}})
     for x in arenas:
         x.close()
 
