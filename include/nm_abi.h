@@ -1768,6 +1768,73 @@ NM_API int nm_klt_sums_host(const float *pyrA, const float *pyrB, const unsigned
 NM_API int nm_klt_set_grid_cap(int cap);
 NM_API int nm_klt_set_lanes(int lanes);
 
+/* ---- Corner detection (no reference counterpart): Shi-Tomasi "good features to track" corners of gray planes, the points
+ * to hand to nm_klt_track_batch_dev_f32. The score is the tracker's own level-0 texture gate at integer pixel centres,
+ * where the sampler's weights are (65536, 0, 0, 0) and a sample is the pixel's level itself: a corner is a point the tracker
+ * will not call NM_KLT_FLAT or NM_KLT_BORDER at level 0. Everything summed is an integer and the fp64 steps are the gate's,
+ * so host and device agree bit for bit. The output (x, y, score, a device count) is what nm_sift_select_batch_dev takes
+ * (xs, ys, scores, d_counts) to spread the strongest `keep` over a grid, in source order:
+ *   ingest -> pyramid -> corners -> select -> track -> RANSAC -> refit
+ * on one stream, capturable into one HIP graph, with no host read and no host-made point table.
+ *
+ * nm_klt_corners_batch_dev_f32. Every table is a HOST table of device pointers, n in [1, NM_KLT_MAX_BATCH].
+ *   gray[k]      an fw x fh fp32 plane; a pyramid block is valid (level 0 lies at offset 0 and is the plane bit for bit);
+ *   mask         optional, fw x fh bytes, 1 = seen, one for all frames; a mask_pyr block is valid for the same reason;
+ *   held_x[k], held_y[k], d_held[k], cap_held   optional, all three tables or none: points the caller already tracks in
+ *                frame k, nH = clip(*d_held[k], 0, cap_held) read on the device; cap_held in [1, 2^22);
+ *   radius r in [1, NM_KLT_MAX_RADIUS]; nms in [1, NM_KLT_CORNERS_MAX_NMS]; min_eig >= 0 and finite; cap in [1, 2^22).
+ *   DEFINITION.
+ *     Level: q(x, y) = (int)rintf(v * 16.0f) when 0 <= v <= 255, else the pixel holds no level (a NaN holds none); with
+ *       mask, a pixel whose byte is 0 holds no level.
+ *     Window: a pixel (x, y) has a window when every pixel (x + u, y + v) with -(r+1) <= u, v <= r+2 lies in the plane and
+ *       holds a level: the tracker's template window of radius r + 1 at an integer centre plus its four corner pixels, so
+ *       "has a window" implies a valid level-0 template (the converse fails only at those four pixels).
+ *     Sums: gx(p) = q(p.x+1, p.y) - q(p.x-1, p.y), gy alike; Gxx = sum gx^2, Gxy = sum gx gy, Gyy = sum gy^2 over the
+ *       (2r+1)^2 pixels |u|, |v| <= r: the first three words of nm_klt_sums_host(level 0, px = x, py = y) exactly.
+ *       Gxx, Gyy <= 225 x 4080^2 = 3 745 440 000 fit an unsigned 32-bit word and no signed one; |Gxy| has the same bound
+ *       (33 bits signed).
+ *     Score: a pixel is scored when it has a window and the tracker's texture gate does not call it flat: det = Gxx Gyy -
+ *       Gxy Gxy is finite and > 0 and e = lam / (1024 (2r+1)^2) >= min_eig with
+ *       lam = ((Gxx + Gyy) - sqrt((Gxx - Gyy)^2 + 4 (Gxy Gxy))) / 2, the gate's fp64 operations in the gate's order; its
+ *       score is (float)e, one rounding. Every other pixel has score -1.
+ *     Corner: a scored pixel p is a corner when (1) for every other scored pixel p' at Chebyshev distance <= nms,
+ *       score(p) > score(p'), or the scores are equal and p comes first in raster order (y, then x); pixels that are not
+ *       scored do not compete; and (2) no tried held row lies within Chebyshev distance nms of p, measured from
+ *       (rintf(hx), rintf(hy)); a held row i is tried when i < nH, hx >= 0 and both coordinates are finite. Held pixels still
+ *       compete as neighbours: only their own corner status is removed.
+ *   Outputs (device): a frame's corners in raster order, x[k][j], y[k][j] whole-number floats, score[k][j]; with more than
+ *     cap corners the first cap in raster order; d_count[k] = min(total, cap); d_total[k] (optional) = total; both are
+ *     always written, 0 is a valid value; rows at and beyond the count are not written. score_plane[k] (optional table):
+ *     fw x fh floats, every pixel written. A frame's results depend on its own inputs alone: not on n, its slot,
+ *     scheduling, the grid cap or what the outputs or the workspace held before.
+ *   workspace: device, nm_klt_corners_workspace_bytes(n, fw, fh) bytes (0 for arguments out of range): a score plane per
+ *     frame, a 64-bit word of corner flags per 64 pixels of a row, a byte plane of held marks with a border of 16. No
+ *     contents expected or preserved.
+ *   Launches: THREE whatever n is (response, non-maximum suppression into the flag words, scan and write), FOUR with held
+ *     points (the marks, behind the response pass, which zeroes the mark planes). Nothing else is zeroed: every word the
+ *     call reads it has written. The order of the output comes from a scan of per-tile-row counts, never from an atomic.
+ *     No allocation, no synchronisation, no host read; no workgroup waits for another.
+ *   Refused with hipErrorInvalidValue before any launch or device access: n outside [1, 64], fw or fh outside [1, 32767],
+ *     radius, nms, cap or (with held points) cap_held out of range, a min_eig that is negative or not finite, a held triple
+ *     given in part, a NULL gray, x, y, score or d_count, a NULL among the first n entries of a given table, a NULL
+ *     workspace.
+ * nm_klt_corners_host_f32: the same with every pointer in host memory, no workspace and no stream: identical outputs.
+ * nm_klt_corners_set_grid_cap (tuning and tests, process-wide): every launch uses min(units, cap) workgroups; cap >= 1 fixes
+ *   the cap, any other value restores the default (8 per compute unit). Results are identical for every cap. Returns the
+ *   previous setting (0: the default).                                                                                  */
+#define NM_KLT_CORNERS_MAX_NMS 16
+NM_API size_t nm_klt_corners_workspace_bytes(int n, int fw, int fh);
+NM_API int nm_klt_corners_batch_dev_f32(int n, const float *const *gray, int fw, int fh, const unsigned char *mask,
+                                        const float *const *held_x, const float *const *held_y, const int *const *d_held,
+                                        int cap_held, int radius, int nms, float min_eig, int cap, float *const *x,
+                                        float *const *y, float *const *score, int *d_count, int *d_total,
+                                        float *const *score_plane, void *workspace, void *stream);
+NM_API int nm_klt_corners_host_f32(int n, const float *const *gray, int fw, int fh, const unsigned char *mask,
+                                   const float *const *held_x, const float *const *held_y, const int *const *held, int cap_held,
+                                   int radius, int nms, float min_eig, int cap, float *const *x, float *const *y,
+                                   float *const *score, int *count, int *total, float *const *score_plane);
+NM_API int nm_klt_corners_set_grid_cap(int cap);
+
 /* ---- Link proposal: which frame pairs of a sequence to link at all (no reference counterpart). Two steps, both on
  * `stream` with no allocation, no synchronisation and no host read -- capturable into a HIP graph.
  * nm_link_votes_dev_u8: the u8 matcher's ratio test for ALL ordered pairs of n in [1, NM_LINK_PROPOSE_MAX_FRAMES] frames,

@@ -188,6 +188,10 @@ _SIGNATURES = {
     "nm_klt_sums_host": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, C.c_double, C.c_double, C.c_double, C.c_double, _P, _P]),
     "nm_klt_set_grid_cap": (_I, [_I]),
     "nm_klt_set_lanes": (_I, [_I]),
+    "nm_klt_corners_workspace_bytes": (_SZ, [_I, _I, _I]),
+    "nm_klt_corners_batch_dev_f32": (_I, [_I, _P, _I, _I, _P, _P, _P, _P, _I, _I, _I, _F, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "nm_klt_corners_host_f32": (_I, [_I, _P, _I, _I, _P, _P, _P, _P, _I, _I, _I, _F, _I, _P, _P, _P, _P, _P, _P]),
+    "nm_klt_corners_set_grid_cap": (_I, [_I]),
     "nm_link_votes_workspace_bytes": (_SZ, [_I, _I]),
     "nm_link_votes_dev_u8": (_I, [_I, _P, _P, _I, _F, _P, _P, _P]),
     "nm_link_votes_host_u8": (_I, [_I, _P, _P, _I, _F, _P]),
@@ -3066,6 +3070,122 @@ def klt_grid_points(fw, fh, step, mask=None):
         keep = np.asarray(mask)[ys, xs] > 0.5
         xs, ys = xs[keep], ys[keep]
     return xs.astype(np.float32), ys.astype(np.float32)
+
+
+KLT_CORNERS_MAX_NMS = 16
+
+
+class KltCornersWorkspace(_PairWorkspace):
+    """Device scratch for nm_klt_corners_batch_dev_f32: n frames of fw x fh (a score plane, the corner flag words and the
+    held-point marks of every frame)."""
+    _bytes_fn, _what, _shape_text = "nm_klt_corners_workspace_bytes", "KLT corners workspace", "n=%d fw=%d fh=%d"
+
+    def __init__(self, n, fw, fh, device):
+        self._alloc(device, n=n, fw=fw, fh=fh)
+
+
+def klt_corners_workspace_bytes(n, fw, fh):
+    """Bytes of the workspace of klt_corners_batch (nm_klt_corners_workspace_bytes); 0 for arguments out of range."""
+    return int(lib().nm_klt_corners_workspace_bytes(int(n), int(fw), int(fh)))
+
+
+def klt_corners_set_grid_cap(cap=0):
+    """Tuning and tests: the most workgroups a launch of klt_corners_batch uses (nm_klt_corners_set_grid_cap); 0 restores the
+    default. Results do not depend on it. Returns the previous setting."""
+    return lib().nm_klt_corners_set_grid_cap(int(cap))
+
+
+def _klt_corners_check(what, grays, radius, nms, min_eig, cap, mask, held):
+    """(n, fw, fh, cap_held) of a corners call; shapes, dtypes and host values only, torch or numpy."""
+    grays = list(grays)
+    n = len(grays)
+    if not 0 < n <= KLT_MAX_BATCH:
+        raise NmError("%s: %d frames (1 .. %d)" % (what, n, KLT_MAX_BATCH))
+    fw, fh = _planes_check(what, grays, mask)
+    _size_check(what, "frame", fw, fh)
+    if any(not _is_dtype(g, "float32") for g in grays) or (mask is not None and not _is_dtype(mask, "uint8")):
+        raise NmError("%s: float32 planes and a uint8 mask expected" % what)
+    if int(radius) != radius or not 1 <= radius <= KLT_MAX_RADIUS or int(nms) != nms or not 1 <= nms <= KLT_CORNERS_MAX_NMS:
+        raise NmError("%s: radius %r outside [1, %d] or nms %r outside [1, %d]" % (what, radius, KLT_MAX_RADIUS, nms,
+                                                                                   KLT_CORNERS_MAX_NMS))
+    if not math.isfinite(min_eig) or min_eig < 0:
+        raise NmError("%s: min_eig %r must be finite and >= 0" % (what, min_eig))
+    if int(cap) != cap or not 1 <= cap < _PAIR_CAP_LIMIT:
+        raise NmError("%s: cap %r outside [1, %d)" % (what, cap, _PAIR_CAP_LIMIT))
+    cap_held = 0
+    if held is not None:
+        if len(held) != 3 or any(len(v) != n for v in held):
+            raise NmError("%s: held is (xs, ys, counts), each a list of n" % what)
+        cap_held = _pair_cap(None, list(held[0]) + list(held[1]))
+    return n, fw, fh, cap_held
+
+
+def klt_corners_batch(grays, radius=7, nms=8, min_eig=1.0, cap=4096, mask=None, held=None, want_score_plane=False, out=None,
+                      workspace=None):
+    """Shi-Tomasi corners of n = len(grays) <= KLT_MAX_BATCH float32 device planes of one (fh, fw) shape
+    (nm_klt_corners_batch_dev_f32): three launches on the current stream whatever n is, four with held points, no host
+    read. The score of a pixel is the tracker's own level-0 texture gate at that pixel (the smaller eigenvalue of the
+    window's gradient matrix per tap, gray^2, for the same radius), so with the same radius, min_eig and mask
+    klt_track_batch_dev calls no corner FLAT or BORDER at level 0. A corner is a scored pixel (score >= min_eig) that is the
+    strongest within Chebyshev distance nms, the first in raster order among equals. mask: a uint8 (fh, fw) plane, 1 =
+    seen (level 0 of a mask_pyr block: gray_pyramid_level(mask_pyr, fw, fh, 0)). held: (xs, ys, d_counts), lists of n float32
+    / float32 / int32 DEVICE tensors, the points a caller already tracks in each frame (survivors of the last frame): no
+    corner appears within nms of one. Returns a dict: "x", "y", "score" (lists of n float32 tensors of `cap` rows, the corners
+    in raster order, rows at and beyond the count not written), "count" and "total" (int32 (n,) device: min(total, cap) and
+    the total), "score_plane" (a list of n (fh, fw) planes, -1 where a pixel is not scored; None unless asked for). out: the
+    dict a former call returned, to write into the same tensors (what a graph capture needs, with a workspace). The chain:
+        c = klt_corners_batch(grays)
+        s = sift_select_batch_dev([c["count"][k:k + 1] for k in range(n)], c["x"], c["y"], fw, fh, scores=c["score"], keep=512)
+        t = klt_track_batch_dev(pyrAs, pyrBs, fw, fh, s["x"], s["y"], [s["count"][k:k + 1] for k in range(n)])
+    workspace: a KltCornersWorkspace (default: new)."""
+    torch = _torch()
+    grays = list(grays)
+    n, fw, fh, cap_held = _klt_corners_check("klt_corners_batch", grays, radius, nms, min_eig, cap, mask, held)
+    held_all = [t for ts in held for t in ts] if held is not None else []
+    device = _on_current_device(grays + held_all + [mask, workspace.buf if workspace is not None else None], "klt_corners_batch")
+    workspace = _pair_workspace(KltCornersWorkspace, workspace, device, n, fw, fh)
+    if out is None:
+        new = lambda: [torch.zeros(cap, dtype=torch.float32, device=device) for _ in range(n)]
+        out = dict(x=new(), y=new(), score=new(), count=torch.zeros(n, dtype=torch.int32, device=device),
+                   total=torch.zeros(n, dtype=torch.int32, device=device),
+                   score_plane=[torch.empty((fh, fw), dtype=torch.float32, device=device) for _ in range(n)]
+                   if want_score_plane else None)
+    if any(len(out[name]) != n for name in ("x", "y", "score")) or out["count"].numel() != n or out["total"].numel() != n or \
+            (out["score_plane"] is not None and
+             (len(out["score_plane"]) != n or any(tuple(p.shape) != (fh, fw) for p in out["score_plane"]))):
+        raise NmError("klt_corners_batch: `out` does not fit this call")
+    _pair_cap(cap, out["x"] + out["y"] + out["score"])
+    f, i32, tab = torch.float32, torch.int32, _pair_dev_table
+    hx, hy, hn = (tab(list(held[0]), f), tab(list(held[1]), f), tab(list(held[2]), i32)) if held is not None else (None,) * 3
+    _check(lib().nm_klt_corners_batch_dev_f32(n, tab(grays, f), fw, fh, _opt(mask, torch.uint8), hx, hy, hn, cap_held,
+                                              int(radius), int(nms), min_eig, int(cap), tab(out["x"], f), tab(out["y"], f),
+                                              tab(out["score"], f), _dev(out["count"], i32), _dev(out["total"], i32),
+                                              tab(out["score_plane"], f), _dev(workspace.buf), _stream()),
+           "nm_klt_corners_batch_dev_f32")
+    return out
+
+
+def klt_corners_host(grays, radius=7, nms=8, min_eig=1.0, cap=4096, mask=None, held=None, want_score_plane=False, fill=0):
+    """klt_corners_batch on the host (nm_klt_corners_host_f32, the same functions): numpy planes in, identical results.
+    held: (xs, ys, counts) with host ints as counts. Returns the same dict with (n, cap) float32 arrays "x", "y", "score"
+    (rows at and beyond a count hold `fill`), int32 (n,) "count" and "total", and "score_plane" (n, fh, fw) or None. The
+    chain: klt_corners_host -> sift_select_host(scores=...) -> klt_track_host."""
+    import numpy as np
+    grays = _pair_host_arrays(grays, np.float32, flat=False)
+    mask = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)
+    if held is not None and len(held) == 3:
+        held = (_pair_host_arrays(held[0], np.float32), _pair_host_arrays(held[1], np.float32), list(held[2]))
+    n, fw, fh, cap_held = _klt_corners_check("klt_corners_host", grays, radius, nms, min_eig, cap, mask, held)
+    x, y, score = (np.full((n, cap), fill, np.float32) for _ in range(3))
+    count, total = np.zeros(n, np.int32), np.zeros(n, np.int32)
+    plane = np.zeros((n, fh, fw), np.float32) if want_score_plane else None
+    arr, ptr = _pair_host_table, _pair_host_ptr
+    sizes = _pair_host_sizes(held[2]) if held is not None else None           # alive until the call returns
+    hx, hy, hn = (arr(held[0]), arr(held[1]), arr(sizes)) if held is not None else (None,) * 3
+    _check(lib().nm_klt_corners_host_f32(n, arr(grays), fw, fh, ptr(mask), hx, hy, hn, cap_held, int(radius), int(nms), min_eig,
+                                         int(cap), arr(list(x)), arr(list(y)), arr(list(score)), ptr(count), ptr(total),
+                                         None if plane is None else arr(list(plane))), "nm_klt_corners_host_f32")
+    return dict(x=x, y=y, score=score, count=count, total=total, score_plane=plane)
 
 
 SIFT_MAX_BATCH = 64

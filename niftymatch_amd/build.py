@@ -25,7 +25,7 @@ FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-fvisibility=h
 
 KERNEL_SOURCES = ["nm_pyramid.hip", "nm_keypoint.hip", "nm_describe.hip", "nm_match.hip", "nm_match_screen.hip", "nm_match_finish.hip", "nm_match_distance.hip", "nm_match_shard.hip", "nm_match_guided.hip", "nm_match_mutual.hip", "nm_pair_batch.hip",
                   "nm_desc_finish.hip", "nm_select.hip", "nm_match_u8.hip", "nm_match_mutual_u8.hip",
-                  "nm_image.hip", "nm_warp.hip", "nm_ransac.hip", "nm_ransac_batch.hip", "nm_ransac_refit.hip", "nm_link_verify.hip", "nm_link_refine.hip", "nm_link_propose.hip", "nm_mosaic.hip", "nm_mosaic_adjust.hip", "nm_mosaic_exposure.hip", "nm_mosaic_bands.hip", "nm_mosaic_median.hip", "nm_frame_weights.hip", "nm_frame_quality.hip", "nm_klt.hip", "nm_ingest.hip", "nm_selftest.hip"]
+                  "nm_image.hip", "nm_warp.hip", "nm_ransac.hip", "nm_ransac_batch.hip", "nm_ransac_refit.hip", "nm_link_verify.hip", "nm_link_refine.hip", "nm_link_propose.hip", "nm_mosaic.hip", "nm_mosaic_adjust.hip", "nm_mosaic_exposure.hip", "nm_mosaic_bands.hip", "nm_mosaic_median.hip", "nm_frame_weights.hip", "nm_frame_quality.hip", "nm_klt.hip", "nm_klt_corners.hip", "nm_ingest.hip", "nm_selftest.hip"]
 SIFT_SOURCES = ["nm_frame.hip", "nm_arena.hip", "nm_tail.hip"]
 KERNEL_CPP = ["kernels_api.cpp", "ransac.cpp"]
 SIFT_CPP = ["pyramidata.cpp", "siftdata.cpp", "siftfunctions.cpp", "nm_client.cpp"]

@@ -98,16 +98,24 @@ __host__ __device__ __forceinline__ int sample(const float *pl, const unsigned c
 // ---- the fp64 steps ----
 __host__ __device__ __forceinline__ bool finite_pos(double v) { return __builtin_isfinite(v) && v > 0.0; }
 
-// the texture gate; det is returned for the step
-__host__ __device__ __forceinline__ bool flat(i64 Gxx, i64 Gxy, i64 Gyy, int r, double min_eig, double &det)
+// the texture gate; det is returned for the step, eig (the smaller eigenvalue per tap, gray^2; 0 where det fails) for the
+// corner detector's score (nm_klt_corners_math.hpp)
+__host__ __device__ __forceinline__ bool flat(i64 Gxx, i64 Gxy, i64 Gyy, int r, double min_eig, double &det, double &eig)
 {
     const double a = (double)Gxx, b = (double)Gxy, c = (double)Gyy;
     const double t1 = a * c, t2 = b * b;
     det = t1 - t2;
+    eig = 0.0;
     if (!finite_pos(det)) return true;
     const double s = a + c, dd = a - c, q = dd * dd, f = 4.0 * t2, root = __builtin_sqrt(q + f);
     const double lam = (s - root) / 2.0;
-    return lam / (double)(1024 * (2 * r + 1) * (2 * r + 1)) < min_eig;
+    eig = lam / (double)(1024 * (2 * r + 1) * (2 * r + 1));
+    return eig < min_eig;
+}
+__host__ __device__ __forceinline__ bool flat(i64 Gxx, i64 Gxy, i64 Gyy, int r, double min_eig, double &det)
+{
+    double eig;
+    return flat(Gxx, Gxy, Gyy, r, min_eig, det, eig);
 }
 
 __host__ __device__ __forceinline__ void step(i64 Gxx, i64 Gxy, i64 Gyy, i64 bx, i64 by, double det, double &sx, double &sy)
